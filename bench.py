@@ -19,6 +19,11 @@ four error counters per step (reference main.cpp:174-182).  Two legs, SURVEY.md 
   strong (`strong` object):        the --groups groups are split into contiguous ranges of whole groups, one per rank
                                     (dist.shard_groups: 256 groups per GPU at N = 8).
 
+A plain run measures the headline only: set-up, --warmup steps, --steps timed steps, the result line.  The side measurements
+(the 3.6 / 4.2 dB points, cpu_baseline, the drop-in call shape and, N > 1, the strong leg) run only with --full.
+--dump-outputs DIR writes what the last timed step returned to its caller (hard decisions of a fixed sample of groups, the
+per-group iteration counts, the four error counters) as .npy files, so that two builds can be compared output for output.
+
 The CPU port under oracle/ is used here only for the cpu_baseline leg and its parity flag; it is never part of the
 measured path (`--launcher-selftest` is a CPU-only test of the spawn / shard / reduce plumbing and says so in its line).
 """
@@ -154,6 +159,10 @@ def parse_args(argv=None):
     ap.add_argument("--factor-2", type=int, default=None, help="Profile.txt Factor_2 (default: the shipped 6)")
     ap.add_argument("--mod-type", type=int, default=2, choices=[2, 4], help="Profile.txt modType: 2 QPSK, 4 16-QAM")
     ap.add_argument("--scale", type=float, default=13.0, help="Profile.txt scale (12.5 for the hybrid 2B1C decoder)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements: Eb/N0 points, cpu_baseline, drop-in call shape, strong leg (N > 1)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-points", action="store_true", help="skip the 3.6 / 4.2 dB side measurements")
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline leg")
     ap.add_argument("--no-dropin", action="store_true", help="skip the drop-in call-shape leg (host/dropin_bench)")
@@ -200,6 +209,34 @@ def launch_children(args, argv):
 
 
 # ---- worker ----------------------------------------------------------------------------------------------------------
+DUMP_GROUPS, DUMP_SEED = 16, 20240607
+
+
+def dump_outputs(out_dir, decoded, stats, counters, n_groups):
+    """--dump-outputs: what the caller of the timed path received from its last step, as float arrays (36 MB at most).
+      hard_decisions.npy         float32 [groups picked, 32 * N]: the decoded bits of a fixed sample of groups (the first,
+                                 the last and up to 14 drawn with a fixed seed: the whole batch would be 4.6 GB as float32)
+      hard_decisions_groups.npy  float64: the indices of those groups
+      group_stats.npy            float64 [n_groups, 2]: layered and bit-flipping iterations of every group
+      counters.npy               float64 [4]: TestFrame, ErrorFrame, ErrorBits, LT3ErrBitFrame of the step"""
+    import numpy as np
+    rng = np.random.default_rng(DUMP_SEED)
+    inner = np.arange(1, n_groups - 1)
+    picked = rng.choice(inner, size=min(inner.size, DUMP_GROUPS - 2), replace=False) if inner.size else inner
+    groups = np.unique(np.concatenate([[0, n_groups - 1], picked]))
+    rows = decoded.reshape(n_groups, 32 * N_VAR)
+    if hasattr(rows, "cpu"):  # a torch tensor on the GPU: copy only the picked groups
+        import torch
+        rows = rows.index_select(0, torch.as_tensor(groups, device=rows.device)).cpu().numpy()
+    else:
+        rows = rows[groups]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "hard_decisions.npy"), rows.astype(np.float32))
+    np.save(os.path.join(out_dir, "hard_decisions_groups.npy"), groups.astype(np.float64))
+    np.save(os.path.join(out_dir, "group_stats.npy"), np.asarray(stats, dtype=np.float64))
+    np.save(os.path.join(out_dir, "counters.npy"), np.asarray(counters, dtype=np.float64))
+
+
 class SelftestDecoder:
     """--launcher-selftest only: the CPU port behind the Decoder interface the worker uses (numpy arrays instead of
     device pointers).  Exists so that the spawn / shard / all-reduce plumbing can be tested without a GPU."""
@@ -343,13 +380,13 @@ def worker(args):
             d_stats = torch.zeros((n_groups, 2), dtype=torch.int32, device=device)
             torch.cuda.synchronize()
         totals, local = None, None
-        host_stats = None
+        host_out, host_stats = None, None
 
         def step():
-            nonlocal totals, local, host_stats
+            nonlocal totals, local, host_out, host_stats
             if selftest:
-                out, host_stats = dec.decode(fix, n_groups)
-                local = dec.count(out, n_groups)
+                host_out, host_stats = dec.decode(fix, n_groups)
+                local = dec.count(host_out, n_groups)
             else:
                 dec.decode_device(d_fix.data_ptr(), n_groups, d_out.data_ptr(), d_stats.data_ptr())
                 local = dec.count_errors_device(d_out.data_ptr(), None, n_groups)
@@ -382,12 +419,17 @@ def worker(args):
                     per_rank_counters=per_rank, per_rank_ms=per_rank_ms, n_groups=n_groups,
                     rows_per_lane=(0 if selftest else dec.rows_per_lane()),
                     message_store=(0 if selftest else dec.message_store()),
-                    waves=(1 if selftest else dec.kernel_waves()))
+                    waves=(1 if selftest else dec.kernel_waves()),
+                    decoded=(host_out if selftest else d_out), stats=stats)
 
     # ---- weak leg = headline ---------------------------------------------------------------------------------------
     n_groups = args.groups
     n_cw = n_groups * 32
     head = run_point(args.eb_n0, args.steps, args.warmup, n_groups, 1234 + 7919 * rank)
+    decoded = head.pop("decoded")
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, decoded, head["stats"], head["counters"], n_groups)
+    del decoded
     info_bits = float(world) * n_cw * K_INFO * args.steps
     value = info_bits / head["dt"] / 1e9
     avg_launch_ms = head["kernel_ms"] / max(1, head["launches"])
@@ -522,7 +564,7 @@ def worker(args):
         result["invalid_for_measurement"] = True
 
     # ---- strong leg: the same number of groups in total, split into contiguous ranges of whole groups ---------------
-    if world > 1 and not args.no_strong:
+    if world > 1 and args.full and not args.no_strong:
         first, last = lnsfaid_dist.shard_groups(args.groups, rank, world)
         if last > first:
             sp = run_point(args.eb_n0, args.steps, 1, last - first, 4321 + 7919 * rank)
@@ -545,7 +587,7 @@ def worker(args):
                 "per_rank_ms_per_step": sp["per_rank_ms"],
             }
 
-    if rank == 0 and world == 1 and not args.no_points and not selftest:
+    if rank == 0 and world == 1 and args.full and not args.no_points and not selftest:
         pts = []
         for eb in ((3.6, 4.2) if args.mod_type == 2 else (8.1, 8.6)):
             torch.cuda.empty_cache()
@@ -556,7 +598,7 @@ def worker(args):
                         "algorithmic_GBs": round(p["alg_bytes"] / (p["kernel_ms"] * 1e-3) / 1e9, 2)})
         result["points"] = pts
 
-    if rank == 0 and world == 1 and not args.no_cpu and not selftest:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu and not selftest:
         # cpu_baseline: the AVX2 port (oracle/, test infrastructure - imported here and nowhere else in the GPU legs) on ALL host
         # cores this process may use, one group stream per thread, at the three Eb/N0 points.  Per point the sample is the whole
         # batch the GPU has just decoded (every frame compared with the GPU's), and the pass is repeated until the point has
@@ -606,7 +648,7 @@ def worker(args):
                     "build is not possible here (it needs Intel MKL's mkl.h)",
         }
 
-    if rank == 0 and world == 1 and not args.no_dropin and not selftest and args.method in (1, 2, 5):
+    if rank == 0 and world == 1 and args.full and not args.no_dropin and not selftest and args.method in (1, 2, 5):
         # The decoder in the reference's OWN call shape (not `value`): T host threads, one context each, ONE group of 32 frames
         # per lnsfaid_decode call on pageable host buffers - what an unmodified CSimulate::Run does through the binding of
         # INTEGRATION.md section 2 (reference CSimulate.cpp:136-164, main.cpp:164-172).  host/dropin_bench is run as a child

@@ -6,6 +6,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 import oracle_abi as oa
@@ -74,7 +75,7 @@ def test_bench_launcher_spawns_one_worker_per_rank():
     """`python bench.py --gpus 2` with no launcher around it: the parent starts two fresh workers (torch.distributed.run),
     the weak leg gives every rank its own groups, the strong leg splits the groups, counters are all-reduced (gloo here;
     the CPU port stands in for the GPU library: this checks the plumbing, not the kernels)."""
-    d = _bench_line(["--gpus", "2", "--launcher-selftest", "--groups", "4", "--steps", "1", "--warmup", "0", "--eb-n0", "3.5"])
+    d = _bench_line(["--gpus", "2", "--launcher-selftest", "--full", "--groups", "4", "--steps", "1", "--warmup", "0", "--eb-n0", "3.5"])
     assert d["n_gpus"] == 2 and d["scaling"] == "weak" and d["invalid_for_measurement"] is True
     cfg = d["config"]
     assert cfg["world_size"] == 2 and len(cfg["per_rank_counters"]) == 2
@@ -93,7 +94,7 @@ def test_bench_two_ranks_through_the_hip_library():
     ranks share the device and the counters travel over gloo (RCCL refuses two ranks on one device)."""
     import torch
     two = torch.cuda.device_count() >= 2
-    argv = ["--gpus", "2", "--groups", "64", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-points"]
+    argv = ["--gpus", "2", "--full", "--groups", "64", "--steps", "2", "--warmup", "1", "--no-cpu", "--no-points"]
     if not two:
         argv += ["--share-gpu", "--backend", "gloo"]
     d = _bench_line(argv)
@@ -114,3 +115,21 @@ def test_bench_single_gpu_through_the_launcher():
     assert d["n_gpus"] == 1 and d["config"]["backend"] == "nccl"
     assert d["config"]["reduce"] == "lnsfaid_allreduce_counters"  # RCCL communicator of one rank, through the C ABI
     assert d["config"]["counters_TestFrame_ErrorFrame_ErrorBits_LT3"][0] == 64 * 32
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path):
+    """A plain run has no side legs; --dump-outputs writes the last timed step's outputs, the same for the same arguments
+    whatever --steps is (CPU port standing in for the GPU library, as above)."""
+    argv = ["--gpus", "2", "--launcher-selftest", "--groups", "4", "--warmup", "0", "--eb-n0", "3.5", "--dump-outputs"]
+    d = _bench_line(["--steps", "2"] + argv + [str(tmp_path / "a")])
+    assert d["steps"] == 2 and d["ms_per_step"] > 0 and "strong" not in d
+    _bench_line(["--steps", "1"] + argv + [str(tmp_path / "b")])
+    names = ["counters", "group_stats", "hard_decisions", "hard_decisions_groups"]
+    assert sorted(p.stem for p in (tmp_path / "a").iterdir()) == names
+    for name in names:
+        a, b = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), name
+    assert sum(p.stat().st_size for p in (tmp_path / "a").iterdir()) <= 64 << 20
+    assert np.load(tmp_path / "a" / "counters.npy").tolist() == d["config"]["counters_TestFrame_ErrorFrame_ErrorBits_LT3"]
+    assert np.load(tmp_path / "a" / "hard_decisions.npy").shape == (4, 32 * 17664)
+    assert np.load(tmp_path / "a" / "group_stats.npy").shape == (4, 2)

@@ -25,15 +25,10 @@ def test_code_table_matches_reference_digest(code50):
 
 
 def test_code_table_matches_reference_header_text(code50):
-    """Only in the build container: compare with the header the reference ships (read as text)."""
-    path = "/root/reference/Constants/50GPON-dc-original/Constants_SSE.h"
-    if not os.path.exists(path):
-        import pytest
-        pytest.skip("reference not mounted")
-    txt = open(path).read()
-    i = txt.index("{", txt.index("_PosNoeudsVariable_"))
-    body = re.sub(r"/\*.*?\*/", "", txt[i + 1:txt.index("};", i)])
-    ref = np.array([int(x) for x in re.findall(r"\d+", body)], dtype=np.uint16)
+    """Compare with the table the reference ships in its header, parsed from the text into
+    tests/golden/pos_noeuds_variable.npy by tools/extract_pos_table.py."""
+    ref = np.load(os.path.join(GOLD, "pos_noeuds_variable.npy"))
+    assert ref.dtype == np.uint16 and ref.shape == (70400,)
     assert np.array_equal(ref, np.ctypeslib.as_array(code50.pos_vn))
 
 

@@ -1,5 +1,5 @@
 # usage: tools/gpu_variants.sh "name1:-DFLAG1 -DFLAG2" "name2:..."   (run on the GPU box through gpurun)
-# POINTS=" " adds the 3.6 / 4.2 dB side measurements.  Rebuilds csrc/liblnsfaid.so with EXTRA flags per variant (the Makefile's flags
+# POINTS=--full adds the 3.6 / 4.2 dB side measurements.  Rebuilds csrc/liblnsfaid.so with EXTRA flags per variant (the Makefile's flags
 # stamp makes every object follow), prints the headline bench of each, and ALWAYS ends on the default build again - also when a
 # variant fails to build or to run - so that nothing after it in the same tree uses a variant library by accident.
 cd $GRAFT_REPO_ROOT
