@@ -236,6 +236,40 @@ int lnsfaid_frontend_set_interleave(lnsfaid_ctx* ctx, int32_t interleave_mod_typ
 int lnsfaid_frontend_set_frames(lnsfaid_ctx* ctx, const int8_t* outputBits, const int8_t* inputBits, size_t n_streams);
 int lnsfaid_frontend_input_bits(lnsfaid_ctx* ctx, const int8_t** d_inputBits);
 
+/* ---- systematic encoder and device frame source (replaces CLDPC::Encode, reference CLDPC.cpp:68-155) ---------------
+ * H = [A | B], B = the last n_check columns.  The parity bits of information bits u are p = B^-1 A u; B^-1 is derived from the
+ * code table (the reference's GenMatrix is not shipped) lazily, at the first lnsfaid_encode* / lnsfaid_frontend_random_frames
+ * call of a context, and kept on its device.  For a code whose parity part is singular these three calls return
+ * LNSFAID_E_CODE; decoding is not affected. */
+
+/* Host only, no GPU: the compact inverse of the parity part of H (the last n_check columns).  B^-1 is block-circulant, so the
+ * first row of each z x z block describes it:
+ *   circ[(a * mb + b) * (z / 8) + c / 8] bit (c % 8) = entry (a*z, b*z + c) of B^-1, mb = n_check / z.
+ * LNSFAID_E_CODE if the code is not quasi-cyclic (same rule as lnsfaid_create) or B is singular;
+ * LNSFAID_E_INVAL if bytes < mb * mb * z / 8. */
+int lnsfaid_code_parity_inverse(const lnsfaid_code* code, uint8_t* circ, size_t bytes);
+
+/* Replaces CLDPC::Encode (reference CLDPC.cpp:68-155) for n_groups groups:
+ *   inputBits  [32][K] per group (int8 0/1), group g at g * 32 * K
+ *   outputBits [32][K] then [32][M] per group, group g at g * 32 * n_var: the layout of CLDPC::outputBits and of
+ *              lnsfaid_frontend_set_frames
+ * _device: device pointers on the context's GPU (any byte offset); plain: host pointers, staged through the context's
+ * buffers of lnsfaid_io_buffers (their content is overwritten).  n_groups 0: no-op; more than max_groups: LNSFAID_E_INVAL.
+ * Both return when the output is complete. */
+int lnsfaid_encode_device(lnsfaid_ctx* ctx, const int8_t* d_inputBits, size_t n_groups, int8_t* d_outputBits);
+int lnsfaid_encode(lnsfaid_ctx* ctx, const int8_t* inputBits, size_t n_groups, int8_t* outputBits);
+
+/* lnsfaid_frontend_set_frames without host buffers: draws the message bits of n_streams groups on the device from keys[s],
+ * encodes them, and leaves both where set_frames leaves its copies.  The following lnsfaid_frontend_device* calls with
+ * codeword = NULL send these frames, and lnsfaid_frontend_input_bits returns the message bits for
+ * lnsfaid_count_errors_device; lnsfaid_frontend_set_frames(NULL) returns to one codeword for all, set_frames with host
+ * buffers replaces them.  Returns when the frames are on the device.
+ * Message generator (stateless, counter-based, bit-sliced by construction):
+ *   mix64(x):  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9; x ^= x >> 27; x *= 0x94D049BB133111EB; x ^= x >> 31  (splitmix64 finaliser)
+ *   stream s, information position j (0 <= j < K):  h = mix64(mix64(keys[s]) + (j + 1) * 0x9E3779B97F4A7C15)  (mod 2^64)
+ *   frame l (l < 32) of stream s carries information bit j = (h >> l) & 1. */
+int lnsfaid_frontend_random_frames(lnsfaid_ctx* ctx, const uint64_t* keys, size_t n_streams);
+
 /* The context's own device staging buffers (each max_groups * 32 * n_var bytes): the fixInput buffer the
  * host-pointer entry points copy into and the decodedBits buffer they copy out of.  A host driver without its own
  * device allocator (host/CLDPC.cpp) runs front-end -> decode -> counters on them with the *_device entry points. */

@@ -38,6 +38,9 @@ extern "C" hipError_t lf_launch_frontend(const uint32_t* d_seeds, const unsigned
                                          int n_check, int interleave, int fast, int8_t* d_fix, hipStream_t stream);
 extern "C" hipError_t lf_frontend_fastpath_scan(double* d_out2, hipStream_t stream);
 extern "C" void lf_frontend_fastpath_assumed(double* eps2);
+extern "C" hipError_t lf_launch_encode(const LfDevCode* d_code, int n_check, const uint32_t* d_bsup, const uint32_t* d_bsup_off,
+                                       const int8_t* d_in, const unsigned long long* d_keys, size_t n_groups, int8_t* d_out,
+                                       int8_t* d_info, hipStream_t stream);
 
 #include <atomic>
 #include <chrono>
@@ -127,6 +130,11 @@ struct lnsfaid_ctx {
     size_t fe_frames_streams = 0;  /* 0: frames not in use */
     int fe_interleave = 1;         /* InterleaveModType of the device front-end */
     int fe_exact = 0;              /* 1: every symbol through the double-precision chain (lnsfaid_frontend_set_exact) */
+    /* encoder (lnsfaid_encoder.hip): support of B^-1's first rows, derived at the first encode / random-frames call */
+    int enc_state = 0;                      /* 0: not derived yet, 1: on the device, LNSFAID_E_CODE: parity part singular */
+    uint32_t* d_enc_sup = nullptr;          /* entries b * z + c, block row after block row */
+    uint32_t* d_enc_off = nullptr;          /* [mb + 1] start of every block row's entries */
+    unsigned long long* d_fe_keys = nullptr; /* stream keys of lnsfaid_frontend_random_frames */
 };
 
 /* wait until everything queued on the context's stream so far has finished */
@@ -326,6 +334,7 @@ extern "C" void lnsfaid_destroy(lnsfaid_ctx* ctx)
     (void)hipFree(ctx->d_io_in); (void)hipFree(ctx->d_io_out); (void)hipFree(ctx->d_io_stats);
     (void)hipFree(ctx->d_fe_seeds); (void)hipFree(ctx->d_fe_draws); (void)hipFree(ctx->d_fe_codeword);
     (void)hipFree(ctx->d_fe_frames); (void)hipFree(ctx->d_fe_input);
+    (void)hipFree(ctx->d_enc_sup); (void)hipFree(ctx->d_enc_off); (void)hipFree(ctx->d_fe_keys);
     if (ctx->h_remaining) (void)hipHostFree(ctx->h_remaining);
     if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -994,16 +1003,23 @@ extern "C" int lnsfaid_frontend_set_interleave(lnsfaid_ctx* ctx, int32_t interle
     return LNSFAID_OK;
 }
 
+/* the per-stream frame buffers of the device front-end (lnsfaid_frontend_set_frames / lnsfaid_frontend_random_frames) */
+static int alloc_fe_frames(lnsfaid_ctx* ctx)
+{
+    if (!ctx->d_fe_frames) {
+        HIP_TRY(hipMalloc(&ctx->d_fe_frames, ctx->max_groups * LNSFAID_GROUP * (size_t)ctx->n_var));
+        HIP_TRY(hipMalloc(&ctx->d_fe_input, ctx->max_groups * LNSFAID_GROUP * (size_t)ctx->k_info));
+    }
+    return LNSFAID_OK;
+}
+
 extern "C" int lnsfaid_frontend_set_frames(lnsfaid_ctx* ctx, const int8_t* outputBits, const int8_t* inputBits, size_t n_streams)
 {
     if (!ctx || n_streams > ctx->max_groups) return LNSFAID_E_INVAL;
     if (!outputBits || n_streams == 0) { ctx->fe_frames_streams = 0; return LNSFAID_OK; } /* back to one codeword for all */
     if (!inputBits) return LNSFAID_E_INVAL;
     HIP_TRY(hipSetDevice(ctx->device));
-    if (!ctx->d_fe_frames) {
-        HIP_TRY(hipMalloc(&ctx->d_fe_frames, ctx->max_groups * LNSFAID_GROUP * (size_t)ctx->n_var));
-        HIP_TRY(hipMalloc(&ctx->d_fe_input, ctx->max_groups * LNSFAID_GROUP * (size_t)ctx->k_info));
-    }
+    { const int rc = alloc_fe_frames(ctx); if (rc) return rc; }
     HIP_TRY(hipMemcpyAsync(ctx->d_fe_frames, outputBits, n_streams * LNSFAID_GROUP * (size_t)ctx->n_var, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipMemcpyAsync(ctx->d_fe_input, inputBits, n_streams * LNSFAID_GROUP * (size_t)ctx->k_info, hipMemcpyHostToDevice, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream));
@@ -1223,6 +1239,156 @@ extern "C" int lnsfaid_frontend_device(lnsfaid_ctx* ctx, const uint32_t* seeds, 
     }
     for (size_t i = 0; i < n_streams; ++i) st[3 * i] = st[3 * i + 1] = st[3 * i + 2] = seeds[i];
     return lnsfaid_frontend_device_states(ctx, st.data(), draws_before, n_streams, mod_type, sigma, scale, codeword, d_fixInput);
+}
+
+/* ---- systematic encoder (lnsfaid_encoder.hip) ----------------------------------------------
+ * B = the last n_check columns of H is block-circulant, so B^-1 is too: one first row per block describes it.  Rows a z of
+ * B^-1 solve B^T x = e_{a z}: one Gauss-Jordan elimination of B^T (bit-packed rows, the mb right-hand sides in one extra
+ * word) gives all of them.  0.1 s for the 50G-PON code on one core. */
+static int parity_inverse(const LfDevCode& code, uint8_t* circ)
+{
+    const int Z = LF_Z, M = code.n_check, K = code.k_info, mb = M / Z, kb = K / Z, W = M / 64 + 1; /* mb <= LF_MAX_BR <= 64 */
+    std::vector<uint64_t> m;
+    try {
+        m.assign((size_t)M * W, 0);
+    } catch (...) {
+        return LNSFAID_E_NOMEM;
+    }
+    /* row c of B^T = column c of B: block row br, circulant of block column cb >= kb with shift sh has B[br z + i][(cb - kb) z + (sh + i) mod z] */
+    for (int br = 0; br < code.nbr; ++br)
+        for (int j = 0; j < code.deg[br]; ++j) {
+            const int cb = (int)(code.circ[br][j].sb / (uint32_t)Z), sh = (int)(code.circ[br][j].sb % (uint32_t)Z);
+            if (cb < kb) continue;
+            for (int i = 0; i < Z; ++i) {
+                const size_t c = (size_t)(cb - kb) * Z + (size_t)((sh + i) % Z), r = (size_t)br * Z + (size_t)i;
+                m[c * W + r / 64] ^= 1ull << (r % 64);
+            }
+        }
+    for (int a = 0; a < mb; ++a) m[(size_t)a * Z * W + (size_t)(W - 1)] |= 1ull << a;
+    std::vector<uint64_t> tmp((size_t)W);
+    for (int col = 0; col < M; ++col) {
+        const size_t w = (size_t)col / 64;
+        const uint64_t bit = 1ull << (col % 64);
+        int piv = -1;
+        for (int r = col; r < M; ++r)
+            if (m[(size_t)r * W + w] & bit) { piv = r; break; }
+        if (piv < 0) return LNSFAID_E_CODE; /* singular */
+        if (piv != col) {
+            memcpy(tmp.data(), &m[(size_t)col * W], sizeof(uint64_t) * W);
+            memcpy(&m[(size_t)col * W], &m[(size_t)piv * W], sizeof(uint64_t) * W);
+            memcpy(&m[(size_t)piv * W], tmp.data(), sizeof(uint64_t) * W);
+        }
+        const uint64_t* prow = &m[(size_t)col * W];
+        for (int r = 0; r < M; ++r) {
+            uint64_t* row = &m[(size_t)r * W];
+            if (r == col || !(row[w] & bit)) continue;
+            for (size_t x = w; x < (size_t)W; ++x) row[x] ^= prow[x]; /* words left of the pivot are zero in prow */
+        }
+    }
+    /* row r now holds x_r: bit a = entry (a z, r) of B^-1 */
+    memset(circ, 0, (size_t)mb * mb * (Z / 8));
+    for (int a = 0; a < mb; ++a)
+        for (int r = 0; r < M; ++r)
+            if ((m[(size_t)r * W + (size_t)(W - 1)] >> a) & 1u) {
+                const int b = r / Z, c = r % Z;
+                circ[((size_t)a * mb + (size_t)b) * (Z / 8) + (size_t)(c / 8)] |= (uint8_t)(1u << (c % 8));
+            }
+    return LNSFAID_OK;
+}
+
+extern "C" int lnsfaid_code_parity_inverse(const lnsfaid_code* code, uint8_t* circ, size_t bytes)
+{
+    if (!code || !circ) return LNSFAID_E_INVAL;
+    LfDevCode* c = new (std::nothrow) LfDevCode(); /* ~90 KiB: not on the caller's stack */
+    if (!c) return LNSFAID_E_NOMEM;
+    int rc = build_code(code, c);
+    if (!rc) {
+        const size_t mb = (size_t)c->nbr;
+        rc = bytes < mb * mb * (LF_Z / 8) ? LNSFAID_E_INVAL : parity_inverse(*c, circ);
+    }
+    delete c;
+    return rc;
+}
+
+/* B^-1 of the context's code on the device, derived at the first call that needs it; a singular parity part is remembered */
+static int ensure_encoder(lnsfaid_ctx* ctx)
+{
+    if (ctx->enc_state == 1) return LNSFAID_OK;
+    if (ctx->enc_state < 0) return ctx->enc_state;
+    const int mb = ctx->hcode.nbr, Z = LF_Z;
+    std::vector<uint8_t> circ;
+    std::vector<uint32_t> sup, off;
+    try {
+        circ.assign((size_t)mb * mb * (Z / 8), 0);
+        off.reserve((size_t)mb + 1);
+        sup.reserve((size_t)mb * mb * Z / 2);
+    } catch (...) {
+        return LNSFAID_E_NOMEM;
+    }
+    const int rc = parity_inverse(ctx->hcode, circ.data());
+    if (rc == LNSFAID_E_CODE) ctx->enc_state = rc;
+    if (rc) return rc;
+    off.push_back(0);
+    for (int a = 0; a < mb; ++a) {
+        for (int b = 0; b < mb; ++b)
+            for (int c = 0; c < Z; ++c)
+                if ((circ[((size_t)a * mb + (size_t)b) * (Z / 8) + (size_t)(c / 8)] >> (c % 8)) & 1u) sup.push_back((uint32_t)(b * Z + c));
+        off.push_back((uint32_t)sup.size());
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMalloc(&ctx->d_enc_sup, sup.size() * sizeof(uint32_t)));
+    HIP_TRY(hipMalloc(&ctx->d_enc_off, off.size() * sizeof(uint32_t)));
+    HIP_TRY(hipMemcpy(ctx->d_enc_sup, sup.data(), sup.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(ctx->d_enc_off, off.data(), off.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+    ctx->enc_state = 1;
+    return LNSFAID_OK;
+}
+
+extern "C" int lnsfaid_encode_device(lnsfaid_ctx* ctx, const int8_t* d_inputBits, size_t n_groups, int8_t* d_outputBits)
+{
+    if (!ctx || (n_groups && (!d_inputBits || !d_outputBits)) || n_groups > ctx->max_groups) return LNSFAID_E_INVAL;
+    if (n_groups == 0) return LNSFAID_OK;
+    const int rc = ensure_encoder(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(lf_launch_encode(ctx->d_code, ctx->n_check, ctx->d_enc_sup, ctx->d_enc_off, d_inputBits, nullptr, n_groups, d_outputBits,
+                             nullptr, ctx->stream));
+    return stream_wait(ctx);
+}
+
+extern "C" int lnsfaid_encode(lnsfaid_ctx* ctx, const int8_t* inputBits, size_t n_groups, int8_t* outputBits)
+{
+    if (!ctx || (n_groups && (!inputBits || !outputBits)) || n_groups > ctx->max_groups) return LNSFAID_E_INVAL;
+    if (n_groups == 0) return LNSFAID_OK;
+    int rc = ensure_encoder(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    rc = ensure_io(ctx);
+    if (rc) return rc;
+    /* the staging buffers of the decode path: [32][K] per group fits in the fixInput buffer */
+    HIP_TRY(hipMemcpyAsync(ctx->d_io_in, inputBits, n_groups * LNSFAID_GROUP * (size_t)ctx->k_info, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(lf_launch_encode(ctx->d_code, ctx->n_check, ctx->d_enc_sup, ctx->d_enc_off, ctx->d_io_in, nullptr, n_groups, ctx->d_io_out,
+                             nullptr, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(outputBits, ctx->d_io_out, n_groups * LNSFAID_GROUP * (size_t)ctx->n_var, hipMemcpyDeviceToHost, ctx->stream));
+    return stream_wait(ctx);
+}
+
+extern "C" int lnsfaid_frontend_random_frames(lnsfaid_ctx* ctx, const uint64_t* keys, size_t n_streams)
+{
+    if (!ctx || (n_streams && !keys) || n_streams > ctx->max_groups) return LNSFAID_E_INVAL;
+    if (n_streams == 0) return LNSFAID_OK;
+    int rc = ensure_encoder(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    rc = alloc_fe_frames(ctx);
+    if (rc) return rc;
+    if (!ctx->d_fe_keys) HIP_TRY(hipMalloc(&ctx->d_fe_keys, ctx->max_groups * sizeof(unsigned long long)));
+    HIP_TRY(hipMemcpyAsync(ctx->d_fe_keys, keys, n_streams * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(lf_launch_encode(ctx->d_code, ctx->n_check, ctx->d_enc_sup, ctx->d_enc_off, nullptr, ctx->d_fe_keys, n_streams,
+                             ctx->d_fe_frames, ctx->d_fe_input, ctx->stream));
+    HIP_TRY(hipStreamSynchronize(ctx->stream)); /* keys may be reused by the caller */
+    ctx->fe_frames_streams = n_streams;
+    return LNSFAID_OK;
 }
 
 /* ---- multi-GPU: one process (or host thread) per GPU, the four counters summed over RCCL ---------------------------

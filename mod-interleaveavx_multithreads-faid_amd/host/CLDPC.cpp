@@ -152,6 +152,14 @@ void CLDPC::DeviceFrames(int decode_method, bool per_stream_frames, int interlea
     if (rc) die("lnsfaid_frontend_set_frames", rc);
 }
 
+void CLDPC::DeviceRandomFrames(int decode_method, const uint64_t* keys, int interleave_mod_type)
+{
+    lnsfaid_ctx* ctx = context(decode_method);
+    if (lnsfaid_frontend_set_interleave(ctx, interleave_mod_type)) die("lnsfaid_frontend_set_interleave", LNSFAID_E_INVAL);
+    const int rc = lnsfaid_frontend_random_frames(ctx, keys, (size_t)m_groups);
+    if (rc) die("lnsfaid_frontend_random_frames", rc);
+}
+
 void CLDPC::DeviceChannel(int decode_method, const uint32_t* states, const uint64_t* draws_before, int mod_type, float sigma,
                           float scale)
 {

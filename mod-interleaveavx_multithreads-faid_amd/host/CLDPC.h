@@ -66,6 +66,9 @@ public:
     /* with per_stream_frames the device front-end sends outputBits (after Encode) instead of the all-zero codeword and
      * CalculateErrors compares with inputBits */
     void DeviceFrames(int decode_method, bool per_stream_frames, int interleave_mod_type = 1);
+    /* --device-encode: the m_groups streams' messages drawn on the device from keys[s] and encoded there
+     * (lnsfaid_frontend_random_frames); the device front-end then sends them and CalculateErrors compares with them */
+    void DeviceRandomFrames(int decode_method, const uint64_t* keys, int interleave_mod_type = 1);
     /* states: RS.IX, RS.IY, RS.IZ per group (3 words each) at draws_before = 0 */
     void DeviceChannel(int decode_method, const uint32_t* states, const uint64_t* draws_before, int mod_type, float sigma,
                        float scale);

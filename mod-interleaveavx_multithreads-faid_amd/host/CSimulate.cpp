@@ -84,38 +84,48 @@ void CSimulate::Run()
     auto code_bit = [N, I](int p) { return (N / I) * (p % I) + p / I; };
     /* FAKE_ENCODE (the reference's default, CSimulate.cpp:103-104: GenMatrix is not shipped) or, with --encode, random
      * information bits through the encoder derived from the code table (reference #else branch :106-107) */
-    if (encode) { ldpc->GenMsgSeq(); ldpc->Encode(); }
-    else ldpc->FakeEncoder();
-    /* interleave + modulate once per 50 calls, reference CSimulate.cpp:111-116.
-     * outputBits of a group is [32][K] then [32][M]; frame m's bit k sits at m*N + k after
-     * BeforeModulationInterleaver (CModulate.cpp:95-148).  With FakeEncoder every stream sends the same 32 frames:
-     * one modulated sequence serves all of them. */
     const size_t bits = (size_t)32 * N;
-    const int n_seq = encode ? m_streams : 1;
     const size_t sym = ModulationType == 1 ? bits : bits / (size_t)ModulationType;
-    if (ModulationType == 1) BPSKModSeq.resize((size_t)n_seq * sym);
-    else ModSeq.resize((size_t)n_seq * sym);
-    for (int g = 0; g < n_seq; ++g) {
-        const int8_t* ob = ldpc->outputBits + (size_t)g * bits;
-        auto tx_bit = [&](int m, int k) { return k < K ? ob[(size_t)m * K + k] : ob[(size_t)32 * K + (size_t)m * M + (k - K)]; };
-        if (ModulationType == 1) {
-            float* dst = BPSKModSeq.data() + (size_t)g * sym;
-            for (int m = 0; m < 32; ++m) for (int k = 0; k < N; ++k) dst[(size_t)m * N + k] = 2.0f * tx_bit(m, k) - 1.0f; /* CModulate.cpp:368 */
-        } else { /* Modulation (reference CModulate.cpp:216-264): even positions index the in-phase entry MSB first, odd ones the quadrature entry */
-            Complex8* dst = ModSeq.data() + (size_t)g * sym;
-            for (size_t i = 0; i < bits / (size_t)Q; ++i) {
-                int idx_i = 0, idx_q = 0;
-                for (int u = 0; u < Q; ++u) {
-                    const size_t pos = (size_t)Q * i + u;
-                    const int b = tx_bit((int)(pos / N), code_bit((int)(pos % N)));
-                    if (u & 1) idx_q += b << (half - u / 2 - 1); else idx_i += b << (half - u / 2 - 1);
+    if (device_encode) {
+        /* --device-encode: messages and frames of every stream are made on the device, once per 50 calls.  The key of
+         * stream s is its generator state at the start of the run (each of IX, IY, IZ is below 2^16), so every round and
+         * every Eb/N0 point get new messages, and a run resumed from Temp.txt continues the same sequence */
+        std::vector<uint64_t> keys((size_t)m_streams);
+        for (int s = 0; s < m_streams; ++s)
+            keys[(size_t)s] = (uint64_t)channel[s].RS.IX | (uint64_t)channel[s].RS.IY << 16 | (uint64_t)channel[s].RS.IZ << 32;
+        ldpc->DeviceRandomFrames(decode_method, keys.data(), InterleaveModType);
+    } else {
+        if (encode) { ldpc->GenMsgSeq(); ldpc->Encode(); }
+        else ldpc->FakeEncoder();
+        /* interleave + modulate once per 50 calls, reference CSimulate.cpp:111-116.
+         * outputBits of a group is [32][K] then [32][M]; frame m's bit k sits at m*N + k after
+         * BeforeModulationInterleaver (CModulate.cpp:95-148).  With FakeEncoder every stream sends the same 32 frames:
+         * one modulated sequence serves all of them. */
+        const int n_seq = encode ? m_streams : 1;
+        if (ModulationType == 1) BPSKModSeq.resize((size_t)n_seq * sym);
+        else ModSeq.resize((size_t)n_seq * sym);
+        for (int g = 0; g < n_seq; ++g) {
+            const int8_t* ob = ldpc->outputBits + (size_t)g * bits;
+            auto tx_bit = [&](int m, int k) { return k < K ? ob[(size_t)m * K + k] : ob[(size_t)32 * K + (size_t)m * M + (k - K)]; };
+            if (ModulationType == 1) {
+                float* dst = BPSKModSeq.data() + (size_t)g * sym;
+                for (int m = 0; m < 32; ++m) for (int k = 0; k < N; ++k) dst[(size_t)m * N + k] = 2.0f * tx_bit(m, k) - 1.0f; /* CModulate.cpp:368 */
+            } else { /* Modulation (reference CModulate.cpp:216-264): even positions index the in-phase entry MSB first, odd ones the quadrature entry */
+                Complex8* dst = ModSeq.data() + (size_t)g * sym;
+                for (size_t i = 0; i < bits / (size_t)Q; ++i) {
+                    int idx_i = 0, idx_q = 0;
+                    for (int u = 0; u < Q; ++u) {
+                        const size_t pos = (size_t)Q * i + u;
+                        const int b = tx_bit((int)(pos / N), code_bit((int)(pos % N)));
+                        if (u & 1) idx_q += b << (half - u / 2 - 1); else idx_i += b << (half - u / 2 - 1);
+                    }
+                    dst[i].real = axis[idx_i];
+                    dst[i].imag = axis[idx_q];
                 }
-                dst[i].real = axis[idx_i];
-                dst[i].imag = axis[idx_q];
             }
         }
+        if (device_frontend) ldpc->DeviceFrames(decode_method, encode, InterleaveModType); /* the 32 frames of every stream, once per 50 calls */
     }
-    if (device_frontend) ldpc->DeviceFrames(decode_method, encode, InterleaveModType); /* the 32 frames of every stream, once per 50 calls */
     std::vector<float> llr(device_frontend ? 0 : (size_t)m_streams * bits);
     std::vector<int> BFiters_((size_t)m_streams * 51, 0); /* per stream, reference CSimulate.cpp:99 */
     std::vector<uint32_t> states(3 * (size_t)m_streams);

@@ -26,6 +26,7 @@ public:
     double decode_seconds = 0; /* host wall time spent inside Decode_*() */
     bool device_frontend = false; /* generate the channel output on the GPU (lnsfaid_frontend_device) */
     bool encode = false;          /* GenMsgSeq + Encode instead of FakeEncoder (reference FAKE_ENCODE 0) */
+    bool device_encode = false;   /* random messages drawn and encoded on the device (needs device_frontend) */
     unsigned long sum_iterations = 0, sum_bf_iterations = 0, decoded_groups = 0;
 
     ~CSimulate();

@@ -49,9 +49,10 @@ int main(int argc, char** argv)
     const char* run_id = "";
     int comm_timeout_s = 120;
     const int64_t started_at = (int64_t)time(nullptr);
-    bool device_frontend = false, force_collect = false, encode = false;
+    bool device_frontend = false, force_collect = false, encode = false, device_encode = false;
     const char* profile = "Profile.txt";
     const char* resume = nullptr;
+    const char* usage = "usage: %s [--streams T] [--gpus G] [--profile Profile.txt] [--max-rounds R] [--device-frontend [--device-encode]] [--encode] [--collect] [--resume Temp.txt] [--ranks N --rank r --comm-file F [--run-id ID] [--comm-timeout S] [--device d]]\n";
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--streams") && i + 1 < argc) streams = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--gpus") && i + 1 < argc) gpus = atoi(argv[++i]);
@@ -67,8 +68,14 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--device-frontend")) device_frontend = true; /* channel + demapper + quantiser on the GPU */
         else if (!strcmp(argv[i], "--resume") && i + 1 < argc) resume = argv[++i]; /* lastSeed table of a Temp.txt (reference CONTINUE_SEED 1) */
         else if (!strcmp(argv[i], "--encode")) encode = true; /* random information bits + the encoder derived from H (reference FAKE_ENCODE 0) */
+        else if (!strcmp(argv[i], "--device-encode")) device_encode = true; /* messages drawn and encoded on the GPU (lnsfaid_frontend_random_frames) */
         else if (!strcmp(argv[i], "--collect")) force_collect = true; /* collectflag = 1 from the first call (reference: once FER < 1e-5) */
-        else { fprintf(stderr, "usage: %s [--streams T] [--gpus G] [--profile Profile.txt] [--max-rounds R] [--device-frontend] [--encode] [--collect] [--resume Temp.txt] [--ranks N --rank r --comm-file F [--run-id ID] [--comm-timeout S] [--device d]]\n", argv[0]); return 2; }
+        else { fprintf(stderr, usage, argv[0]); return 2; }
+    }
+    if (device_encode && !device_frontend) {
+        fprintf(stderr, usage, argv[0]);
+        fprintf(stderr, "--device-encode needs --device-frontend\n");
+        return 2;
     }
     if (streams < 1 || gpus < 1 || gpus > streams) { fprintf(stderr, "need 1 <= gpus <= streams\n"); return 2; }
     if (ranks < 1 || rank < 0 || rank >= ranks || (ranks > 1 && (gpus != 1 || !comm_file || ranks > streams))) {
@@ -93,6 +100,7 @@ int main(int argc, char** argv)
         const int first = r_first + (int)((long)mine * g / gpus), last = r_first + (int)((long)mine * (g + 1) / gpus);
         simulate[g].device_frontend = device_frontend;
         simulate[g].encode = encode;
+        simulate[g].device_encode = device_encode;
         simulate[g].Initial(p_simulation, first, last - first, multi ? device : g);
     }
     if (multi) { /* RCCL communicator of this run: the id travels through --comm-file */

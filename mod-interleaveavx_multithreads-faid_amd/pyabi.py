@@ -76,6 +76,10 @@ SYMBOLS = {
     "lnsfaid_frontend_set_interleave": (C.c_int, [C.c_void_p, C.c_int32]),
     "lnsfaid_frontend_set_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "lnsfaid_frontend_input_bits": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "lnsfaid_code_parity_inverse": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_size_t]),
+    "lnsfaid_encode_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lnsfaid_encode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lnsfaid_frontend_random_frames": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_size_t]),
     "lnsfaid_io_buffers": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_void_p)]),
     "lnsfaid_read_stats": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t]),
     "lnsfaid_host_register": (C.c_int, [C.c_void_p, C.c_size_t]),
@@ -206,6 +210,23 @@ class Decoder:
         self._check(self.lib.lnsfaid_count_errors_device(self.ctx, d_decoded_ptr, d_input_ptr, n_groups, out),
                     "lnsfaid_count_errors_device")
         return list(out)
+
+    def encode(self, info, n_groups):
+        """info: numpy int8 0/1, [32][K] per group.  Returns the encoder output, [32][K] then [32][M] per group."""
+        import numpy as np
+        K, N = self.code50.K, self.code50.N
+        assert info.dtype == np.int8 and info.size == n_groups * GROUP * K and info.flags.c_contiguous
+        out = np.empty(n_groups * GROUP * N, dtype=np.int8)
+        self._check(self.lib.lnsfaid_encode(self.ctx, info.ctypes.data, n_groups, out.ctypes.data), "lnsfaid_encode")
+        return out
+
+    def encode_device(self, d_in_ptr, n_groups, d_out_ptr):
+        self._check(self.lib.lnsfaid_encode_device(self.ctx, d_in_ptr, n_groups, d_out_ptr), "lnsfaid_encode_device")
+
+    def random_frames(self, keys):
+        """lnsfaid_frontend_random_frames: one uint64 key per stream"""
+        buf = (C.c_uint64 * len(keys))(*[int(k) for k in keys])
+        self._check(self.lib.lnsfaid_frontend_random_frames(self.ctx, buf, len(keys)), "lnsfaid_frontend_random_frames")
 
     def comm_init(self, n_ranks, rank, comm_id):
         self._check(self.lib.lnsfaid_comm_init(self.ctx, n_ranks, rank, comm_id), "lnsfaid_comm_init")
