@@ -24,10 +24,12 @@
  * buffer it passes, the context owns device buffers and its HIP stream.  One
  * context per (host thread, GPU): thread-compatible, not thread-safe.
  *
- * Batches are consecutive GROUPS of 32 codewords.  The group is part of the
- * contract: the reference decodes 32 codewords in lock-step and stops a group
- * only when all 32 lanes are clean (CDecoder_FAID.cpp:616, :6782), which is
- * observable in the hard decisions; this library reproduces it bit for bit.
+ * Batches are consecutive GROUPS of 32 codewords.  By default the group is part
+ * of the contract: the reference decodes 32 codewords in lock-step and stops a
+ * group only when all 32 lanes are clean (CDecoder_FAID.cpp:616, :6782), which
+ * is observable in the hard decisions; this library reproduces it bit for bit.
+ * lnsfaid_set_early_stop(ctx, LNSFAID_STOP_CODEWORD) and lnsfaid_decode_codewords
+ * let every codeword stop on its own instead (still in groups of 32 in memory).
  */
 #ifndef LNSFAID_H
 #define LNSFAID_H
@@ -101,6 +103,14 @@ typedef struct lnsfaid_group_stats {
     int32_t bf_iterations; /* J: bit-flipping iterations that reached the flip step  */
 } lnsfaid_group_stats;
 
+/* per-codeword execution record (lnsfaid_decode_codewords): what the reference reports for a group of 32 copies of the codeword */
+typedef struct lnsfaid_codeword_stats {
+    int32_t iterations;    /* I: layered iterations the codeword executed                                          */
+    int32_t bf_iterations; /* J: bit-flipping iterations that reached the flip step                                */
+    int32_t unsatisfied;   /* parity checks the RETURNED decodedBits leave unsatisfied, over all n_var bits (the
+                            * punctured tail included): 0 means the output is a codeword                          */
+} lnsfaid_codeword_stats;
+
 typedef struct lnsfaid_ctx lnsfaid_ctx;
 
 /* ---- code / configuration helpers (host only, no GPU needed) ---------------- */
@@ -169,6 +179,30 @@ int lnsfaid_decode(lnsfaid_ctx* ctx, const int8_t* fixInput, size_t n_groups,
  * nothing converges, typically 3 with early stop) and returns after the batch is complete.  d_stats optional. */
 int lnsfaid_decode_device(lnsfaid_ctx* ctx, const int8_t* d_fixInput, size_t n_groups,
                           int8_t* d_decodedBits, lnsfaid_group_stats* d_stats);
+
+/* ---- early stop per codeword ----------------------------------------------------------------------
+ * LNSFAID_STOP_GROUP (the default) is the reference's rule: a group stops at the first decision point at which all 32 codewords
+ * are clean, and until then clean codewords keep iterating (and bit flipping).  Under LNSFAID_STOP_CODEWORD every codeword stops
+ * at the first decision point at which it is itself clean (the syndrome stage in front of every layered iteration, then the one
+ * in front of every bit-flipping iteration).  Decoding codeword c under that rule gives exactly what the reference gives for a
+ * group of 32 copies of c (hard decisions, I and J), and the batch is decoded in one launch.  DecodeMethod 0 has no early stop:
+ * both rules give the same output.  Under the per-codeword rule the group_stats of a group are the maxima of I and of J over
+ * its 32 codewords.  Configurations that run on the two-rows-per-lane kernel (DecodeMethod 0 with two normalisation factors,
+ * FAID tables that are not uniform over the weight classes) and contexts with lnsfaid_select_waves(ctx, 2) in effect have no
+ * per-codeword decoder: their decodes under the per-codeword rule return LNSFAID_E_INVAL. */
+#define LNSFAID_STOP_GROUP 0
+#define LNSFAID_STOP_CODEWORD 1
+/* The rule of every later lnsfaid_decode / lnsfaid_decode_device call of ctx, through the call combiner too (calls of contexts
+ * with different rules never share a launch).  LNSFAID_E_INVAL for another value.  lnsfaid_early_stop returns the rule. */
+int lnsfaid_set_early_stop(lnsfaid_ctx* ctx, int32_t rule);
+int lnsfaid_early_stop(const lnsfaid_ctx* ctx);
+/* lnsfaid_decode / lnsfaid_decode_device under the per-codeword rule whatever the context's setting, with a record per codeword:
+ *   cw_stats  optional, [n_groups * 32] in decodedBits order (host pointer / device pointer on the context's GPU)
+ * A one-group context that asks for cw_stats decodes on its own stream, not through the call combiner. */
+int lnsfaid_decode_codewords(lnsfaid_ctx* ctx, const int8_t* fixInput, size_t n_groups, int8_t* decodedBits,
+                             lnsfaid_codeword_stats* cw_stats);
+int lnsfaid_decode_codewords_device(lnsfaid_ctx* ctx, const int8_t* d_fixInput, size_t n_groups, int8_t* d_decodedBits,
+                                    lnsfaid_codeword_stats* d_cw_stats);
 
 /*
  * Replaces CLDPC::CalculateErrors (CLDPC.cpp:4842-4876) for n_groups groups:

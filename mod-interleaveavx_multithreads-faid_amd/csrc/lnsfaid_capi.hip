@@ -27,6 +27,8 @@ extern "C" const void* lf_decode4_func(int method, int ef, int rm);
 extern "C" int lf_decode4_threads(void);
 extern "C" hipError_t lf_launch_decode4(int method, int ef, int rm, const LfKernelArgs* args, size_t lds_bytes, hipStream_t stream);
 extern "C" int lf_decode4_rm_layers(void);
+extern "C" const void* lf_decode4cw_func(int method, int ef, int rm);
+extern "C" hipError_t lf_launch_decode4cw(int method, int ef, int rm, const LfCwArgs* args, size_t lds_bytes, hipStream_t stream);
 extern "C" const void* lf_decode5_func(int method);
 extern "C" int lf_decode5_threads(void);
 extern "C" hipError_t lf_launch_decode5(int method, const LfKernelArgs* args, size_t lds_bytes, hipStream_t stream);
@@ -109,13 +111,15 @@ struct lnsfaid_ctx {
     int8_t* d_io_in = nullptr;
     int8_t* d_io_out = nullptr;
     lnsfaid_group_stats* d_io_stats = nullptr;
+    lnsfaid_codeword_stats* d_io_cw_stats = nullptr; /* lnsfaid_decode_codewords, allocated at its first call */
+    int early_stop = LNSFAID_STOP_GROUP; /* rule of lnsfaid_decode / lnsfaid_decode_device (lnsfaid_set_early_stop) */
     int rows_per_lane = 0; /* 0: pick per configuration; 2 / 4: forced (lnsfaid_select_kernel) */
     int waves_per_cw = 0;  /* 0 / 1: one wave per codeword; 2: lnsfaid_kernel5.hip where it applies (lnsfaid_select_waves) */
     int msg_store = 0;     /* 0: pick per code; 1: registers; 2: streamed through HBM (lnsfaid_select_message_store) */
     struct LfCombiner* comb = nullptr; /* call combiner this one-group context is a member of (see below) */
     int comb_slot = -1;
-    const void* checked_fn = nullptr; /* kernel instance kernel_check() last looked at */
-    int resident_wg = 0, lds_wg = 0;  /* its workgroups per CU: what the occupancy query says / what its LDS alone allows */
+    const void* checked_fn[2] = {};           /* kernel instance kernel_check() last looked at, per early-stop rule */
+    int resident_wg[2] = {}, lds_wg[2] = {};  /* its workgroups per CU: what the occupancy query says / what its LDS alone allows */
     void* comm = nullptr;      /* ncclComm_t for lnsfaid_allreduce_counters */
     bool comm_owned = false;
     unsigned long long* d_reduce = nullptr;
@@ -332,6 +336,7 @@ extern "C" void lnsfaid_destroy(lnsfaid_ctx* ctx)
     (void)hipFree(ctx->d_bits); (void)hipFree(ctx->d_lane); (void)hipFree(ctx->d_status[0]); (void)hipFree(ctx->d_status[1]);
     (void)hipFree(ctx->d_remaining); (void)hipFree(ctx->d_live); (void)hipFree(ctx->d_counters);
     (void)hipFree(ctx->d_io_in); (void)hipFree(ctx->d_io_out); (void)hipFree(ctx->d_io_stats);
+    (void)hipFree(ctx->d_io_cw_stats);
     (void)hipFree(ctx->d_fe_seeds); (void)hipFree(ctx->d_fe_draws); (void)hipFree(ctx->d_fe_codeword);
     (void)hipFree(ctx->d_fe_frames); (void)hipFree(ctx->d_fe_input);
     (void)hipFree(ctx->d_enc_sup); (void)hipFree(ctx->d_enc_off); (void)hipFree(ctx->d_fe_keys);
@@ -518,8 +523,16 @@ static bool use_msg_registers(const lnsfaid_ctx* ctx)
     return ctx->msg_store != LNSFAID_MSG_HBM;
 }
 
-static const void* selected_kernel(const lnsfaid_ctx* ctx, int* threads)
+/* Under the per-codeword rule (lnsfaid_kernel4cw.hip) the four-rows kernel's configurations have an instance each, with the
+ * same message store; the two-rows kernel and the two-waves kernel have none. */
+static bool cw_possible(const lnsfaid_ctx* ctx) { return ctx->waves_per_cw != 2 && use_kernel4(ctx); }
+
+static const void* selected_kernel(const lnsfaid_ctx* ctx, int* threads, int rule)
 {
+    if (rule == LNSFAID_STOP_CODEWORD) {
+        *threads = lf_decode4_threads();
+        return cw_possible(ctx) ? lf_decode4cw_func(ctx->hcfg.method, ctx->hcfg.ef, use_msg_registers(ctx) ? 1 : 0) : nullptr;
+    }
     if (use_kernel5(ctx)) {
         *threads = lf_decode5_threads();
         return lf_decode5_func(ctx->hcfg.method);
@@ -553,13 +566,12 @@ extern "C" int lnsfaid_message_store(const lnsfaid_ctx* ctx)
  *  - how many of its workgroups a CU holds.  The decoders are sized so that LDS alone decides that (50G-PON: 20 424 B per
  *    codeword, 8 per CU); one more register or LDS word in the wrong place halves it, which costs ~40 % of the throughput and
  *    nothing else would show.  Recorded for lnsfaid_kernel_residency, printed under LNSFAID_TRACE. */
-static const void* selected_kernel(const lnsfaid_ctx* ctx, int* threads);
-static int kernel_check(lnsfaid_ctx* ctx)
+static int kernel_check(lnsfaid_ctx* ctx, int rule)
 {
     int threads = 0;
-    const void* fn = selected_kernel(ctx, &threads);
-    if (!fn) return LNSFAID_E_INTERNAL;
-    if (fn == ctx->checked_fn) return LNSFAID_OK;
+    const void* fn = selected_kernel(ctx, &threads, rule);
+    if (!fn) return rule == LNSFAID_STOP_CODEWORD ? LNSFAID_E_INVAL : LNSFAID_E_INTERNAL; /* no per-codeword instance */
+    if (fn == ctx->checked_fn[rule]) return LNSFAID_OK;
     hipFuncAttributes at;
     HIP_TRY(hipFuncGetAttributes(&at, fn));
     if (at.sharedSizeBytes != 0) {
@@ -576,7 +588,7 @@ static int kernel_check(lnsfaid_ctx* ctx)
     int by_lds = (int)(lds_cu / ((ctx->lds_bytes + gran - 1) / gran * gran));
     const int by_waves = 32 / ((threads + 63) / 64); /* 32 wave slots per CU */
     if (by_lds > by_waves) by_lds = by_waves;
-    ctx->checked_fn = fn; ctx->resident_wg = wg; ctx->lds_wg = by_lds;
+    ctx->checked_fn[rule] = fn; ctx->resident_wg[rule] = wg; ctx->lds_wg[rule] = by_lds;
     static const bool trace = getenv("LNSFAID_TRACE") != nullptr;
     if (trace)
         fprintf(stderr, "[lnsfaid] decode kernel: %d threads, %d VGPRs, %zu B LDS per workgroup, %d workgroups per CU (LDS alone: %d)%s\n",
@@ -588,10 +600,10 @@ extern "C" int lnsfaid_kernel_residency(lnsfaid_ctx* ctx, int32_t* workgroups_pe
 {
     if (!ctx) return LNSFAID_E_INVAL;
     HIP_TRY(hipSetDevice(ctx->device));
-    const int rc = kernel_check(ctx);
+    const int rc = kernel_check(ctx, ctx->early_stop);
     if (rc) return rc;
-    if (workgroups_per_cu) *workgroups_per_cu = ctx->resident_wg;
-    if (lds_limit) *lds_limit = ctx->lds_wg;
+    if (workgroups_per_cu) *workgroups_per_cu = ctx->resident_wg[ctx->early_stop];
+    if (lds_limit) *lds_limit = ctx->lds_wg[ctx->early_stop];
     return LNSFAID_OK;
 }
 
@@ -599,10 +611,70 @@ extern "C" int lnsfaid_kernel_residency(lnsfaid_ctx* ctx, int32_t* workgroups_pe
  * that take no part in a batch as finished); otherwise every codeword is fresh */
 static int decode_device_impl(lnsfaid_ctx* ctx, const int8_t* d_fixInput, size_t n_groups, int8_t* d_decodedBits,
                               lnsfaid_group_stats* d_stats, bool status_preloaded);
+static int decode_cw_device_impl(lnsfaid_ctx* ctx, const int8_t* d_fixInput, size_t n_groups, int8_t* d_decodedBits,
+                                 lnsfaid_group_stats* d_stats, lnsfaid_codeword_stats* d_cw_stats, bool status_preloaded);
+/* the context's rule, or the per-codeword one (lnsfaid_decode_codewords*) */
+static int decode_device_rule(lnsfaid_ctx* ctx, const int8_t* d_fixInput, size_t n_groups, int8_t* d_decodedBits, lnsfaid_group_stats* d_stats,
+                              lnsfaid_codeword_stats* d_cw_stats, int rule, bool status_preloaded)
+{
+    if (rule == LNSFAID_STOP_CODEWORD)
+        return decode_cw_device_impl(ctx, d_fixInput, n_groups, d_decodedBits, d_stats, d_cw_stats, status_preloaded);
+    return decode_device_impl(ctx, d_fixInput, n_groups, d_decodedBits, d_stats, status_preloaded);
+}
 extern "C" int lnsfaid_decode_device(lnsfaid_ctx* ctx, const int8_t* d_fixInput, size_t n_groups, int8_t* d_decodedBits,
                                      lnsfaid_group_stats* d_stats)
 {
-    return decode_device_impl(ctx, d_fixInput, n_groups, d_decodedBits, d_stats, false);
+    if (!ctx) return LNSFAID_E_INVAL;
+    return decode_device_rule(ctx, d_fixInput, n_groups, d_decodedBits, d_stats, nullptr, ctx->early_stop, false);
+}
+extern "C" int lnsfaid_decode_codewords_device(lnsfaid_ctx* ctx, const int8_t* d_fixInput, size_t n_groups, int8_t* d_decodedBits,
+                                               lnsfaid_codeword_stats* d_cw_stats)
+{
+    return decode_cw_device_impl(ctx, d_fixInput, n_groups, d_decodedBits, nullptr, d_cw_stats, false);
+}
+
+extern "C" int lnsfaid_set_early_stop(lnsfaid_ctx* ctx, int32_t rule)
+{
+    if (!ctx || (rule != LNSFAID_STOP_GROUP && rule != LNSFAID_STOP_CODEWORD)) return LNSFAID_E_INVAL;
+    ctx->early_stop = rule;
+    return LNSFAID_OK;
+}
+extern "C" int lnsfaid_early_stop(const lnsfaid_ctx* ctx) { return ctx ? ctx->early_stop : LNSFAID_E_INVAL; }
+
+/* Per-codeword rule (lnsfaid_kernel4cw.hip): every codeword runs to its own stop in ONE launch, so there is no chain, no status
+ * double buffer and no "codewords left" counter - one launch, one wait.  The group records are maxima, taken with atomics over
+ * zeroed words.  status_preloaded: ctx->d_status[0] marks the groups of a combiner batch that take no part (LF_DONE). */
+static int decode_cw_device_impl(lnsfaid_ctx* ctx, const int8_t* d_fixInput, size_t n_groups, int8_t* d_decodedBits,
+                                 lnsfaid_group_stats* d_stats, lnsfaid_codeword_stats* d_cw_stats, bool status_preloaded)
+{
+    if (!ctx || (n_groups && (!d_fixInput || !d_decodedBits))) return LNSFAID_E_INVAL;
+    if (n_groups > ctx->max_groups) return LNSFAID_E_INVAL;
+    if (!cw_possible(ctx)) return LNSFAID_E_INVAL;
+    if (n_groups == 0) return LNSFAID_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    {
+        const int rc = kernel_check(ctx, LNSFAID_STOP_CODEWORD);
+        if (rc) return rc;
+    }
+    const size_t n_cw = n_groups * LNSFAID_GROUP;
+    LfCwArgs a;
+    a.code = ctx->d_code; a.cfg = ctx->d_cfg;
+    a.fix_input = d_fixInput; a.decoded = d_decodedBits;
+    a.st_rows = ctx->d_rows;
+    a.skip = status_preloaded ? ctx->d_status[0] : nullptr;
+    a.stats = d_stats; a.cw_stats = d_cw_stats; a.n_cw = (int32_t)n_cw;
+    if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, n_groups * sizeof(lnsfaid_group_stats), ctx->stream));
+    static const bool trace = getenv("LNSFAID_TRACE") != nullptr;
+    HIP_TRY(hipEventRecord(ctx->ev_chain[0], ctx->stream));
+    HIP_TRY(lf_launch_decode4cw(ctx->hcfg.method, ctx->hcfg.ef, use_msg_registers(ctx) ? 1 : 0, &a, ctx->lds_bytes, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev_chain[1], ctx->stream));
+    { const int rcw = stream_wait(ctx); if (rcw) return rcw; }
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_chain[0], ctx->ev_chain[1]));
+    ctx->kernel_ms += ms;
+    ctx->kernel_launches += 1;
+    if (trace) fprintf(stderr, "[lnsfaid] per-codeword launch: %.3f ms, %zu codewords\n", ms, n_cw);
+    return LNSFAID_OK;
 }
 
 static int decode_device_impl(lnsfaid_ctx* ctx, const int8_t* d_fixInput, size_t n_groups, int8_t* d_decodedBits,
@@ -613,7 +685,7 @@ static int decode_device_impl(lnsfaid_ctx* ctx, const int8_t* d_fixInput, size_t
     if (n_groups == 0) return LNSFAID_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     {
-        const int rc = kernel_check(ctx);
+        const int rc = kernel_check(ctx, LNSFAID_STOP_GROUP);
         if (rc) return rc;
     }
     const size_t n_cw = n_groups * LNSFAID_GROUP;
@@ -709,6 +781,7 @@ struct LfSlot {
     int state = LF_SLOT_FREE;
     int rc = 0;
     LfDevCfg cfg;
+    int rule = LNSFAID_STOP_GROUP; /* early-stop rule of the call: part of the batch key with cfg */
     lnsfaid_group_stats stats;
 };
 struct LfCombiner {
@@ -794,7 +867,7 @@ static void comb_run_batch(LfCombiner* cb, int w, const int* batch, int nb)
         fail(hipMemcpyAsync(P->d_io_in + (size_t)lo * gb, cb->h_in + (size_t)lo * gb, span * gb, hipMemcpyHostToDevice, P->stream), "fixInput upload");
         k_in = P->d_io_in; k_out = P->d_io_out;
     }
-    if (rc == LNSFAID_OK) rc = decode_device_impl(P, k_in, n, k_out, P->d_io_stats, true);
+    if (rc == LNSFAID_OK) rc = decode_device_rule(P, k_in, n, k_out, P->d_io_stats, nullptr, cb->slots[batch[0]].rule, true);
     if (rc == LNSFAID_OK) {
         if (k_out == P->d_io_out)
             fail(hipMemcpyAsync(cb->h_out + (size_t)lo * gb, P->d_io_out + (size_t)lo * gb, span * gb, hipMemcpyDeviceToHost, P->stream), "decodedBits download");
@@ -841,12 +914,13 @@ static void comb_worker(LfCombiner* cb, int w)
         cb->gather_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_first).count();
         int batch[LF_COMB_SLOTS], nb = 0;
         const int cap = cb->members > 8 * comb_workers() ? (cb->members + comb_batches() - 1) / comb_batches() : LF_COMB_SLOTS;
-        const LfDevCfg* cfg = nullptr; /* one configuration per batch: the first pending one's */
+        const LfDevCfg* cfg = nullptr; /* one configuration and one early-stop rule per batch: the first pending call's */
+        int rule = LNSFAID_STOP_GROUP;
         for (int i = 0; i < LF_COMB_SLOTS && nb < cap; ++i) {
             LfSlot& s = cb->slots[i];
             if (s.state != LF_SLOT_PENDING) continue;
-            if (!cfg) cfg = &s.cfg;
-            if (memcmp(cfg, &s.cfg, sizeof(LfDevCfg)) != 0) continue; /* next batch */
+            if (!cfg) { cfg = &s.cfg; rule = s.rule; }
+            if (memcmp(cfg, &s.cfg, sizeof(LfDevCfg)) != 0 || s.rule != rule) continue; /* next batch */
             s.state = LF_SLOT_RUNNING;
             batch[nb++] = i;
         }
@@ -961,7 +1035,7 @@ static void comb_leave(lnsfaid_ctx* ctx, int slot)
 }
 
 /* 1: decoded through the combiner (*rc_out = result); 0: not applicable now, take the direct path */
-static int comb_decode(lnsfaid_ctx* ctx, const int8_t* fixInput, int8_t* decodedBits, lnsfaid_group_stats* stats, int* rc_out)
+static int comb_decode(lnsfaid_ctx* ctx, const int8_t* fixInput, int8_t* decodedBits, lnsfaid_group_stats* stats, int rule, int* rc_out)
 {
     if (ctx->comb_slot < 0 || ctx->rows_per_lane != 0 || ctx->msg_store != 0 || ctx->waves_per_cw != 0) return 0;
     LfCombiner* cb = ctx->comb;
@@ -977,6 +1051,7 @@ static int comb_decode(lnsfaid_ctx* ctx, const int8_t* fixInput, int8_t* decoded
         std::unique_lock<std::mutex> lk(cb->m);
         LfSlot& s = cb->slots[slot];
         s.cfg = ctx->hcfg;
+        s.rule = rule;
         s.state = LF_SLOT_PENDING;
         cb->pending += 1;
         cb->cv_work.notify_all(); /* (at most LF_COMB_WORKERS waiters) */
@@ -1065,19 +1140,24 @@ static bool host_pinned(const void* p)
     return at.type == hipMemoryTypeHost;
 }
 
-extern "C" int lnsfaid_decode(lnsfaid_ctx* ctx, const int8_t* fixInput, size_t n_groups, int8_t* decodedBits,
-                              lnsfaid_group_stats* stats)
+/* lnsfaid_decode under the given rule; cw_stats (per-codeword rule only) optional */
+static int decode_host_impl(lnsfaid_ctx* ctx, const int8_t* fixInput, size_t n_groups, int8_t* decodedBits, lnsfaid_group_stats* stats,
+                            lnsfaid_codeword_stats* cw_stats, int rule)
 {
     if (!ctx || (n_groups && (!fixInput || !decodedBits))) return LNSFAID_E_INVAL;
     if (n_groups > ctx->max_groups) return LNSFAID_E_INVAL;
+    if (rule == LNSFAID_STOP_CODEWORD && !cw_possible(ctx)) return LNSFAID_E_INVAL;
     if (n_groups == 0) return LNSFAID_OK;
-    {   /* a one-group context among others on its device: through the call combiner */
+    if (!cw_stats) {   /* a one-group context among others on its device: through the call combiner */
         int rcc = 0;
-        if (comb_decode(ctx, fixInput, decodedBits, stats, &rcc)) return rcc;
+        if (comb_decode(ctx, fixInput, decodedBits, stats, rule, &rcc)) return rcc;
     }
     HIP_TRY(hipSetDevice(ctx->device));
     int rc = ensure_io(ctx);
     if (rc) return rc;
+    if (cw_stats && !ctx->d_io_cw_stats)
+        HIP_TRY(hipMalloc(&ctx->d_io_cw_stats, ctx->max_groups * LNSFAID_GROUP * sizeof(lnsfaid_codeword_stats)));
+    lnsfaid_codeword_stats* d_cw = cw_stats ? ctx->d_io_cw_stats : nullptr;
     const size_t group_bytes = LNSFAID_GROUP * (size_t)ctx->n_var;
     const size_t bytes = n_groups * group_bytes;
     /* Pinned host buffers (hipHostMalloc / lnsfaid_host_register): cut the batch into pieces of whole groups and overlap
@@ -1087,7 +1167,7 @@ extern "C" int lnsfaid_decode(lnsfaid_ctx* ctx, const int8_t* fixInput, size_t n
     size_t chunk = ((n_groups + LF_IO_CHUNKS - 1) / LF_IO_CHUNKS + 63) / 64 * 64; /* >= one full wave of workgroups */
     if (chunk >= n_groups || !host_pinned(fixInput) || !host_pinned(decodedBits)) { /* (small batches: no pointer query at all) */
         HIP_TRY(hipMemcpyAsync(ctx->d_io_in, fixInput, bytes, hipMemcpyHostToDevice, ctx->stream));
-        rc = lnsfaid_decode_device(ctx, ctx->d_io_in, n_groups, ctx->d_io_out, ctx->d_io_stats);
+        rc = decode_device_rule(ctx, ctx->d_io_in, n_groups, ctx->d_io_out, ctx->d_io_stats, d_cw, rule, false);
         if (rc) return rc;
         HIP_TRY(hipMemcpyAsync(decodedBits, ctx->d_io_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
     } else {
@@ -1105,7 +1185,8 @@ extern "C" int lnsfaid_decode(lnsfaid_ctx* ctx, const int8_t* fixInput, size_t n
         for (size_t c = 0; c < n_chunks; ++c) {
             const size_t g0 = c * chunk, ng = g0 + chunk <= n_groups ? chunk : n_groups - g0;
             HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_in[c], 0));
-            rc = lnsfaid_decode_device(ctx, ctx->d_io_in + g0 * group_bytes, ng, ctx->d_io_out + g0 * group_bytes, ctx->d_io_stats + g0);
+            rc = decode_device_rule(ctx, ctx->d_io_in + g0 * group_bytes, ng, ctx->d_io_out + g0 * group_bytes, ctx->d_io_stats + g0,
+                                    d_cw ? d_cw + g0 * LNSFAID_GROUP : nullptr, rule, false);
             if (rc) { (void)hipStreamSynchronize(ctx->s_in); (void)hipStreamSynchronize(ctx->s_out); return rc; }
             /* decode_device returns with the piece finished: its copy out needs no further ordering */
             HIP_TRY(hipMemcpyAsync(decodedBits + g0 * group_bytes, ctx->d_io_out + g0 * group_bytes, ng * group_bytes, hipMemcpyDeviceToHost, ctx->s_out));
@@ -1115,8 +1196,24 @@ extern "C" int lnsfaid_decode(lnsfaid_ctx* ctx, const int8_t* fixInput, size_t n
     if (stats)
         HIP_TRY(hipMemcpyAsync(stats, ctx->d_io_stats, n_groups * sizeof(lnsfaid_group_stats), hipMemcpyDeviceToHost,
                                ctx->stream));
+    if (cw_stats)
+        HIP_TRY(hipMemcpyAsync(cw_stats, d_cw, n_groups * LNSFAID_GROUP * sizeof(lnsfaid_codeword_stats), hipMemcpyDeviceToHost,
+                               ctx->stream));
     { const int rcw = stream_wait(ctx); if (rcw) return rcw; }
     return LNSFAID_OK;
+}
+
+extern "C" int lnsfaid_decode(lnsfaid_ctx* ctx, const int8_t* fixInput, size_t n_groups, int8_t* decodedBits,
+                              lnsfaid_group_stats* stats)
+{
+    if (!ctx) return LNSFAID_E_INVAL;
+    return decode_host_impl(ctx, fixInput, n_groups, decodedBits, stats, nullptr, ctx->early_stop);
+}
+
+extern "C" int lnsfaid_decode_codewords(lnsfaid_ctx* ctx, const int8_t* fixInput, size_t n_groups, int8_t* decodedBits,
+                                        lnsfaid_codeword_stats* cw_stats)
+{
+    return decode_host_impl(ctx, fixInput, n_groups, decodedBits, nullptr, cw_stats, LNSFAID_STOP_CODEWORD);
 }
 
 /* ---- pinned host memory for callers without a HIP toolchain (the reference is plain C++) ---------------- */
@@ -1527,8 +1624,8 @@ extern "C" const char* lnsfaid_last_hip_error(void) { return g_hip_err; }
 #ifndef LNSFAID_EXTRA_FLAGS
 #define LNSFAID_EXTRA_FLAGS ""
 #endif
-/* the experiment switches of the build (Makefile EXTRA) are part of the version: "lnsfaid-amd 0.3 (gfx950)" is the default build */
+/* the experiment switches of the build (Makefile EXTRA) are part of the version: "lnsfaid-amd 0.4 (gfx950)" is the default build */
 extern "C" const char* lnsfaid_version(void)
 {
-    return sizeof(LNSFAID_EXTRA_FLAGS) > 1 ? "lnsfaid-amd 0.3 (gfx950) [" LNSFAID_EXTRA_FLAGS "]" : "lnsfaid-amd 0.3 (gfx950)";
+    return sizeof(LNSFAID_EXTRA_FLAGS) > 1 ? "lnsfaid-amd 0.4 (gfx950) [" LNSFAID_EXTRA_FLAGS "]" : "lnsfaid-amd 0.4 (gfx950)";
 }

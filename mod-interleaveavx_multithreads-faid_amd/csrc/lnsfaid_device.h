@@ -88,6 +88,19 @@ struct LfKernelArgs {
     int32_t n_cw;
 };
 
+/* Launch arguments of the per-codeword-rule kernel (lnsfaid_kernel4cw.hip): one launch per batch, nothing kept between launches. */
+struct LfCwArgs {
+    const LfDevCode* code;
+    const LfDevCfg* cfg;
+    const int8_t* fix_input;               /* reference fixInput layout, per group [32][K] then [32][M]           */
+    int8_t* decoded;                       /* reference decodedBits layout, per group [32][N]                      */
+    uint4* st_rows;                        /* [n_cw][nbr][128] messages between layers (instances without messages in registers) */
+    const int32_t* skip;                   /* [n_cw] or null: codewords whose word has LF_DONE set take no part (call combiner) */
+    lnsfaid_group_stats* stats;            /* [n_groups] or null: maxima over the group's codewords, zeroed by the host  */
+    lnsfaid_codeword_stats* cw_stats;      /* [n_cw] or null                                                       */
+    int32_t n_cw;
+};
+
 /* dynamic LDS carve-up, shared by host (size) and device (offsets):
  *   [0, N)        En (int8).  In the bit-flipping stage En is dead and the same bytes hold
  *                 hard_ch  at [0, 4*n_words) and hard2 at [4*n_words, 8*n_words)

@@ -108,6 +108,8 @@ void CLDPC::float2LimitChar_4bit(int8_t* output, const float* input, float scale
     }
 }
 
+int g_early_stop = LNSFAID_STOP_GROUP;
+
 lnsfaid_ctx* CLDPC::context(int method)
 {
     lnsfaid_cfg cfg;
@@ -118,6 +120,8 @@ lnsfaid_ctx* CLDPC::context(int method)
     if (!m_ctx[method]) {
         rc = lnsfaid_create(&m_ctx[method], &m_code, &cfg, m_device, (size_t)m_groups);
         if (rc) die("lnsfaid_create", rc);
+        rc = lnsfaid_set_early_stop(m_ctx[method], g_early_stop); /* every later lnsfaid_decode of the context, combiner included */
+        if (rc) die("lnsfaid_set_early_stop", rc);
     } else {
         rc = lnsfaid_set_cfg(m_ctx[method], &cfg);
         if (rc) die("lnsfaid_set_cfg", rc);

@@ -24,6 +24,8 @@ struct Statistic { /* reference CLDPC.h:103-108 */
     unsigned long LT3ErrBitFrame;
 };
 
+extern int g_early_stop; /* --early-stop: LNSFAID_STOP_GROUP (the reference's rule) or LNSFAID_STOP_CODEWORD, set on every context */
+
 class CLDPC {
 public:
     double m_Rate;

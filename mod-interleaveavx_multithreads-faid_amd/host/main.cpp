@@ -52,7 +52,7 @@ int main(int argc, char** argv)
     bool device_frontend = false, force_collect = false, encode = false, device_encode = false;
     const char* profile = "Profile.txt";
     const char* resume = nullptr;
-    const char* usage = "usage: %s [--streams T] [--gpus G] [--profile Profile.txt] [--max-rounds R] [--device-frontend [--device-encode]] [--encode] [--collect] [--resume Temp.txt] [--ranks N --rank r --comm-file F [--run-id ID] [--comm-timeout S] [--device d]]\n";
+    const char* usage = "usage: %s [--streams T] [--gpus G] [--profile Profile.txt] [--max-rounds R] [--device-frontend [--device-encode]] [--encode] [--collect] [--resume Temp.txt] [--early-stop group|codeword] [--ranks N --rank r --comm-file F [--run-id ID] [--comm-timeout S] [--device d]]\n";
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--streams") && i + 1 < argc) streams = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--gpus") && i + 1 < argc) gpus = atoi(argv[++i]);
@@ -69,6 +69,8 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--resume") && i + 1 < argc) resume = argv[++i]; /* lastSeed table of a Temp.txt (reference CONTINUE_SEED 1) */
         else if (!strcmp(argv[i], "--encode")) encode = true; /* random information bits + the encoder derived from H (reference FAKE_ENCODE 0) */
         else if (!strcmp(argv[i], "--device-encode")) device_encode = true; /* messages drawn and encoded on the GPU (lnsfaid_frontend_random_frames) */
+        else if (!strcmp(argv[i], "--early-stop") && i + 1 < argc && (!strcmp(argv[i + 1], "group") || !strcmp(argv[i + 1], "codeword")))
+            g_early_stop = !strcmp(argv[++i], "codeword") ? LNSFAID_STOP_CODEWORD : LNSFAID_STOP_GROUP; /* lnsfaid_set_early_stop */
         else if (!strcmp(argv[i], "--collect")) force_collect = true; /* collectflag = 1 from the first call (reference: once FER < 1e-5) */
         else { fprintf(stderr, usage, argv[0]); return 2; }
     }
@@ -78,6 +80,7 @@ int main(int argc, char** argv)
         return 2;
     }
     if (streams < 1 || gpus < 1 || gpus > streams) { fprintf(stderr, "need 1 <= gpus <= streams\n"); return 2; }
+    printf("early stop: %s\n", g_early_stop == LNSFAID_STOP_CODEWORD ? "codeword (every codeword stops on its own)" : "group (the reference's group of 32)");
     if (ranks < 1 || rank < 0 || rank >= ranks || (ranks > 1 && (gpus != 1 || !comm_file || ranks > streams))) {
         fprintf(stderr, "--ranks N needs --rank r in [0, N), --comm-file F, N <= streams, and one GPU per process\n");
         return 2;

@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(HERE, "csrc", "liblnsfaid.so")
 
 GROUP = 32
 MSG_REGISTERS, MSG_HBM = 1, 2  # lnsfaid_select_message_store
+STOP_GROUP, STOP_CODEWORD = 0, 1  # lnsfaid_set_early_stop
 
 
 class Code(C.Structure):
@@ -55,6 +56,10 @@ class GroupStats(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("bf_iterations", C.c_int32)]
 
 
+class CodewordStats(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("bf_iterations", C.c_int32), ("unsatisfied", C.c_int32)]
+
+
 # every symbol include/lnsfaid.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "lnsfaid_code_50gpon": (C.c_int, [C.POINTER(Code), C.POINTER(C.c_uint16), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -66,6 +71,10 @@ SYMBOLS = {
     "lnsfaid_set_cfg": (C.c_int, [C.c_void_p, C.POINTER(Cfg)]),
     "lnsfaid_decode": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "lnsfaid_decode_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "lnsfaid_set_early_stop": (C.c_int, [C.c_void_p, C.c_int32]),
+    "lnsfaid_early_stop": (C.c_int, [C.c_void_p]),
+    "lnsfaid_decode_codewords": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "lnsfaid_decode_codewords_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "lnsfaid_count_errors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
     "lnsfaid_count_errors_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
     "lnsfaid_frontend_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_size_t, C.c_int32,
@@ -194,6 +203,29 @@ class Decoder:
         self._check(self.lib.lnsfaid_decode(self.ctx, fix_input.ctypes.data, n_groups, out.ctypes.data,
                                             stats.ctypes.data), "lnsfaid_decode")
         return out, stats
+
+    def set_early_stop(self, rule):
+        """STOP_GROUP (default) or STOP_CODEWORD (lnsfaid_set_early_stop)"""
+        self._check(self.lib.lnsfaid_set_early_stop(self.ctx, rule), "lnsfaid_set_early_stop")
+
+    def early_stop(self):
+        return self.lib.lnsfaid_early_stop(self.ctx)
+
+    def decode_codewords(self, fix_input, n_groups, with_stats=True):
+        """lnsfaid_decode_codewords: (decodedBits int8 array, [n_groups * 32, 3] int32 array of iterations / bf_iterations /
+        unsatisfied, or None)"""
+        import numpy as np
+        N = self.code50.N
+        assert fix_input.dtype == np.int8 and fix_input.size == n_groups * GROUP * N and fix_input.flags.c_contiguous
+        out = np.empty(n_groups * GROUP * N, dtype=np.int8)
+        cw = np.zeros((n_groups * GROUP, 3), dtype=np.int32) if with_stats else None
+        self._check(self.lib.lnsfaid_decode_codewords(self.ctx, fix_input.ctypes.data, n_groups, out.ctypes.data,
+                                                      cw.ctypes.data if with_stats else None), "lnsfaid_decode_codewords")
+        return out, cw
+
+    def decode_codewords_device(self, d_fix_ptr, n_groups, d_out_ptr, d_cw_stats_ptr=None):
+        self._check(self.lib.lnsfaid_decode_codewords_device(self.ctx, d_fix_ptr, n_groups, d_out_ptr, d_cw_stats_ptr),
+                    "lnsfaid_decode_codewords_device")
 
     def decode_device(self, d_fix_ptr, n_groups, d_out_ptr, d_stats_ptr=None):
         self._check(self.lib.lnsfaid_decode_device(self.ctx, d_fix_ptr, n_groups, d_out_ptr, d_stats_ptr),
