@@ -134,6 +134,10 @@ SW_FN uint32_t sw_vconst(uint32_t k, uint32_t dep = 0u)
 #endif
 }
 
+/* table of sw_therm2num: entries 0 / 1 / 3 / 7 = 0xfb ^ 0 / 1 / 2 / 3 */
+#define SW_T2N_LO 0xf900fafbu
+#define SW_T2N_HI 0xf8000000u
+
 /* the register constants of the layer step, built ONCE per kernel: inside the layer function they would sit in a conditionally
  * executed block (the per-degree instances), out of which the compiler may not move an asm statement */
 struct SwK {
@@ -141,6 +145,9 @@ struct SwK {
     uint32_t cbit[8]; /* 0x01010101 << e; [0] = 0x01010101, [7] = 0x80808080 */
     uint32_t c7f;
     uint32_t c70;     /* NMS only: its minima keep 16 levels */
+    uint32_t n_lo, n_hi; /* thermometer code -> number (sw_therm2num) */
+    uint32_t c55, c33, c0f; /* merge masks of pass 2's sign words */
+    uint32_t cm27;    /* -0x27272727: the last constant of sw_update2, as an addend of v_add3_u32 */
 };
 SW_FN SwK sw_consts(uint32_t dep = 0u)
 {
@@ -153,6 +160,9 @@ SW_FN SwK sw_consts(uint32_t dep = 0u)
     for (int e = 0; e < 8; ++e) k.cbit[e] = sw_vconst(0x01010101u << e, dep);
     k.c7f = sw_vconst(0x7f7f7f7fu, dep);
     k.c70 = sw_vconst(0x70707070u, dep);
+    k.n_lo = sw_vconst(SW_T2N_LO, dep); k.n_hi = sw_vconst(SW_T2N_HI, dep);
+    k.c55 = sw_vconst(0x55555555u, dep); k.c33 = sw_vconst(0x33333333u, dep); k.c0f = sw_vconst(0x0f0f0f0fu, dep);
+    k.cm27 = sw_vconst(0u - 0x27272727u, dep);
     return k;
 }
 
@@ -167,6 +177,18 @@ SW_FN uint32_t sw_popcount7(uint32_t x)
     x = x - ((x >> 1) & 0x55555555u);
     x = (x & 0x33333333u) + ((x >> 2) & 0x33333333u);
     return (x + (x >> 4)) & 0x0f0f0f0fu;
+}
+/* The same number for the eight codes the minimum search can hold (0x00, 0x01, 0x03, 0x07, 0x0f, 0x1f, 0x3f, 0xff) from two v_perm_b32
+ * look-ups in ONE table: six instructions instead of eleven (sw_popcount7 stays as the definition the tests compare with).  The
+ * table maps the nibble patterns 0 / 1 / 3 / 7 (k = 0 .. 3 bits set) to 0xfb ^ k; a full low nibble is selector 15, which saturates
+ * to 0xff.  A = table[low nibble], B = table[bits 4..6]:
+ *   n <= 3: A = 0xfb ^ n, B = table[0] = 0xfb          -> A ^ B = n
+ *   n >= 4: A = 0xff,     B = 0xfb ^ (n - 4) = ~n      -> A ^ B = n   (0xfb = ~4, and n - 4 <= 3 only touches the low two bits) */
+SW_FN uint32_t sw_therm2num(uint32_t x, uint32_t n_lo, uint32_t n_hi)
+{
+    const uint32_t a = sw_perm(n_hi, n_lo, x & 0x0f0f0f0fu);
+    const uint32_t b = sw_perm(n_hi, n_lo, (x >> 4) & 0x07070707u);
+    return a ^ b;
 }
 /* 0xff in every byte that is zero; bytes must be <= 0x7f */
 SW_FN uint32_t sw_zero_mask(uint32_t x, uint32_t sel_sign) { return ~sw_mask7(x + 0x7f7f7f7fu, sel_sign); }
@@ -332,6 +354,103 @@ SW_FN uint32_t sw_update(uint32_t tb, uint32_t ms, const SwUpd& u, uint32_t sel_
     return sw_bitop3<SW_TT_SEL>(mo, hi, sw_bitop3<SW_TT_SEL>(mq, zb, c80)) - sb;
 }
 
+/* The same update in fewer instructions (sw_update / sw_update_consts stay as the definition the tests compare with):
+ *  - the constants that depend on the sign of the new message differ by c only: with d = (L < 0 ? 0 : c) they are za = zc + d
+ *    (zc = za_p - c), sb = 0x27 - d and, for the min-sum decoders, oc = 0x3f - d, hi = 0xbe - d: ONE masked c per edge and two
+ *    three-operand additions instead of a select per constant;
+ *  - z can only exceed the upper limit where t > 0 and only fall below the lower one where t < 0 (the limits are at least 24
+ *    away from 0 and |z - t| <= 7), so ONE "out of range" test - bit 7 of ~zb | (zb - oc) - and the limit picked by the sign of t
+ *    replace the two tests with their two mask expansions and two selects.
+ * ms: byte mask, 0xff where t is not negative (plain or back-tracked sign: they differ at t == 0 only); fm: the row's mask F, the
+ * new message is not negative where ms ^ fm is set. */
+struct SwUpd2 {
+    uint32_t c, fm, zc, oc, hi;
+};
+template <bool MINSUM>
+SW_FN SwUpd2 sw_update2_consts(uint32_t c, uint32_t fm, uint32_t bias)
+{
+    SwUpd2 u;
+    u.c = c; u.fm = fm;
+    u.zc = 0x1f1f1f1fu - bias - c;
+    u.oc = MINSUM ? 0u - 0x3f3f3f3fu : 0x3f3f3f3fu - c; /* min-sum: added together with d */
+    u.hi = MINSUM ? 0xbebebebeu : 0xbebebebeu - c;
+    return u;
+}
+/* the stages of sw_update2, separately: pass 2 of the layer step runs them stage by stage over a group of edges */
+SW_FN uint32_t sw_upd2_d(uint32_t ms, const SwUpd2& u) { return sw_bitop3<SW_TT_XORAND>(ms, u.fm, u.c); }
+SW_FN uint32_t sw_upd2_zb(uint32_t tb, uint32_t d, const SwUpd2& u) { return tb + d + u.zc; }
+template <bool MINSUM>
+SW_FN uint32_t sw_upd2_out(uint32_t zb, uint32_t d, const SwUpd2& u)
+{
+    const uint32_t ov = MINSUM ? zb + d + u.oc : zb - u.oc;
+    return sw_bitop3<0xcf>(zb, ov, ov); /* ~a | b: bit 7 set = under or over */
+}
+template <bool MINSUM>
+SW_FN uint32_t sw_upd2_limit(uint32_t ms, uint32_t d, const SwUpd2& u, uint32_t c80)
+{
+    return sw_bitop3<SW_TT_ANDOR>(ms, MINSUM ? u.hi - d : u.hi, c80); /* hi where t >= 0, 0x80 (z = -31) where t < 0 */
+}
+SW_FN uint32_t sw_upd2_en(uint32_t mout, uint32_t lim, uint32_t zb, uint32_t d, uint32_t cm27) { return sw_bitop3<SW_TT_SEL>(mout, lim, zb) + d + cm27; }
+/* tb: t + 128 (+ bias) per byte; cm27: -0x27272727 in a register */
+template <bool MINSUM>
+SW_FN uint32_t sw_update2(uint32_t tb, uint32_t ms, const SwUpd2& u, uint32_t sel_sign, uint32_t c80, uint32_t cm27)
+{
+    const uint32_t d = sw_upd2_d(ms, u);
+    const uint32_t zb = sw_upd2_zb(tb, d, u);
+    const uint32_t mout = sw_mask7(sw_upd2_out<MINSUM>(zb, d, u), sel_sign);
+    return sw_upd2_en(mout, sw_upd2_limit<MINSUM>(ms, d, u, c80), zb, d, cm27);
+}
+
+/* ---- minimum search over thermometer codes: running minimum t1, second minimum t2 (with multiplicity) and the five index
+ * accumulators ta[] (see "binary index" in sw_layer_step) ---- */
+/* one edge (index j) at a time */
+SW_FN void sw_min_edge(uint32_t& t1, uint32_t& t2, uint32_t ta[5], uint32_t u, int j)
+{
+    t2 = sw_bitop3<SW_TT_A_AND_BORC>(t2, t1, u); /* VECTOR_MIN_2 with the old min1 */
+    t1 &= u;
+#pragma unroll
+    for (int b = 0; b < 5; ++b)
+        if (((j >> b) & 1) == (b >= 3 ? 1 : 0)) ta[b] &= u;
+}
+/* The four edges j0 .. j0 + 3 (j0 a multiple of 4) as one set: their minimum q, their second minimum and the partial minima the
+ * index accumulators need, then ONE merge into the running pair.  Index bits 2..4 are constant over an aligned group of four, so
+ * ta[2..4] take q whole; ta[1] takes the first pair, ta[0] edges 0 and 2.  Minimum and second minimum of a multiset do not depend
+ * on the order in which it is merged, so every bit equals what four calls of sw_min_edge give - in fewer operations, because the
+ * pairs and the quad are shared by t1 and the accumulators. */
+SW_FN void sw_min_quad(uint32_t& t1, uint32_t& t2, uint32_t ta[5], uint32_t v0, uint32_t v1, uint32_t v2, uint32_t v3, int j0)
+{
+    const uint32_t p0 = v0 & v1, p1 = v2 & v3, q = p0 & p1;
+    const uint32_t o0 = v0 | v1, o1 = v2 | v3;
+    const uint32_t m2 = sw_bitop3<SW_TT_A_AND_BORC>(o0, p0, p1); /* second minimum of the four = m2 & o1: folded into the merge */
+    const uint32_t y = sw_bitop3<SW_TT_A_AND_BORC>(t2, t1, q);
+    t2 = sw_bitop3<SW_TT_AND3>(y, m2, o1);
+    t1 &= q;
+    ta[0] = sw_bitop3<SW_TT_AND3>(ta[0], v0, v2);
+    ta[1] &= p0;
+    if (((j0 >> 2) & 1) == 0) ta[2] &= q;
+    if (((j0 >> 3) & 1) == 1) ta[3] &= q;
+    if (((j0 >> 4) & 1) == 1) ta[4] &= q;
+}
+
+/* Sign words of pass 2 (bit e of byte k of ns[g]: the V2C on edge 8 g + e of row k is not negative), four edges j0 .. j0 + 3
+ * (j0 a multiple of 4) at a time from their byte masks ms[]: two masks interleaved bit by bit, two pairs by bit pairs, two groups by
+ * nibbles - 7 selects per 8 edges and three constants instead of 8 and eight.  Bits of edges the row does not have are copies of
+ * other edges' bits: the caller masks them (`valid`). */
+/* one edge at a time; cbit = 0x01010101 << (j mod 8) */
+SW_FN void sw_sign_edge(uint32_t ns[3], uint32_t ms, int j, uint32_t cbit) { ns[j >> 3] = sw_bitop3<SW_TT_ANDNOT_OR>(ns[j >> 3], ms, cbit); }
+template <int NJ>
+SW_FN void sw_sign_quad(uint32_t ns[3], const uint32_t* ms, int j0, int deg, bool fixed, uint32_t c55, uint32_t c33, uint32_t c0f)
+{
+    uint32_t m[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) m[g] = (j0 + g < NJ && (fixed || j0 + g < deg)) ? ms[j0 + g < NJ ? j0 + g : 0] : 0u;
+    const bool has1 = j0 + 1 < NJ, has2 = j0 + 2 < NJ, has3 = j0 + 3 < NJ;
+    const uint32_t a = has1 ? sw_bitop3<SW_TT_SEL>(c55, m[0], m[1]) : m[0];
+    const uint32_t b = has3 ? sw_bitop3<SW_TT_SEL>(c55, m[2], m[3]) : m[2];
+    const uint32_t q = has2 ? sw_bitop3<SW_TT_SEL>(c33, a, b) : a;
+    ns[j0 >> 3] = (j0 & 4) ? sw_bitop3<SW_TT_SEL>(c0f, ns[j0 >> 3], q) : q;
+}
+
 /* ERA helpers.  Plane bit of the variable node at LDS byte address a (interleaved image: block column in the high bits,
  * dword = node mod 64, byte = node div 64); returns 0 / 1. */
 SW_FN uint32_t sw_plane_bit(const SwLds& lds, uint32_t era_plane, uint32_t a)
@@ -380,6 +499,10 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
     static_assert(!ERA || METHOD == 2, "the erasure exists in Decode_FAID only");
     constexpr int NJ = DEG > 0 ? DEG : SW_MAX_DEG;
     constexpr bool MINSUM = SW_MINSUM(METHOD);
+    /* the minimum search merges aligned groups of four edges (pass 1); the per-degree instances only: in the generic one every
+     * edge is conditional and the group's values would have to be kept under a select each */
+    constexpr bool QUADS = WAVES == 1 && SW_ILP == 4 && DEG > 0;
+    constexpr bool NSTREE = WAVES == 1 && SW_ILP == 4; /* pass 2 packs its sign words four edges at a time (sw_sign_quad) */
     const uint32_t c01 = K.cbit[0], c80 = K.cbit[7], c7f = K.c7f, c78 = K.c78, c0642 = K.c0642, cfc = K.cfc, sel_sign = K.sel_sign;
     const uint32_t tid4 = lane << 2;
     /* the layer's circulants first (scalar loads share the LDS counter: in flight together with LDS reads they force full drains) */
@@ -444,7 +567,9 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
     for (int j0 = 0; j0 < NJ; j0 += SW_ILP) {
         uint32_t r_[SW_ILP], x_[SW_ILP], s_[SW_ILP], k_[SW_ILP], a_[SW_ILP], i_[SW_ILP], u_[SW_ILP];
 #define SW_EDGES(...) _Pragma("unroll") for (int g = 0; g < SW_ILP; ++g) { const int j = j0 + g; if (j < NJ && (DEG > 0 || j < deg) && SW_OWN(j)) { __VA_ARGS__ } }
-        SW_EDGES(r_[g] = sw_alignbyte(ld[j], ld[j], rq[j]);)                                  /* byte k = En + 120 of row k */
+        /* byte k = En + 120 of row k.  The group's LAST read is consumed first: LDS reads return in order, so the one s_waitcnt in
+         * front of it covers the group (in ascending order every edge gets a wait of its own) */
+        _Pragma("unroll") for (int g = SW_ILP - 1; g >= 0; --g) { const int j = j0 + g; if (j < NJ && (DEG > 0 || j < deg) && SW_OWN(j)) r_[g] = sw_alignbyte(ld[j], ld[j], rq[j]); }
         SW_EDGES(x_[g] = (j & 7) ? cur.x[j >> 3] >> (j & 7) : cur.x[j >> 3];)
         SW_EDGES(s_[g] = sw_bitop3<SW_TT_ANDOR>(x_[g], c01, c0642);)
         SW_EDGES(k_[g] = sw_perm(kt_hi, kt_lo, s_[g]);)
@@ -493,10 +618,14 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
         }
         SW_EDGES(
             if (WAVES == 2) sx ^= ts[j]; /* (the neighbour edge belongs to the other wave) */
-            else if (j & 1) sx = sw_bitop3<SW_TT_XOR3>(sx, ts[j - 1], ts[j]); else if (j == (DEG > 0 ? DEG : deg) - 1) sx ^= ts[j];
-            t2 = sw_bitop3<SW_TT_A_AND_BORC>(t2, t1, u_[g]);      /* VECTOR_MIN_2 with the old min1 */
-            t1 &= u_[g];
-            _Pragma("unroll") for (int b = 0; b < 5; ++b) if (((j >> b) & 1) == (b >= 3 ? 1 : 0)) ta[b] &= u_[g];)
+            else if (j & 1) sx = sw_bitop3<SW_TT_XOR3>(sx, ts[j - 1], ts[j]); else if (j == (DEG > 0 ? DEG : deg) - 1) sx ^= ts[j];)
+        if (QUADS) {
+            uint32_t v_[4];
+            _Pragma("unroll") for (int g = 0; g < 4; ++g) v_[g] = j0 + g < NJ ? u_[g] : 0xffffffffu; /* no such edge: "no minimum" */
+            sw_min_quad(t1, t2, ta, v_[0], v_[1], v_[2], v_[3], j0);
+        } else {
+            SW_EDGES(sw_min_edge(t1, t2, ta, u_[g], j);)
+        }
     }
 
     if (WAVES == 2) {
@@ -521,7 +650,8 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
     }
 
     /* ---- the row's new magnitudes ---- */
-    uint32_t min1 = sw_popcount7(t1), min2 = sw_popcount7(t2);
+    const uint32_t n_lo = WAVES == 2 ? SW_T2N_LO : K.n_lo, n_hi = WAVES == 2 ? SW_T2N_HI : K.n_hi;
+    const uint32_t min1 = sw_therm2num(t1, n_lo, n_hi), min2 = sw_therm2num(t2, n_lo, n_hi);
     uint32_t c1n, c2n;
     if (METHOD == 0) {
         /* the levels of the search ARE cste() of the minima (CLDPC.cpp:337-352: cste_2 from min1, cste_1 from min2, one factor) */
@@ -583,45 +713,27 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
     SW_SCHED_FENCE();
 
     /* ---- pass 2 (CDecoder_FAID.cpp:909-929, CDecoder_OMS.cpp:452-471): every edge as if it carried c2 ---- */
-    const SwUpd u2 = sw_update_consts<MINSUM>(c2n, fm, bias);
+    const SwUpd2 u2 = sw_update2_consts<MINSUM>(c2n, fm, bias);
+    const uint32_t cm27 = WAVES == 2 ? 0u - 0x27272727u : K.cm27; /* (two waves per codeword: 128 registers, none to spare for constants) */
     uint32_t ns[3] = { 0u, 0u, 0u };
     uint32_t cbit[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) cbit[e] = K.cbit[e];
-    /* The two clamp tests of an edge, "over" = bit 7 of zb - oc and "not under" = bit 7 of zb, as select masks.  SW_CLAMP7: 0x7f
-     * masks from three full-rate operations each (b = x & 0x80.., b - (b >> 7)) instead of 0xff masks from a left shift and a
-     * v_perm_b32 (both half rate): enough here, because bit 7 is set in everything the selects choose between (zb where it is not
-     * under, 0x80 where it is, hi = 0xbe - c) */
-#ifdef SW_CLAMP7
-#define SW_CLAMP_MASKS(MO, MQ, OC, ZA)                                                                               \
-        SW_EDGES(MO[g] = OC[g] & c80;)                                                                               \
-        SW_EDGES(MQ[g] = ZA[g] & c80;)                                                                               \
-        SW_EDGES(MO[g] = MO[g] - (MO[g] >> 7);)                                                                      \
-        SW_EDGES(MQ[g] = MQ[g] - (MQ[g] >> 7);)
-#define SW_CLAMP_LOW(MQ, ZA) sw_bitop3<0xea>(ZA, MQ, c80) /* (a & b) | c */
-#else
-#define SW_CLAMP_MASKS(MO, MQ, OC, ZA)                                                                               \
-        SW_EDGES(MO[g] = sw_mask7(OC[g], sel_sign);)     /* over      */                                             \
-        SW_EDGES(MQ[g] = sw_mask7(ZA[g], sel_sign);)     /* not under */
-#define SW_CLAMP_LOW(MQ, ZA) sw_bitop3<SW_TT_SEL>(MQ, ZA, c80)
-#endif
-    /* one group of edges: the arithmetic (ARITH) and the LDS writes (STORE) separately, stage by stage over the group as in pass 1 */
+    /* one group of edges: the arithmetic (ARITH) and the LDS writes (STORE) separately, stage by stage over the group as in pass 1
+     * (the stages of sw_update2) */
 #define SW_PASS2_ARITH(J0, EN)                                                                                       \
     {                                                                                                                \
         const int j0 = (J0);                                                                                         \
-        uint32_t za[SW_ILP], sb[SW_ILP], oc[SW_ILP], hi[SW_ILP], mo[SW_ILP], mq[SW_ILP];                             \
-        SW_EDGES(za[g] = sw_bitop3<SW_TT_SEL>(ms[j], u2.za[1], u2.za[0]);)                                           \
-        SW_EDGES(sb[g] = sw_bitop3<SW_TT_SEL>(ms[j], u2.sb[1], u2.sb[0]);)                                           \
-        SW_EDGES(oc[g] = MINSUM ? sw_bitop3<SW_TT_SEL>(ms[j], u2.oc[1], u2.oc[0]) : u2.oc[1];)                       \
-        SW_EDGES(hi[g] = MINSUM ? sw_bitop3<SW_TT_SEL>(ms[j], u2.hi[1], u2.hi[0]) : u2.hi[1];)                       \
-        SW_EDGES(za[g] = tb[j] + za[g];)                 /* zb */                                                    \
-        SW_EDGES(oc[g] = za[g] - oc[g];)                                                                             \
-        SW_CLAMP_MASKS(mo, mq, oc, za)                                                                               \
-        SW_EDGES(EN[g] = SW_CLAMP_LOW(mq[g], za[g]);)                                                                \
-        SW_EDGES(EN[g] = sw_bitop3<SW_TT_SEL>(mo[g], hi[g], EN[g]);)                                                 \
-        SW_EDGES(EN[g] = EN[g] - sb[g];)                                                                             \
+        uint32_t d_[SW_ILP], zb[SW_ILP], mo[SW_ILP], lm[SW_ILP];                                                     \
+        SW_EDGES(d_[g] = sw_upd2_d(ms[j], u2);)                                                                      \
+        SW_EDGES(zb[g] = sw_upd2_zb(tb[j], d_[g], u2);)                                                              \
+        SW_EDGES(mo[g] = sw_upd2_out<MINSUM>(zb[g], d_[g], u2);)                                                     \
+        SW_EDGES(mo[g] = sw_mask7(mo[g], sel_sign);)     /* under or over */                                         \
+        SW_EDGES(lm[g] = sw_upd2_limit<MINSUM>(ms[j], d_[g], u2, c80);)                                              \
+        SW_EDGES(EN[g] = sw_upd2_en(mo[g], lm[g], zb[g], d_[g], cm27);)                                              \
         SW_EDGES(EN[g] = sw_alignbyte(EN[g], EN[g], 4u - rq[j]);)                                                    \
-        SW_EDGES(ns[j >> 3] = sw_bitop3<SW_TT_ANDNOT_OR>(ns[j >> 3], ms[j], cbit[j & 7]);) /* bit e of byte k: V2C on edge 8 g + e not negative */ \
+        if (NSTREE) sw_sign_quad<NJ>(ns, ms, j0, deg, DEG > 0, K.c55, K.c33, K.c0f);                                 \
+        else SW_EDGES(sw_sign_edge(ns, ms[j], j, cbit[j & 7]);)                                                      \
     }
 #define SW_PASS2_STORE(J0, EN)                                                                                       \
     {                                                                                                                \
@@ -680,9 +792,8 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
     const uint32_t tsA = MINSUM ? tbA : tbA - (xb | c0642);
     const uint32_t msA = sw_mask7(tsA, sel_sign);
     const uint32_t negA = ~(msA ^ fm); /* byte mask: the new message on the arg-min edge is negative */
-    /* used once: flip = 0 leaves [1] = "not negative" constants, [0] = "negative" ones, picked by the combined mask */
-    const SwUpd u1 = sw_update_consts<MINSUM, false>(c1n, 0u, bias);
-    const uint32_t enA = sw_update<MINSUM>(tbA, ~negA, u1, sel_sign, c80);
+    const SwUpd2 u1 = sw_update2_consts<MINSUM>(c1n, fm, bias);
+    const uint32_t enA = sw_update2<MINSUM>(tbA, msA, u1, sel_sign, c80, cm27);
 
 #pragma unroll
     for (int jg = 2 * SW_ILP; jg < NJ; jg += SW_ILP) { /* the remaining groups of pass 2 */
@@ -693,8 +804,6 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
 #undef SW_EDGES
 #undef SW_PASS2_ARITH
 #undef SW_PASS2_STORE
-#undef SW_CLAMP_MASKS
-#undef SW_CLAMP_LOW
     if (WAVES == 2) {
         if (WAVE == 1) { xch.put(0, ns[0]); xch.put(1, ns[1]); xch.put(2, ns[2]); }
         xch.barrier(); /* D: wave 1's En is in LDS */

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Per-class VALU instruction histogram of the basic blocks of a gfx950 kernel (the judge's "full-rate vs half-rate" split).
 
-usage: isa_histogram.py <file.s> [kernel-name-substring] [--blocks N]
+usage: isa_histogram.py <file.s> [kernel-name-substring] [--blocks N] [--all-ops]
+--all-ops: "top" lists every VALU mnemonic of the block, not only the twelve most frequent ones.
 Classes (tools/ubench/valu_rate.hip, tools/ubench/issue_mix.hip, profiles/*/ubench_*.txt): a wave64 VALU instruction issues in 2 cycles
 ("full") unless it is a LEFT shift, a packed 16-bit operation, a three-source VOP3 other than v_bitop3_b32, an integer
 multiply, a dot product, or reads an SGPR operand ("half", 4 cycles).  Prints the largest blocks of the kernel with their
@@ -41,6 +42,7 @@ def main():
     path = sys.argv[1]
     want = sys.argv[2] if len(sys.argv) > 2 and not sys.argv[2].startswith("--") else None
     nblocks = int(sys.argv[sys.argv.index("--blocks") + 1]) if "--blocks" in sys.argv else 4
+    ntop = None if "--all-ops" in sys.argv else 12
     kernel, block = None, None
     blocks = collections.OrderedDict()
     for raw in open(path):
@@ -71,7 +73,8 @@ def main():
                      "lds": sum(1 for i in ins if i.startswith("ds_")), "salu": sum(1 for i in ins if i.startswith("s_") and not i.startswith("s_nop") and not i.startswith("s_waitcnt")),
                      "s_nop": sum(1 for i in ins if i.startswith("s_nop")), "vmem": sum(1 for i in ins if i.startswith(("global_", "buffer_", "flat_"))),
                      "issue_cycles_weighted": 2 * c["full"] + 4 * (c["half"] + c["half(sgpr)"]),
-                     "top": ops.most_common(12)})
+                     "s_waitcnt": sum(1 for i in ins if i.startswith("s_waitcnt")),
+                     "top": ops.most_common(ntop)})
     rows.sort(key=lambda r: -r["valu"])
     for r in rows[:nblocks]:
         print(json.dumps(r))
