@@ -217,6 +217,43 @@ int lnsfaid_count_errors(lnsfaid_ctx* ctx, const int8_t* decodedBits, const int8
 int lnsfaid_count_errors_device(lnsfaid_ctx* ctx, const int8_t* d_decodedBits,
                                 const int8_t* d_inputBits, size_t n_groups, uint64_t out[4]);
 
+/* ---- packed decode I/O --------------------------------------------------------------------------------
+ * The same decodes with 4-bit LLRs in and one bit per decision out: 11 040 instead of 35 328 bytes per 50G-PON codeword.
+ *   llr4  packed fixInput.  Elements in the order of fixInput (per group [32][K] information LLRs, then [32][M] parity LLRs;
+ *         group g starts at byte g * 16 * n_var).  Element e is a 4-bit two's-complement nibble in byte e / 2: the low nibble
+ *         when e is even, the high one when e is odd.  The nibble 0x8 (-8) decodes exactly as the int8 value -8 does.
+ *   bits  packed decodedBits.  Per codeword n_var / 32 little-endian 32-bit words in the order of decodedBits, codeword c of
+ *         the batch at word c * n_var / 32; bit b of word w is decodedBits[32 w + b] (numpy: packbits(..., bitorder="little")).
+ *         The information bits are the first K / 32 words of a codeword.
+ *   msg   packed message bits for the counters: per codeword K bits in the same bit order, codeword c at byte c * K / 8; NULL
+ *         means the all-zero codeword.
+ * Device pointers (the _device calls) must be 4-byte aligned, LNSFAID_E_INVAL otherwise; host pointers may have any alignment
+ * (they are copied through packed staging buffers of the context, allocated at its first packed host call).  n_var, K and M
+ * are multiples of z = 256, so every offset above is a multiple of 128 bytes.
+ * Results, stats, cw_stats and counters are those of the int8 calls for the same data.  Configurations of the four-rows kernel
+ * decode in packed twins of its kernels; the others (two-rows kernel, lnsfaid_select_waves(ctx, 2)) convert on the device
+ * through the buffers of lnsfaid_io_buffers (their content is overwritten) and, like the int8 calls, return LNSFAID_E_INVAL
+ * under the per-codeword rule.  Host calls of one-group contexts decode on the context's own stream, not through the call
+ * combiner.  NULL buffers with n_groups > 0 and n_groups > max_groups: LNSFAID_E_INVAL; n_groups 0: no-op. */
+int lnsfaid_decode_packed(lnsfaid_ctx* ctx, const uint8_t* llr4, size_t n_groups, uint32_t* bits, lnsfaid_group_stats* stats);
+int lnsfaid_decode_packed_device(lnsfaid_ctx* ctx, const uint8_t* d_llr4, size_t n_groups, uint32_t* d_bits,
+                                 lnsfaid_group_stats* d_stats);
+int lnsfaid_decode_codewords_packed(lnsfaid_ctx* ctx, const uint8_t* llr4, size_t n_groups, uint32_t* bits,
+                                    lnsfaid_codeword_stats* cw_stats);
+int lnsfaid_decode_codewords_packed_device(lnsfaid_ctx* ctx, const uint8_t* d_llr4, size_t n_groups, uint32_t* d_bits,
+                                           lnsfaid_codeword_stats* d_cw_stats);
+/* lnsfaid_count_errors on packed decisions and message bits (XOR and popcount over the K information bits of a codeword) */
+int lnsfaid_count_errors_packed(lnsfaid_ctx* ctx, const uint32_t* bits, const uint8_t* msg, size_t n_groups, uint64_t out[4]);
+int lnsfaid_count_errors_packed_device(lnsfaid_ctx* ctx, const uint32_t* d_bits, const uint8_t* d_msg, size_t n_groups,
+                                       uint64_t out[4]);
+/* Host only, no context, no GPU.  lnsfaid_pack_llr4: n_values int8 LLRs (even count, each in [-8, 7]) -> n_values / 2 bytes of
+ * llr4.  lnsfaid_unpack_bits: n_bits (a multiple of 32) packed decisions -> int8 0/1.  lnsfaid_pack_bits: n_bits (a multiple
+ * of 8) int8 0/1 message bits -> n_bits / 8 bytes.  LNSFAID_E_INVAL for a count or a value outside these rules (the output is
+ * then incomplete). */
+int lnsfaid_pack_llr4(const int8_t* fixInput, size_t n_values, uint8_t* llr4);
+int lnsfaid_unpack_bits(const uint32_t* bits, size_t n_bits, int8_t* decodedBits);
+int lnsfaid_pack_bits(const int8_t* inputBits, size_t n_bits, uint8_t* packed);
+
 /* ---- front-end on the device (optional, the host generator stays the parity source) ---- */
 
 /*

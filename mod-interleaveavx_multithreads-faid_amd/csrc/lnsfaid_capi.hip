@@ -29,6 +29,13 @@ extern "C" hipError_t lf_launch_decode4(int method, int ef, int rm, const LfKern
 extern "C" int lf_decode4_rm_layers(void);
 extern "C" const void* lf_decode4cw_func(int method, int ef, int rm);
 extern "C" hipError_t lf_launch_decode4cw(int method, int ef, int rm, const LfCwArgs* args, size_t lds_bytes, hipStream_t stream);
+extern "C" const void* lf_decode4p_func(int method, int ef, int rm, int per_codeword);
+extern "C" hipError_t lf_launch_decode4p(int method, int ef, int rm, const LfKernelArgs* args, size_t lds_bytes, hipStream_t stream);
+extern "C" hipError_t lf_launch_decode4pcw(int method, int ef, int rm, const LfCwArgs* args, size_t lds_bytes, hipStream_t stream);
+extern "C" hipError_t lf_launch_unpack_llr4(const uint8_t* d_llr4, int8_t* d_fix, size_t n_values, hipStream_t stream);
+extern "C" hipError_t lf_launch_pack_bits(const int8_t* d_decoded, uint32_t* d_bits, size_t n_values, hipStream_t stream);
+extern "C" hipError_t lf_launch_count_errors_packed(const uint32_t* d_bits, const uint32_t* d_msg, int n_var, int k_info, size_t n_cw,
+                                                    unsigned long long* out, hipStream_t stream);
 extern "C" const void* lf_decode5_func(int method);
 extern "C" int lf_decode5_threads(void);
 extern "C" hipError_t lf_launch_decode5(int method, const LfKernelArgs* args, size_t lds_bytes, hipStream_t stream);
@@ -112,14 +119,18 @@ struct lnsfaid_ctx {
     int8_t* d_io_out = nullptr;
     lnsfaid_group_stats* d_io_stats = nullptr;
     lnsfaid_codeword_stats* d_io_cw_stats = nullptr; /* lnsfaid_decode_codewords, allocated at its first call */
+    /* staging for the packed host-pointer entry points, allocated at the first packed call */
+    uint8_t* d_pk_in = nullptr;   /* llr4, 16 * n_var bytes per group */
+    uint32_t* d_pk_out = nullptr; /* bits, n_var words per group */
+    lnsfaid_group_stats* d_pk_stats = nullptr;
     int early_stop = LNSFAID_STOP_GROUP; /* rule of lnsfaid_decode / lnsfaid_decode_device (lnsfaid_set_early_stop) */
     int rows_per_lane = 0; /* 0: pick per configuration; 2 / 4: forced (lnsfaid_select_kernel) */
     int waves_per_cw = 0;  /* 0 / 1: one wave per codeword; 2: lnsfaid_kernel5.hip where it applies (lnsfaid_select_waves) */
     int msg_store = 0;     /* 0: pick per code; 1: registers; 2: streamed through HBM (lnsfaid_select_message_store) */
     struct LfCombiner* comb = nullptr; /* call combiner this one-group context is a member of (see below) */
     int comb_slot = -1;
-    const void* checked_fn[2] = {};           /* kernel instance kernel_check() last looked at, per early-stop rule */
-    int resident_wg[2] = {}, lds_wg[2] = {};  /* its workgroups per CU: what the occupancy query says / what its LDS alone allows */
+    const void* checked_fn[4] = {};           /* kernel instance kernel_check() last looked at, per early-stop rule (+ 2: packed I/O) */
+    int resident_wg[4] = {}, lds_wg[4] = {};  /* its workgroups per CU: what the occupancy query says / what its LDS alone allows */
     void* comm = nullptr;      /* ncclComm_t for lnsfaid_allreduce_counters */
     bool comm_owned = false;
     unsigned long long* d_reduce = nullptr;
@@ -337,6 +348,7 @@ extern "C" void lnsfaid_destroy(lnsfaid_ctx* ctx)
     (void)hipFree(ctx->d_remaining); (void)hipFree(ctx->d_live); (void)hipFree(ctx->d_counters);
     (void)hipFree(ctx->d_io_in); (void)hipFree(ctx->d_io_out); (void)hipFree(ctx->d_io_stats);
     (void)hipFree(ctx->d_io_cw_stats);
+    (void)hipFree(ctx->d_pk_in); (void)hipFree(ctx->d_pk_out); (void)hipFree(ctx->d_pk_stats);
     (void)hipFree(ctx->d_fe_seeds); (void)hipFree(ctx->d_fe_draws); (void)hipFree(ctx->d_fe_codeword);
     (void)hipFree(ctx->d_fe_frames); (void)hipFree(ctx->d_fe_input);
     (void)hipFree(ctx->d_enc_sup); (void)hipFree(ctx->d_enc_off); (void)hipFree(ctx->d_fe_keys);
@@ -527,8 +539,16 @@ static bool use_msg_registers(const lnsfaid_ctx* ctx)
  * same message store; the two-rows kernel and the two-waves kernel have none. */
 static bool cw_possible(const lnsfaid_ctx* ctx) { return ctx->waves_per_cw != 2 && use_kernel4(ctx); }
 
-static const void* selected_kernel(const lnsfaid_ctx* ctx, int* threads, int rule)
+/* The packed decoders (lnsfaid_kernel4p.hip) are twins of the one-wave four-rows kernels; the other configurations decode
+ * packed I/O through conversion kernels around the int8 decode. */
+static bool packed_kernel(const lnsfaid_ctx* ctx) { return use_kernel4(ctx) && !use_kernel5(ctx); }
+
+static const void* selected_kernel(const lnsfaid_ctx* ctx, int* threads, int rule, bool packed = false)
 {
+    if (packed) {
+        *threads = lf_decode4_threads();
+        return lf_decode4p_func(ctx->hcfg.method, ctx->hcfg.ef, use_msg_registers(ctx) ? 1 : 0, rule == LNSFAID_STOP_CODEWORD ? 1 : 0);
+    }
     if (rule == LNSFAID_STOP_CODEWORD) {
         *threads = lf_decode4_threads();
         return cw_possible(ctx) ? lf_decode4cw_func(ctx->hcfg.method, ctx->hcfg.ef, use_msg_registers(ctx) ? 1 : 0) : nullptr;
@@ -566,12 +586,13 @@ extern "C" int lnsfaid_message_store(const lnsfaid_ctx* ctx)
  *  - how many of its workgroups a CU holds.  The decoders are sized so that LDS alone decides that (50G-PON: 20 424 B per
  *    codeword, 8 per CU); one more register or LDS word in the wrong place halves it, which costs ~40 % of the throughput and
  *    nothing else would show.  Recorded for lnsfaid_kernel_residency, printed under LNSFAID_TRACE. */
-static int kernel_check(lnsfaid_ctx* ctx, int rule)
+static int kernel_check(lnsfaid_ctx* ctx, int rule, bool packed = false)
 {
     int threads = 0;
-    const void* fn = selected_kernel(ctx, &threads, rule);
+    const void* fn = selected_kernel(ctx, &threads, rule, packed);
     if (!fn) return rule == LNSFAID_STOP_CODEWORD ? LNSFAID_E_INVAL : LNSFAID_E_INTERNAL; /* no per-codeword instance */
-    if (fn == ctx->checked_fn[rule]) return LNSFAID_OK;
+    const int slot = rule + (packed ? 2 : 0);
+    if (fn == ctx->checked_fn[slot]) return LNSFAID_OK;
     hipFuncAttributes at;
     HIP_TRY(hipFuncGetAttributes(&at, fn));
     if (at.sharedSizeBytes != 0) {
@@ -588,7 +609,7 @@ static int kernel_check(lnsfaid_ctx* ctx, int rule)
     int by_lds = (int)(lds_cu / ((ctx->lds_bytes + gran - 1) / gran * gran));
     const int by_waves = 32 / ((threads + 63) / 64); /* 32 wave slots per CU */
     if (by_lds > by_waves) by_lds = by_waves;
-    ctx->checked_fn[rule] = fn; ctx->resident_wg[rule] = wg; ctx->lds_wg[rule] = by_lds;
+    ctx->checked_fn[slot] = fn; ctx->resident_wg[slot] = wg; ctx->lds_wg[slot] = by_lds;
     static const bool trace = getenv("LNSFAID_TRACE") != nullptr;
     if (trace)
         fprintf(stderr, "[lnsfaid] decode kernel: %d threads, %d VGPRs, %zu B LDS per workgroup, %d workgroups per CU (LDS alone: %d)%s\n",
@@ -609,10 +630,12 @@ extern "C" int lnsfaid_kernel_residency(lnsfaid_ctx* ctx, int32_t* workgroups_pe
 
 /* status_preloaded: ctx->d_status[0] already holds the decision point of every codeword (the call combiner marks the groups
  * that take no part in a batch as finished); otherwise every codeword is fresh */
+/* packed: the buffers are llr4 / bits and the packed twin of the four-rows kernel runs (packed_kernel() must hold) */
 static int decode_device_impl(lnsfaid_ctx* ctx, const int8_t* d_fixInput, size_t n_groups, int8_t* d_decodedBits,
-                              lnsfaid_group_stats* d_stats, bool status_preloaded);
+                              lnsfaid_group_stats* d_stats, bool status_preloaded, bool packed = false);
 static int decode_cw_device_impl(lnsfaid_ctx* ctx, const int8_t* d_fixInput, size_t n_groups, int8_t* d_decodedBits,
-                                 lnsfaid_group_stats* d_stats, lnsfaid_codeword_stats* d_cw_stats, bool status_preloaded);
+                                 lnsfaid_group_stats* d_stats, lnsfaid_codeword_stats* d_cw_stats, bool status_preloaded,
+                                 bool packed = false);
 /* the context's rule, or the per-codeword one (lnsfaid_decode_codewords*) */
 static int decode_device_rule(lnsfaid_ctx* ctx, const int8_t* d_fixInput, size_t n_groups, int8_t* d_decodedBits, lnsfaid_group_stats* d_stats,
                               lnsfaid_codeword_stats* d_cw_stats, int rule, bool status_preloaded)
@@ -645,7 +668,7 @@ extern "C" int lnsfaid_early_stop(const lnsfaid_ctx* ctx) { return ctx ? ctx->ea
  * double buffer and no "codewords left" counter - one launch, one wait.  The group records are maxima, taken with atomics over
  * zeroed words.  status_preloaded: ctx->d_status[0] marks the groups of a combiner batch that take no part (LF_DONE). */
 static int decode_cw_device_impl(lnsfaid_ctx* ctx, const int8_t* d_fixInput, size_t n_groups, int8_t* d_decodedBits,
-                                 lnsfaid_group_stats* d_stats, lnsfaid_codeword_stats* d_cw_stats, bool status_preloaded)
+                                 lnsfaid_group_stats* d_stats, lnsfaid_codeword_stats* d_cw_stats, bool status_preloaded, bool packed)
 {
     if (!ctx || (n_groups && (!d_fixInput || !d_decodedBits))) return LNSFAID_E_INVAL;
     if (n_groups > ctx->max_groups) return LNSFAID_E_INVAL;
@@ -653,7 +676,7 @@ static int decode_cw_device_impl(lnsfaid_ctx* ctx, const int8_t* d_fixInput, siz
     if (n_groups == 0) return LNSFAID_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     {
-        const int rc = kernel_check(ctx, LNSFAID_STOP_CODEWORD);
+        const int rc = kernel_check(ctx, LNSFAID_STOP_CODEWORD, packed);
         if (rc) return rc;
     }
     const size_t n_cw = n_groups * LNSFAID_GROUP;
@@ -666,7 +689,8 @@ static int decode_cw_device_impl(lnsfaid_ctx* ctx, const int8_t* d_fixInput, siz
     if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, n_groups * sizeof(lnsfaid_group_stats), ctx->stream));
     static const bool trace = getenv("LNSFAID_TRACE") != nullptr;
     HIP_TRY(hipEventRecord(ctx->ev_chain[0], ctx->stream));
-    HIP_TRY(lf_launch_decode4cw(ctx->hcfg.method, ctx->hcfg.ef, use_msg_registers(ctx) ? 1 : 0, &a, ctx->lds_bytes, ctx->stream));
+    if (packed) HIP_TRY(lf_launch_decode4pcw(ctx->hcfg.method, ctx->hcfg.ef, use_msg_registers(ctx) ? 1 : 0, &a, ctx->lds_bytes, ctx->stream));
+    else HIP_TRY(lf_launch_decode4cw(ctx->hcfg.method, ctx->hcfg.ef, use_msg_registers(ctx) ? 1 : 0, &a, ctx->lds_bytes, ctx->stream));
     HIP_TRY(hipEventRecord(ctx->ev_chain[1], ctx->stream));
     { const int rcw = stream_wait(ctx); if (rcw) return rcw; }
     float ms = 0.f;
@@ -678,14 +702,14 @@ static int decode_cw_device_impl(lnsfaid_ctx* ctx, const int8_t* d_fixInput, siz
 }
 
 static int decode_device_impl(lnsfaid_ctx* ctx, const int8_t* d_fixInput, size_t n_groups, int8_t* d_decodedBits,
-                              lnsfaid_group_stats* d_stats, bool status_preloaded)
+                              lnsfaid_group_stats* d_stats, bool status_preloaded, bool packed)
 {
     if (!ctx || (n_groups && (!d_fixInput || !d_decodedBits))) return LNSFAID_E_INVAL;
     if (n_groups > ctx->max_groups) return LNSFAID_E_INVAL;
     if (n_groups == 0) return LNSFAID_OK;
     HIP_TRY(hipSetDevice(ctx->device));
     {
-        const int rc = kernel_check(ctx, LNSFAID_STOP_GROUP);
+        const int rc = kernel_check(ctx, LNSFAID_STOP_GROUP, packed);
         if (rc) return rc;
     }
     const size_t n_cw = n_groups * LNSFAID_GROUP;
@@ -722,7 +746,8 @@ static int decode_device_impl(lnsfaid_ctx* ctx, const int8_t* d_fixInput, size_t
             a.status_next = ctx->d_status[cur ^ 1];
             a.remaining = ctx->d_remaining + j;
             HIP_TRY(hipEventRecord(ctx->ev_chain[j], ctx->stream));
-            if (use_kernel5(ctx)) HIP_TRY(lf_launch_decode5(ctx->hcfg.method, &a, ctx->lds_bytes, ctx->stream));
+            if (packed) HIP_TRY(lf_launch_decode4p(ctx->hcfg.method, ctx->hcfg.ef, use_msg_registers(ctx) ? 1 : 0, &a, ctx->lds_bytes, ctx->stream));
+            else if (use_kernel5(ctx)) HIP_TRY(lf_launch_decode5(ctx->hcfg.method, &a, ctx->lds_bytes, ctx->stream));
             else if (use_kernel4(ctx)) HIP_TRY(lf_launch_decode4(ctx->hcfg.method, ctx->hcfg.ef, use_msg_registers(ctx) ? 1 : 0, &a, ctx->lds_bytes, ctx->stream));
             else HIP_TRY(lf_launch_decode(ctx->hcfg.method, ctx->hcfg.uniform_w, &a, ctx->lds_bytes, ctx->stream));
             cur ^= 1;
@@ -1265,6 +1290,195 @@ extern "C" int lnsfaid_count_errors(lnsfaid_ctx* ctx, const int8_t* decodedBits,
         d_in = ctx->d_io_in;
     }
     return lnsfaid_count_errors_device(ctx, ctx->d_io_out, d_in, n_groups, out);
+}
+
+/* ---- packed decode I/O (include/lnsfaid.h "Packed decode I/O") ------------------------------------------ */
+static bool dword_aligned(const void* p) { return ((uintptr_t)p & 3u) == 0u; }
+
+static int ensure_packed_io(lnsfaid_ctx* ctx)
+{
+    if (ctx->d_pk_in) return LNSFAID_OK;
+    HIP_TRY(hipMalloc(&ctx->d_pk_in, ctx->max_groups * LNSFAID_GROUP * (size_t)ctx->n_var / 2));
+    HIP_TRY(hipMalloc(&ctx->d_pk_out, ctx->max_groups * LNSFAID_GROUP * (size_t)ctx->n_var / 8));
+    HIP_TRY(hipMalloc(&ctx->d_pk_stats, ctx->max_groups * sizeof(lnsfaid_group_stats)));
+    return LNSFAID_OK;
+}
+
+/* one batch of device buffers under the given rule: the packed twin of the four-rows kernel, or (group rule only) llr4 -> int8 in
+ * the context's io buffers, the int8 decode, int8 -> bits */
+static int decode_packed_rule(lnsfaid_ctx* ctx, const uint8_t* d_llr4, size_t n_groups, uint32_t* d_bits, lnsfaid_group_stats* d_stats,
+                              lnsfaid_codeword_stats* d_cw_stats, int rule)
+{
+    if (rule == LNSFAID_STOP_CODEWORD)
+        return decode_cw_device_impl(ctx, (const int8_t*)d_llr4, n_groups, (int8_t*)d_bits, d_stats, d_cw_stats, false, true);
+    if (packed_kernel(ctx)) return decode_device_impl(ctx, (const int8_t*)d_llr4, n_groups, (int8_t*)d_bits, d_stats, false, true);
+    int rc = ensure_io(ctx);
+    if (rc) return rc;
+    const size_t n_values = n_groups * LNSFAID_GROUP * (size_t)ctx->n_var;
+    HIP_TRY(lf_launch_unpack_llr4(d_llr4, ctx->d_io_in, n_values, ctx->stream));
+    rc = decode_device_impl(ctx, ctx->d_io_in, n_groups, ctx->d_io_out, d_stats, false);
+    if (rc) return rc;
+    HIP_TRY(lf_launch_pack_bits(ctx->d_io_out, d_bits, n_values, ctx->stream));
+    return stream_wait(ctx); /* returns with the output complete, as the decoders do */
+}
+
+static int decode_packed_device_impl(lnsfaid_ctx* ctx, const uint8_t* d_llr4, size_t n_groups, uint32_t* d_bits, lnsfaid_group_stats* d_stats,
+                                     lnsfaid_codeword_stats* d_cw_stats, int rule)
+{
+    if (!ctx || (n_groups && (!d_llr4 || !d_bits))) return LNSFAID_E_INVAL;
+    if (n_groups > ctx->max_groups) return LNSFAID_E_INVAL;
+    if (rule == LNSFAID_STOP_CODEWORD && !cw_possible(ctx)) return LNSFAID_E_INVAL;
+    if (n_groups == 0) return LNSFAID_OK;
+    if (!dword_aligned(d_llr4) || !dword_aligned(d_bits) || !dword_aligned(d_stats) || !dword_aligned(d_cw_stats)) return LNSFAID_E_INVAL;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return decode_packed_rule(ctx, d_llr4, n_groups, d_bits, d_stats, d_cw_stats, rule);
+}
+
+extern "C" int lnsfaid_decode_packed_device(lnsfaid_ctx* ctx, const uint8_t* d_llr4, size_t n_groups, uint32_t* d_bits,
+                                            lnsfaid_group_stats* d_stats)
+{
+    if (!ctx) return LNSFAID_E_INVAL;
+    return decode_packed_device_impl(ctx, d_llr4, n_groups, d_bits, d_stats, nullptr, ctx->early_stop);
+}
+
+extern "C" int lnsfaid_decode_codewords_packed_device(lnsfaid_ctx* ctx, const uint8_t* d_llr4, size_t n_groups, uint32_t* d_bits,
+                                                      lnsfaid_codeword_stats* d_cw_stats)
+{
+    return decode_packed_device_impl(ctx, d_llr4, n_groups, d_bits, nullptr, d_cw_stats, LNSFAID_STOP_CODEWORD);
+}
+
+/* host buffers through the packed staging: as decode_host_impl (pieces that overlap copy-in, decode and copy-out when both buffers
+ * are pinned, one copy each way otherwise), always on the context's own stream (no call combiner) */
+static int decode_packed_host_impl(lnsfaid_ctx* ctx, const uint8_t* llr4, size_t n_groups, uint32_t* bits, lnsfaid_group_stats* stats,
+                                   lnsfaid_codeword_stats* cw_stats, int rule)
+{
+    if (!ctx || (n_groups && (!llr4 || !bits))) return LNSFAID_E_INVAL;
+    if (n_groups > ctx->max_groups) return LNSFAID_E_INVAL;
+    if (rule == LNSFAID_STOP_CODEWORD && !cw_possible(ctx)) return LNSFAID_E_INVAL;
+    if (n_groups == 0) return LNSFAID_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    int rc = ensure_packed_io(ctx);
+    if (rc) return rc;
+    if (cw_stats && !ctx->d_io_cw_stats)
+        HIP_TRY(hipMalloc(&ctx->d_io_cw_stats, ctx->max_groups * LNSFAID_GROUP * sizeof(lnsfaid_codeword_stats)));
+    lnsfaid_codeword_stats* d_cw = cw_stats ? ctx->d_io_cw_stats : nullptr;
+    const size_t in_bytes = LNSFAID_GROUP * (size_t)ctx->n_var / 2, out_words = LNSFAID_GROUP * (size_t)ctx->n_var / 32;
+    size_t chunk = ((n_groups + LF_IO_CHUNKS - 1) / LF_IO_CHUNKS + 63) / 64 * 64;
+    if (chunk >= n_groups || !host_pinned(llr4) || !host_pinned(bits)) {
+        HIP_TRY(hipMemcpyAsync(ctx->d_pk_in, llr4, n_groups * in_bytes, hipMemcpyHostToDevice, ctx->stream));
+        rc = decode_packed_rule(ctx, ctx->d_pk_in, n_groups, ctx->d_pk_out, ctx->d_pk_stats, d_cw, rule);
+        if (rc) return rc;
+        HIP_TRY(hipMemcpyAsync(bits, ctx->d_pk_out, n_groups * out_words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    } else {
+        if (!ctx->s_in) {
+            HIP_TRY(hipStreamCreateWithFlags(&ctx->s_in, hipStreamNonBlocking));
+            HIP_TRY(hipStreamCreateWithFlags(&ctx->s_out, hipStreamNonBlocking));
+            for (auto& e : ctx->ev_in) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        }
+        const size_t n_chunks = (n_groups + chunk - 1) / chunk; /* <= LF_IO_CHUNKS */
+        for (size_t c = 0; c < n_chunks; ++c) {
+            const size_t g0 = c * chunk, ng = g0 + chunk <= n_groups ? chunk : n_groups - g0;
+            HIP_TRY(hipMemcpyAsync(ctx->d_pk_in + g0 * in_bytes, llr4 + g0 * in_bytes, ng * in_bytes, hipMemcpyHostToDevice, ctx->s_in));
+            HIP_TRY(hipEventRecord(ctx->ev_in[c], ctx->s_in));
+        }
+        for (size_t c = 0; c < n_chunks; ++c) {
+            const size_t g0 = c * chunk, ng = g0 + chunk <= n_groups ? chunk : n_groups - g0;
+            HIP_TRY(hipStreamWaitEvent(ctx->stream, ctx->ev_in[c], 0));
+            rc = decode_packed_rule(ctx, ctx->d_pk_in + g0 * in_bytes, ng, ctx->d_pk_out + g0 * out_words, ctx->d_pk_stats + g0,
+                                    d_cw ? d_cw + g0 * LNSFAID_GROUP : nullptr, rule);
+            if (rc) { (void)hipStreamSynchronize(ctx->s_in); (void)hipStreamSynchronize(ctx->s_out); return rc; }
+            HIP_TRY(hipMemcpyAsync(bits + g0 * out_words, ctx->d_pk_out + g0 * out_words, ng * out_words * sizeof(uint32_t),
+                                   hipMemcpyDeviceToHost, ctx->s_out));
+        }
+        HIP_TRY(hipStreamSynchronize(ctx->s_out));
+    }
+    if (stats)
+        HIP_TRY(hipMemcpyAsync(stats, ctx->d_pk_stats, n_groups * sizeof(lnsfaid_group_stats), hipMemcpyDeviceToHost, ctx->stream));
+    if (cw_stats)
+        HIP_TRY(hipMemcpyAsync(cw_stats, d_cw, n_groups * LNSFAID_GROUP * sizeof(lnsfaid_codeword_stats), hipMemcpyDeviceToHost,
+                               ctx->stream));
+    { const int rcw = stream_wait(ctx); if (rcw) return rcw; }
+    return LNSFAID_OK;
+}
+
+extern "C" int lnsfaid_decode_packed(lnsfaid_ctx* ctx, const uint8_t* llr4, size_t n_groups, uint32_t* bits, lnsfaid_group_stats* stats)
+{
+    if (!ctx) return LNSFAID_E_INVAL;
+    return decode_packed_host_impl(ctx, llr4, n_groups, bits, stats, nullptr, ctx->early_stop);
+}
+
+extern "C" int lnsfaid_decode_codewords_packed(lnsfaid_ctx* ctx, const uint8_t* llr4, size_t n_groups, uint32_t* bits,
+                                               lnsfaid_codeword_stats* cw_stats)
+{
+    return decode_packed_host_impl(ctx, llr4, n_groups, bits, nullptr, cw_stats, LNSFAID_STOP_CODEWORD);
+}
+
+extern "C" int lnsfaid_count_errors_packed_device(lnsfaid_ctx* ctx, const uint32_t* d_bits, const uint8_t* d_msg, size_t n_groups,
+                                                  uint64_t out[4])
+{
+    if (!ctx || !out || (n_groups && !d_bits)) return LNSFAID_E_INVAL;
+    if (n_groups == 0) return LNSFAID_OK;
+    if (!dword_aligned(d_bits) || !dword_aligned(d_msg)) return LNSFAID_E_INVAL;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, 4 * sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(lf_launch_count_errors_packed(d_bits, (const uint32_t*)d_msg, ctx->n_var, ctx->k_info, n_groups * LNSFAID_GROUP,
+                                          ctx->d_counters, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->h_counters, ctx->d_counters, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    { const int rcw = stream_wait(ctx); if (rcw) return rcw; }
+    for (int i = 0; i < 4; ++i) out[i] += ctx->h_counters[i];
+    return LNSFAID_OK;
+}
+
+extern "C" int lnsfaid_count_errors_packed(lnsfaid_ctx* ctx, const uint32_t* bits, const uint8_t* msg, size_t n_groups, uint64_t out[4])
+{
+    if (!ctx || !out || (n_groups && !bits)) return LNSFAID_E_INVAL;
+    if (n_groups > ctx->max_groups) return LNSFAID_E_INVAL;
+    if (n_groups == 0) return LNSFAID_OK;
+    HIP_TRY(hipSetDevice(ctx->device));
+    const int rc = ensure_packed_io(ctx);
+    if (rc) return rc;
+    const size_t n_cw = n_groups * LNSFAID_GROUP;
+    HIP_TRY(hipMemcpyAsync(ctx->d_pk_out, bits, n_cw * (size_t)ctx->n_var / 8, hipMemcpyHostToDevice, ctx->stream));
+    const uint8_t* d_msg = nullptr;
+    if (msg) { /* K / 8 bytes per codeword fit in the (larger) llr4 staging buffer */
+        HIP_TRY(hipMemcpyAsync(ctx->d_pk_in, msg, n_cw * (size_t)ctx->k_info / 8, hipMemcpyHostToDevice, ctx->stream));
+        d_msg = ctx->d_pk_in;
+    }
+    return lnsfaid_count_errors_packed_device(ctx, ctx->d_pk_out, d_msg, n_groups, out);
+}
+
+/* host-only format helpers (no context, no GPU) */
+extern "C" int lnsfaid_pack_llr4(const int8_t* fixInput, size_t n_values, uint8_t* llr4)
+{
+    if (n_values % 2 || (n_values && (!fixInput || !llr4))) return LNSFAID_E_INVAL;
+    for (size_t i = 0; i < n_values; i += 2) {
+        const int a = fixInput[i], b = fixInput[i + 1];
+        if (a < -8 || a > 7 || b < -8 || b > 7) return LNSFAID_E_INVAL;
+        llr4[i / 2] = (uint8_t)((a & 15) | ((b & 15) << 4));
+    }
+    return LNSFAID_OK;
+}
+
+extern "C" int lnsfaid_unpack_bits(const uint32_t* bits, size_t n_bits, int8_t* decodedBits)
+{
+    if (n_bits % 32 || (n_bits && (!bits || !decodedBits))) return LNSFAID_E_INVAL;
+    for (size_t i = 0; i < n_bits; ++i) decodedBits[i] = (int8_t)((bits[i / 32] >> (i % 32)) & 1u);
+    return LNSFAID_OK;
+}
+
+extern "C" int lnsfaid_pack_bits(const int8_t* inputBits, size_t n_bits, uint8_t* packed)
+{
+    if (n_bits % 8 || (n_bits && (!inputBits || !packed))) return LNSFAID_E_INVAL;
+    for (size_t i = 0; i < n_bits; i += 8) {
+        uint8_t v = 0;
+        for (int b = 0; b < 8; ++b) {
+            const int x = inputBits[i + (size_t)b];
+            if (x != 0 && x != 1) return LNSFAID_E_INVAL;
+            v |= (uint8_t)(x << b);
+        }
+        packed[i / 8] = v;
+    }
+    return LNSFAID_OK;
 }
 
 /* ---- front-end on the device ------------------------------------------------------------------------ */

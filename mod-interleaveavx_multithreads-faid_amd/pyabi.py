@@ -77,6 +77,15 @@ SYMBOLS = {
     "lnsfaid_decode_codewords_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "lnsfaid_count_errors": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
     "lnsfaid_count_errors_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "lnsfaid_decode_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "lnsfaid_decode_packed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "lnsfaid_decode_codewords_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "lnsfaid_decode_codewords_packed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "lnsfaid_count_errors_packed": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "lnsfaid_count_errors_packed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64)]),
+    "lnsfaid_pack_llr4": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lnsfaid_unpack_bits": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lnsfaid_pack_bits": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "lnsfaid_frontend_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_size_t, C.c_int32,
                                           C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "lnsfaid_frontend_device_states": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_size_t, C.c_int32,
@@ -173,6 +182,42 @@ def default_cfg(method, max_iter, lib=None):
     return cfg
 
 
+def pack_llr4(fix_input, lib=None):
+    """lnsfaid_pack_llr4: int8 fixInput (values in [-8, 7]) -> uint8 llr4, two elements per byte"""
+    import numpy as np
+    lib = lib or load()
+    fix_input = np.ascontiguousarray(fix_input, dtype=np.int8)
+    out = np.empty(fix_input.size // 2, dtype=np.uint8)
+    rc = lib.lnsfaid_pack_llr4(fix_input.ctypes.data, fix_input.size, out.ctypes.data)
+    if rc != 0:
+        raise ValueError("lnsfaid_pack_llr4 failed: %d" % rc)
+    return out
+
+
+def unpack_bits(bits, lib=None):
+    """lnsfaid_unpack_bits: packed decisions (uint32 words) -> int8 0/1, one byte per bit"""
+    import numpy as np
+    lib = lib or load()
+    bits = np.ascontiguousarray(bits, dtype=np.uint32)
+    out = np.empty(bits.size * 32, dtype=np.int8)
+    rc = lib.lnsfaid_unpack_bits(bits.ctypes.data, out.size, out.ctypes.data)
+    if rc != 0:
+        raise ValueError("lnsfaid_unpack_bits failed: %d" % rc)
+    return out
+
+
+def pack_bits(input_bits, lib=None):
+    """lnsfaid_pack_bits: int8 0/1 message bits -> uint8, eight per byte, bit b of byte i = input_bits[8 i + b]"""
+    import numpy as np
+    lib = lib or load()
+    input_bits = np.ascontiguousarray(input_bits, dtype=np.int8)
+    out = np.empty(input_bits.size // 8, dtype=np.uint8)
+    rc = lib.lnsfaid_pack_bits(input_bits.ctypes.data, input_bits.size, out.ctypes.data)
+    if rc != 0:
+        raise ValueError("lnsfaid_pack_bits failed: %d" % rc)
+    return out
+
+
 class Decoder:
     """Thin RAII wrapper over lnsfaid_create / lnsfaid_decode* / lnsfaid_destroy."""
 
@@ -241,6 +286,49 @@ class Decoder:
         out = (C.c_uint64 * 4)()
         self._check(self.lib.lnsfaid_count_errors_device(self.ctx, d_decoded_ptr, d_input_ptr, n_groups, out),
                     "lnsfaid_count_errors_device")
+        return list(out)
+
+    def decode_packed(self, llr4, n_groups):
+        """lnsfaid_decode_packed: llr4 uint8 array (pack_llr4).  Returns (packed decisions uint32 array, stats array)."""
+        import numpy as np
+        N = self.code50.N
+        assert llr4.dtype == np.uint8 and llr4.size == n_groups * GROUP * N // 2 and llr4.flags.c_contiguous
+        out = np.empty(n_groups * GROUP * N // 32, dtype=np.uint32)
+        stats = np.zeros((n_groups, 2), dtype=np.int32)
+        self._check(self.lib.lnsfaid_decode_packed(self.ctx, llr4.ctypes.data, n_groups, out.ctypes.data, stats.ctypes.data),
+                    "lnsfaid_decode_packed")
+        return out, stats
+
+    def decode_codewords_packed(self, llr4, n_groups, with_stats=True):
+        """lnsfaid_decode_codewords_packed: (packed decisions uint32 array, [n_groups * 32, 3] int32 array or None)"""
+        import numpy as np
+        N = self.code50.N
+        assert llr4.dtype == np.uint8 and llr4.size == n_groups * GROUP * N // 2 and llr4.flags.c_contiguous
+        out = np.empty(n_groups * GROUP * N // 32, dtype=np.uint32)
+        cw = np.zeros((n_groups * GROUP, 3), dtype=np.int32) if with_stats else None
+        self._check(self.lib.lnsfaid_decode_codewords_packed(self.ctx, llr4.ctypes.data, n_groups, out.ctypes.data,
+                                                             cw.ctypes.data if with_stats else None), "lnsfaid_decode_codewords_packed")
+        return out, cw
+
+    def decode_packed_device(self, d_llr4_ptr, n_groups, d_bits_ptr, d_stats_ptr=None):
+        self._check(self.lib.lnsfaid_decode_packed_device(self.ctx, d_llr4_ptr, n_groups, d_bits_ptr, d_stats_ptr),
+                    "lnsfaid_decode_packed_device")
+
+    def decode_codewords_packed_device(self, d_llr4_ptr, n_groups, d_bits_ptr, d_cw_stats_ptr=None):
+        self._check(self.lib.lnsfaid_decode_codewords_packed_device(self.ctx, d_llr4_ptr, n_groups, d_bits_ptr, d_cw_stats_ptr),
+                    "lnsfaid_decode_codewords_packed_device")
+
+    def count_errors_packed(self, bits, msg, n_groups):
+        """lnsfaid_count_errors_packed: bits uint32 (decode_packed), msg uint8 (pack_bits) or None for the all-zero codeword"""
+        out = (C.c_uint64 * 4)()
+        mp = msg.ctypes.data if msg is not None else None
+        self._check(self.lib.lnsfaid_count_errors_packed(self.ctx, bits.ctypes.data, mp, n_groups, out), "lnsfaid_count_errors_packed")
+        return list(out)
+
+    def count_errors_packed_device(self, d_bits_ptr, d_msg_ptr, n_groups):
+        out = (C.c_uint64 * 4)()
+        self._check(self.lib.lnsfaid_count_errors_packed_device(self.ctx, d_bits_ptr, d_msg_ptr, n_groups, out),
+                    "lnsfaid_count_errors_packed_device")
         return list(out)
 
     def encode(self, info, n_groups):
