@@ -302,7 +302,11 @@ __device__ __forceinline__ void main_step4(CCode c, CCfg f, const LfDevCode* gc,
             else if (deg == 23) st = sw_layer_step<METHOD, 23>(lds, tab, p, K, (uint32_t)lane, deg, cur, fresh, rowpar, lme);
             else if (deg == 22) st = sw_layer_step<METHOD, 22>(lds, tab, p, K, (uint32_t)lane, deg, cur, fresh, rowpar, lme);
             else st = sw_layer_step<METHOD, 0>(lds, tab, p, K, (uint32_t)lane, deg, cur, fresh, rowpar, lme);
+            /* the six indexed writes back to back, nothing scheduled between them: ONE s_set_gpr_idx_on / _off pair around all of
+             * them instead of one per write */
+            __builtin_amdgcn_sched_barrier(0);
             regs_put(R, br, st);
+            __builtin_amdgcn_sched_barrier(0);
             tabv = tabn;
         }
         return;

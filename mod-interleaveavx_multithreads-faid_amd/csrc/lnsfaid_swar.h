@@ -193,6 +193,53 @@ SW_FN uint32_t sw_therm2num(uint32_t x, uint32_t n_lo, uint32_t n_hi)
 /* 0xff in every byte that is zero; bytes must be <= 0x7f */
 SW_FN uint32_t sw_zero_mask(uint32_t x, uint32_t sel_sign) { return ~sw_mask7(x + 0x7f7f7f7fu, sel_sign); }
 
+/* four bytes read one by one (each value < 256) into one word, byte k = g_k, as two pairs and their merge: three v_lshl_or_b32 where
+ * the compiler finds them (written through an asm statement they were forced - and one of the packed kernels then reserved a stack
+ * slot it never touches) */
+SW_FN uint32_t sw_gather4(uint32_t g0, uint32_t g1, uint32_t g2, uint32_t g3)
+{
+    const uint32_t lo = (g1 << 8) | g0, hi = (g3 << 8) | g2;
+    return (hi << 16) | lo;
+}
+/* a value the compiler may not look through: keeps `x >> 16` of it a read of bits 23:16 (ds_write_b8_d16_hi) */
+SW_FN uint32_t sw_opaque(uint32_t x)
+{
+#if SW_DEV
+    asm("" : "+v"(x));
+#endif
+    return x;
+}
+/* LDS byte address of the variable node that row k of a lane meets through a circulant, from
+ * x = 4 (lane + shift) + (k << 8) in the low half (below 0x10000, a multiple of 4) and the block column << 24:
+ * byte 0 of x is the dword of the node, byte 3 its block column, bits 9:8 the byte inside the dword ((lane + shift) div 64 + k) mod 4.
+ * One v_perm_b32 places the two bytes (tests/layer_trip_helpers_exhaustive.cpp holds the mask / shift / merge form it replaced). */
+SW_FN uint32_t sw_node_addr(uint32_t x) { return sw_perm(x, x, 0x0c0c0300u) | ((x >> 8) & 3u); }
+
+/* ---- small per-row statements of the layer step, as functions so that the tests run the very statements the kernel runs ---- */
+/* A row's magnitude from one of two 8-entry tables, per byte: table W where the row's mask is set, table T elsewhere */
+SW_FN uint32_t sw_table_pick(uint32_t rowmask, uint32_t w_hi, uint32_t w_lo, uint32_t t_hi, uint32_t t_lo, uint32_t m)
+{
+    return sw_bitop3<SW_TT_SEL>(rowmask, sw_perm(w_hi, w_lo, m), sw_perm(t_hi, t_lo, m));
+}
+/* One of the three sign words per byte by the arg-min index's bits 4 and 3, given as byte masks that are set where the bit is CLEAR
+ * (nm4, nm3; bit 4 is looked at first, so nm3 need not know that bit 3 gives way to it) */
+SW_FN uint32_t sw_word_pick(uint32_t nm3, uint32_t nm4, uint32_t x0, uint32_t x1, uint32_t x2)
+{
+    return sw_bitop3<SW_TT_SEL>(nm4, sw_bitop3<SW_TT_SEL>(nm3, x0, x1), x2);
+}
+/* `keep` dealt to the three words the same way: oh[g] = keep where the index is in word g */
+SW_FN void sw_word_deal(uint32_t keep, uint32_t nm3, uint32_t nm4, uint32_t oh[3])
+{
+    oh[0] = sw_bitop3<SW_TT_AND3>(keep, nm3, nm4);
+    oh[1] = sw_bitop3<0x20>(keep, nm3, nm4); /* a & ~b & c */
+    oh[2] = keep & ~nm4;
+}
+/* v_perm selector 2 k + b of the arg-min edge: b = 1 in byte k where the picked sign word has the edge's one-hot bit set */
+SW_FN uint32_t sw_argmin_selector(uint32_t w, uint32_t oh8, uint32_t c7f, uint32_t c01, uint32_t c0642)
+{
+    return sw_bitop3<SW_TT_ANDOR>(((w & oh8) + c7f) >> 7, c01, c0642);
+}
+
 /* ---- compressed messages of the four rows of one lane in one layer (24 bytes, streamed through HBM) ---------------
  * x[g] bit 8 k + e : the message on edge 8 g + e of row k is negative (0 for a zero message, FAID / 2B1C)
  * cw byte k        : c2 | c1 << 3 | (message on the arg-min edge negative) << 6
@@ -530,9 +577,9 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
         /* En - L(c1) = (En - sigma (c1 - c2)) - sigma c2 */
         padd = sw_bitop3<SW_TT_SEL>(mneg, c1o, c2o); psub = sw_bitop3<SW_TT_SEL>(mneg, c2o, c1o);
         SW_SCHED_FENCE();
-        const uint32_t g = g0 | (g1 << 8) | (g2 << 16) | (g3 << 24);
-        const uint32_t r = g + padd - psub;
-        lds.wr8(a0, r); lds.wr8(a1, r >> 8); lds.wr8(a2, r >> 16); lds.wr8(a3, r >> 24);
+        const uint32_t r = sw_gather4(g0, g1, g2, g3) + padd - psub;
+        const uint32_t rh = sw_opaque(r >> 8); /* one shift serves both odd bytes */
+        lds.wr8(a0, r); lds.wr8(a1, rh); lds.wr8(a2, r >> 16); lds.wr8(a3, rh >> 16);
     }
 #endif
     if (WAVES == 2) xch.barrier(); /* A */
@@ -660,21 +707,29 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
     } else if (SW_OMS(METHOD)) {
         /* selective offset and clamp (cste_2 from min1, cste_1 from min2, CDecoder_OMS.cpp:431-432) as table look-ups; rows
          * with an unsatisfied check take the other rule inside the error-floor window of a codeword with few of them (:388) */
-        c2n = sw_perm(p.oms_hi[0], p.oms_lo[0], min1);
-        c1n = sw_perm(p.oms_hi[0], p.oms_lo[0], min2);
-        if (p.window && lme) {
-            c2n = sw_bitop3<SW_TT_SEL>(rowpar, sw_perm(p.oms_hi[1], p.oms_lo[1], min1), c2n);
-            c1n = sw_bitop3<SW_TT_SEL>(rowpar, sw_perm(p.oms_hi[1], p.oms_lo[1], min2), c1n);
-        }
+        /* (the choice of the second table is uniform and the same for every layer of an iteration: made on the table WORDS - two
+         * scalar selects, loop-invariant, which the compiler is relied on to hoist out of the layer loop; tests/test_layer_trip_count.py
+         * would show them - instead of on the rows' results.  Outside the window both look-ups read the same table) */
+        const bool win = p.window && lme;
+        const uint32_t w_lo = win ? p.oms_lo[1] : p.oms_lo[0], w_hi = win ? p.oms_hi[1] : p.oms_hi[0];
+        c2n = sw_table_pick(rowpar, w_hi, w_lo, p.oms_hi[0], p.oms_lo[0], min1);
+        c1n = sw_table_pick(rowpar, w_hi, w_lo, p.oms_hi[0], p.oms_lo[0], min2);
     } else {
         /* uniform non-decreasing table applied after the search; offset 0 (CDecoder_FAID.cpp:864-866) */
-        c2n = sw_perm(p.lut_hi, p.lut_lo, min1);
-        c1n = sw_perm(p.lut_hi, p.lut_lo, min2);
-        if ((METHOD == 5 || p.ef_tables) && p.window && lme) { /* mask_eef per row (CDecoder_FAID.cpp:713-720) */
-            c2n = sw_bitop3<SW_TT_SEL>(rowpar, sw_perm(p.ef_hi, p.ef_lo, min1), c2n);
-            c1n = sw_bitop3<SW_TT_SEL>(rowpar, sw_perm(p.ef_hi, p.ef_lo, min2), c1n);
-        }
+        /* mask_eef per row (CDecoder_FAID.cpp:713-720).  Whether the error-floor table applies at all is uniform and the same for
+         * every layer of an iteration: the choice is made on the table WORDS (two scalar selects, loop-invariant: the compiler is
+         * relied on to hoist them out of the layer loop, tests/test_layer_trip_count.py would show them), instead of on the rows'
+         * results (outside the window both look-ups read the same table) */
+        const bool win = (METHOD == 5 || p.ef_tables) && p.window && lme;
+        const uint32_t w_lo = win ? p.ef_lo : p.lut_lo, w_hi = win ? p.ef_hi : p.lut_hi;
+        c2n = sw_table_pick(rowpar, w_hi, w_lo, p.lut_hi, p.lut_lo, min1);
+        c1n = sw_table_pick(rowpar, w_hi, w_lo, p.lut_hi, p.lut_lo, min2);
     }
+#if SW_DEV
+    /* The magnitudes are complete HERE.  Nothing but the arg-min edge, far below, reads c1n: without a fixed point the instruction
+     * selector's list scheduler puts the whole second-minimum chain of pass 1 there and keeps every edge's code alive until then. */
+    asm volatile("" : "+v"(c1n), "+v"(c2n));
+#endif
     /* new message on edge j is negative iff s_j ^ XOR_all(s) ^ (deg odd) (the 0xC0 / 0x40 constants of
      * CDecoder_FAID.cpp:902-917); with nn_j = bit 7 of ts_j = "V2C not negative" that is: not negative iff nn_j ^ F,
      * F = bit 7 of the XOR of all ts */
@@ -686,11 +741,14 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
      * edges 8..15, ta[4] over edges 16..23, the bit is 1 iff one of them attains it; bit 3 gives way to bit 4.  With a unique
      * minimum that is its index; a tie leaves 16 / 8 / 0 + the AND of the tied indices' low bits, not above one of the tied
      * edges in that range, so still an edge of the row - and in a tie c1 == c2 ---- */
-    uint32_t idx = 0;
+    uint32_t idx = 0, ne7_3 = 0, ne7_4 = 0; /* the decode words of bits 3 and 4, kept for their byte masks below */
 #pragma unroll
     for (int b = 4; b >= 0; --b) {
         const uint32_t dd = sw_bitop3<SW_TT_XORAND>(ta[b], t1, c7f);
-        const uint32_t ne = (dd + c7f) >> (7 - b); /* bit b of every byte: ta[b] != t1 */
+        const uint32_t ne7 = dd + c7f;      /* bit 7 of every byte: ta[b] != t1 */
+        const uint32_t ne = ne7 >> (7 - b); /* the same at bit b */
+        if (b == 4) ne7_4 = ne7;
+        if (b == 3) ne7_3 = ne7;
         /* (a row of the generic instance with no edge in 16..23 / 8..15 leaves that accumulator untouched: bit stays 0) */
         if (b == 4) idx = (DEG == 0 && deg <= 16) ? 0u : ~ne & (0x01010101u << 4);
         else if (b == 3) idx = (DEG == 0 && deg <= 8) ? idx : sw_bitop3<0xf2>(idx, ne | (idx >> 1), 0x01010101u << 3); /* a | (~b & c) */
@@ -702,7 +760,7 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
      * (two waves per SIMD).  Pass 2 does not depend on them, so its first group of edges is computed between the issue of
      * the table look-up and its use, and the rest of it between the issue of the En reads and theirs.  LDS operations of a
      * wave execute in order: the En reads are ISSUED before the first write of pass 2, so they return the old values. ---- */
-    uint32_t pa[4], sbk[4], gb = 0, xb = 0;
+    uint32_t pa[4], sbk[4], gk0 = 0, gk1 = 0, gk2 = 0, gk3 = 0, xb = 0;
     const uint32_t idx4 = idx << 2;
 #pragma unroll
 #ifdef SW_EXP_NO_ARGMIN /* timing experiment only: results are wrong */
@@ -744,20 +802,13 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
     SW_PASS2_ARITH(0, en0)
     SW_SCHED_FENCE();
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint32_t x = tid4 + sbk[k]; /* low half: 4 * (lane + shift) < 2048, high half: block column * 256 */
-        const uint32_t a = (x & 0xfcu) | (x >> 16);
-        const uint32_t q = (x >> 8) & 3u;
-        pa[k] = k ? a | ((q + (uint32_t)k) & 3u) : a | q;
-    }
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
+    for (int k = 0; k < 4; ++k) /* low half: 4 * (lane + shift) < 2048, with the row folded in < 2816; high half: block column * 256 */
+        pa[k] = sw_node_addr(tid4 + sbk[k] + ((uint32_t)k << 8));
 #ifdef SW_EXP_NO_ARGMIN
-        gb |= (ld[k] & 0xffu) << (8 * k);
+    gk0 = ld[0] & 0xffu; gk1 = ld[1] & 0xffu; gk2 = ld[2] & 0xffu; gk3 = ld[3] & 0xffu;
 #else
-        if (WAVE == 0) gb |= lds.rd8(pa[k]) << (8 * k);
+    if (WAVE == 0) { gk0 = lds.rd8(pa[0]); gk1 = lds.rd8(pa[1]); gk2 = lds.rd8(pa[2]); gk3 = lds.rd8(pa[3]); }
 #endif
-    }
     if (WAVES == 2 && WAVE == 0) { /* the barrier also waits for the reads above: wave 1 may overwrite those nodes from here on */
         xch.put(0, c2n); xch.put(1, fm);
         xch.barrier(); /* C */
@@ -769,12 +820,14 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
     /* the arg-min edges as one-hot bits inside their 8-edge word (byte k: 1 << (index mod 8)) and the word they are in
      * (index div 8 = 0, 1, 2) as byte masks, all four rows at once */
     const uint32_t oh8 = sw_perm(K.oh_hi, K.oh_lo, idx & 0x07070707u);
-    const uint32_t in1 = sw_mask7(idx << 4, sel_sign), in2 = sw_mask7(idx << 3, sel_sign); /* index bit 3 / bit 4 */
-    {   /* old message on that edge negative: bit (index mod 8) of byte k of sign word (index div 8) */
-        const uint32_t w = sw_bitop3<SW_TT_SEL>(in2, cur.x[2], sw_bitop3<SW_TT_SEL>(in1, cur.x[1], cur.x[0]));
-        xb = (((w & oh8) + c7f) & c80) >> 7;
-    }
-    const uint32_t selA = xb | c0642;
+    /* index bit 4 / bit 3 as byte masks, from the words the index was decoded from (their bit 7: the accumulator differs from the
+     * minimum, i.e. the bit is CLEAR): no shifts.  nm3 ignores that bit 3 gives way to bit 4: every use below looks at nm4 first */
+    const uint32_t nm4 = (DEG == 0 && deg <= 16) ? 0xffffffffu : sw_mask7(ne7_4, sel_sign);
+    const uint32_t nm3 = (DEG == 0 && deg <= 8) ? 0xffffffffu : sw_mask7(ne7_3, sel_sign);
+    /* old message on that edge negative: bit (index mod 8) of byte k of sign word (index div 8), as 2 k + b: the v_perm selector */
+    const uint32_t selA = sw_argmin_selector(sw_word_pick(nm3, nm4, cur.x[0], cur.x[1], cur.x[2]), oh8, c7f, c01, c0642);
+    if (ERA) xb = selA & c01;
+    const uint32_t gb = sw_gather4(gk0, gk1, gk2, gk3);
     uint32_t tbA = gb + sw_perm(kt_hi, kt_lo, selA); /* carries `bias` like tb[] */
     if (ERA) { /* the arg-min edge of a row may be an erased one (a V2C of 0 usually IS the minimum) */
         uint32_t em = 0, match = 0;
@@ -789,7 +842,7 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
         tbA = sw_bitop3<SW_TT_SEL>(em, c80 + bias, tbA);
         xb = sw_bitop3<SW_TT_SEL>(em, ~((en_true + 0x08080808u) >> 7) & c01, xb);
     }
-    const uint32_t tsA = MINSUM ? tbA : tbA - (xb | c0642);
+    const uint32_t tsA = MINSUM ? tbA : tbA - (ERA ? (xb | c0642) : selA);
     const uint32_t msA = sw_mask7(tsA, sel_sign);
     const uint32_t negA = ~(msA ^ fm); /* byte mask: the new message on the arg-min edge is negative */
     const SwUpd2 u1 = sw_update2_consts<MINSUM>(c1n, fm, bias);
@@ -813,8 +866,10 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
     /* the arg-min edge carries c1: its exact En replaces the as-if value pass 2 wrote (same lane, LDS operations in order; with two
      * waves: after barrier D, behind the other wave's as-if value) */
 #ifndef SW_EXP_NO_ARGMIN
-#pragma unroll
-    for (int k = 0; k < 4; ++k) lds.wr8(pa[k], enA >> (8 * k));
+    {
+        const uint32_t eh = sw_opaque(enA >> 8); /* one shift serves both odd bytes */
+        lds.wr8(pa[0], enA); lds.wr8(pa[1], eh); lds.wr8(pa[2], enA >> 16); lds.wr8(pa[3], eh >> 16);
+    }
 #endif
 
     /* ---- the row's new compressed messages ---- */
@@ -831,7 +886,8 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
          * "Lmn < 0" straight from the bit.  c2 == 0 zeroes every message of the row but the arg-min's. */
         const uint32_t z2 = sw_zero_mask(c2n, sel_sign), nz1 = ~sw_zero_mask(c1n, sel_sign);
         const uint32_t keep = oh8 & nz1; /* the arg-min edge's bit survives where its message c1 is not zero */
-        const uint32_t oh[3] = { keep & ~(in1 | in2), keep & in1, keep & in2 };
+        uint32_t oh[3];
+        sw_word_deal(keep, nm3, nm4, oh);
 #pragma unroll
         for (int g = 0; g < 3; ++g) out.x[g] &= ~z2 | oh[g];
     }
