@@ -294,7 +294,7 @@ int lnsfaid_frontend_fastpath_bounds(lnsfaid_ctx* ctx, double measured[2], doubl
 
 /* Profile.txt InterleaveModType for lnsfaid_frontend_device: the block interleaver of BeforeModulationInterleaver /
  * AfterDeModulationDeInterleaver (CModulate.cpp:95-212) inside every frame; 1 (the default and the shipped value) is the
- * identity.  Must divide n_var. */
+ * identity.  Must divide n_var.  The value also applies to lnsfaid_demap_device / lnsfaid_demap_packed_device. */
 int lnsfaid_frontend_set_interleave(lnsfaid_ctx* ctx, int32_t interleave_mod_type);
 
 /* Frames for lnsfaid_frontend_device when every stream sends its own 32 frames (the reference with a real encoder:
@@ -306,6 +306,47 @@ int lnsfaid_frontend_set_interleave(lnsfaid_ctx* ctx, int32_t interleave_mod_typ
  * inputBits for lnsfaid_count_errors_device (NULL while no frames are set). */
 int lnsfaid_frontend_set_frames(lnsfaid_ctx* ctx, const int8_t* outputBits, const int8_t* inputBits, size_t n_streams);
 int lnsfaid_frontend_input_bits(lnsfaid_ctx* ctx, const int8_t** d_inputBits);
+
+/* ---- demapper for received symbols --------------------------------------------------------------------
+ * Replaces, for n_groups groups of caller-supplied symbols, CModulate::Demodulation (CModulate.cpp:270-362),
+ * AfterDeModulationDeInterleaver (:156-212) and CLDPC::float2LimitChar_4bit (CLDPC.cpp:4553-4573): the receive chain of
+ * CSimulate.cpp:127-129 behind a channel of the caller's own (a capture, a channel model on the same GPU).
+ *   rx    mod_type 2 / 4 / 6 / 8: the reference's MKL_Complex8 SymbolSeq of each group.  A symbol is a pair (re, im) of floats, a
+ *         group has 32 * n_var / mod_type symbols, symbol s of group g starts at float index 2 * (g * 32 * n_var / mod_type + s)
+ *         and carries stream positions mod_type * s .. mod_type * s + mod_type - 1.
+ *         mod_type 1 (the reference's BPSK branch, CSimulate.cpp:121-124): one real float per code bit, frame-major - frame m,
+ *         bit k of group g at g * 32 * n_var + m * n_var + k; the interleaver is not applied (as in that branch).  Positive
+ *         means bit 1, as for every other order.  This is also the way in for LLRs computed elsewhere.
+ *   levels   l0 = re, l1 = im; for n = 1 .. mod_type / 2 - 1:  l[2n]   = (float)(fabs((double)l[2n-2]) - c[n-1]),
+ *                                                              l[2n+1] = (float)(fabs((double)l[2n-1]) - c[n-1]),
+ *         c = {0.6324555} (16-QAM), {0.6172134, 0.3086067} (64-QAM), {0.613568, 0.306784, 0.153392} (256-QAM); every level
+ *         is stored as float before it feeds the next.  Level u of symbol s is the LLR of stream position mod_type * s + u.
+ *   de-interleaver   stream position pos belongs to frame m = pos / n_var, in-frame position p = pos % n_var, and carries code
+ *         bit k = (n_var / I) * (p % I) + p / I, I = InterleaveModType (the device calls use the context's value,
+ *         lnsfaid_frontend_set_interleave; the host calls take it as an argument).
+ *   quantiser   y = l * scale (one float multiply), q = (int)y truncated toward zero and clamped to [-7, 7]; when
+ *         !(y > -2^31 && y < 2^31) - NaN, +Inf, -Inf and every |y| >= 2^31, positive ones included - the conversion yields
+ *         the integer indefinite, which ends at -7.
+ *   output   the group's element m * K + k for k < K, else 32 * K + m * M + (k - K) (K = n_var - n_check, M = n_check): the
+ *         fixInput order of lnsfaid_decode.  d_fixInput / fixInput: one int8 per element, group g at byte g * 32 * n_var.
+ *         d_llr4 / llr4: the llr4 format of the packed decode I/O above (element e in byte e / 2, low nibble for even e, group g
+ *         at byte 16 * g * n_var).
+ * Rules: mod_type in {1, 2, 4, 6, 8}; I >= 1 dividing n_var; (32 * n_var) % mod_type == 0 (the rule of
+ * lnsfaid_frontend_device, so everything it can produce these calls can consume); the packed forms also need n_var and K
+ * even; a NULL buffer with n_groups > 0; the device calls: n_groups > max_groups, d_rx or d_llr4 not 4-byte aligned -
+ * LNSFAID_E_INVAL.  n_groups 0 is a no-op (NULL buffers allowed).  d_fixInput may have any alignment.  Alignment beyond that
+ * only selects the width of the loads and stores, never the bytes written.  The calls write exactly n_groups * 32 * n_var bytes
+ * (half of that for the packed forms) and nothing outside.
+ * The device calls queue on the context's stream and return when the output is complete (as lnsfaid_encode_device): a
+ * following lnsfaid_decode*_device needs no synchronisation by the caller. */
+int lnsfaid_demap_device(lnsfaid_ctx* ctx, const float* d_rx, size_t n_groups, int32_t mod_type, float scale, int8_t* d_fixInput);
+int lnsfaid_demap_packed_device(lnsfaid_ctx* ctx, const float* d_rx, size_t n_groups, int32_t mod_type, float scale, uint8_t* d_llr4);
+/* Host only, no context, no GPU (like lnsfaid_pack_llr4): the same bytes, for callers whose samples are in host memory -
+ * quantise there and ship 4 bits per LLR through lnsfaid_decode_packed instead of 32. */
+int lnsfaid_demap_host(int32_t n_var, int32_t n_check, int32_t interleave_mod_type, const float* rx, size_t n_groups,
+                       int32_t mod_type, float scale, int8_t* fixInput);
+int lnsfaid_demap_packed_host(int32_t n_var, int32_t n_check, int32_t interleave_mod_type, const float* rx, size_t n_groups,
+                              int32_t mod_type, float scale, uint8_t* llr4);
 
 /* ---- systematic encoder and device frame source (replaces CLDPC::Encode, reference CLDPC.cpp:68-155) ---------------
  * H = [A | B], B = the last n_check columns.  The parity bits of information bits u are p = B^-1 A u; B^-1 is derived from the

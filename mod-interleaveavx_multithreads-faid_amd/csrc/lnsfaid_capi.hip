@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "lnsfaid_device.h"
+#include "lnsfaid_quantise.h"
 #include "lnsfaid_swar.h" /* sw_nms_fits / sw_nms_tables (host side) */
 
 extern "C" hipError_t lf_launch_decode(int method, int uniform_w, const LfKernelArgs* args, size_t lds_bytes,
@@ -45,6 +46,8 @@ extern "C" hipError_t lf_launch_count_errors(const int8_t* decoded, const int8_t
 extern "C" hipError_t lf_launch_frontend(const uint32_t* d_seeds, const unsigned long long* d_draws, int n_streams, int mod_type,
                                          float sigma_ch, float scale, const int8_t* d_codeword, const int8_t* d_frames, int n_var,
                                          int n_check, int interleave, int fast, int8_t* d_fix, hipStream_t stream);
+extern "C" hipError_t lf_launch_demap(const float* d_rx, size_t n_groups, int mod_type, float scale, int n_var, int n_check,
+                                      int interleave, int packed, void* d_out, hipStream_t stream);
 extern "C" hipError_t lf_frontend_fastpath_scan(double* d_out2, hipStream_t stream);
 extern "C" void lf_frontend_fastpath_assumed(double* eps2);
 extern "C" hipError_t lf_launch_encode(const LfDevCode* d_code, int n_check, const uint32_t* d_bsup, const uint32_t* d_bsup_off,
@@ -1550,6 +1553,113 @@ extern "C" int lnsfaid_frontend_device(lnsfaid_ctx* ctx, const uint32_t* seeds, 
     }
     for (size_t i = 0; i < n_streams; ++i) st[3 * i] = st[3 * i + 1] = st[3 * i + 2] = seeds[i];
     return lnsfaid_frontend_device_states(ctx, st.data(), draws_before, n_streams, mod_type, sigma, scale, codeword, d_fixInput);
+}
+
+/* ---- demapper for received symbols (lnsfaid_demap.hip) ------------------------------------- */
+static int demap_rules(int n_var, int n_check, int interleave, int mod_type, bool packed)
+{
+    if (n_var <= 0 || n_check <= 0 || n_check >= n_var) return LNSFAID_E_INVAL;
+    if (mod_type != 1 && mod_type != 2 && mod_type != 4 && mod_type != 6 && mod_type != 8) return LNSFAID_E_INVAL;
+    if (interleave < 1 || n_var % interleave != 0 || (32L * n_var) % mod_type != 0) return LNSFAID_E_INVAL;
+    if (packed && (n_var % 2 != 0 || (n_var - n_check) % 2 != 0)) return LNSFAID_E_INVAL;
+    return LNSFAID_OK;
+}
+
+static int demap_device_impl(lnsfaid_ctx* ctx, const float* d_rx, size_t n_groups, int32_t mod_type, float scale, void* d_out, bool packed)
+{
+    if (!ctx) return LNSFAID_E_INVAL;
+    const int rc = demap_rules(ctx->n_var, ctx->n_check, ctx->fe_interleave, mod_type, packed);
+    if (rc) return rc;
+    if (n_groups > ctx->max_groups) return LNSFAID_E_INVAL;
+    if (n_groups == 0) return LNSFAID_OK;
+    if (!d_rx || !d_out || !dword_aligned(d_rx) || (packed && !dword_aligned(d_out))) return LNSFAID_E_INVAL;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(lf_launch_demap(d_rx, n_groups, mod_type, scale, ctx->n_var, ctx->n_check, ctx->fe_interleave, packed ? 1 : 0, d_out, ctx->stream));
+    return stream_wait(ctx); /* returns with the output complete, as the encoder does */
+}
+
+extern "C" int lnsfaid_demap_device(lnsfaid_ctx* ctx, const float* d_rx, size_t n_groups, int32_t mod_type, float scale, int8_t* d_fixInput)
+{
+    return demap_device_impl(ctx, d_rx, n_groups, mod_type, scale, d_fixInput, false);
+}
+
+extern "C" int lnsfaid_demap_packed_device(lnsfaid_ctx* ctx, const float* d_rx, size_t n_groups, int32_t mod_type, float scale, uint8_t* d_llr4)
+{
+    return demap_device_impl(ctx, d_rx, n_groups, mod_type, scale, d_llr4, true);
+}
+
+/* One group on the host, the formulas of include/lnsfaid.h taken literally (no HIP call) */
+static void demap_group_host(int N, int M, int I, int mod_type, const float* rx, float scale, int8_t* fix)
+{
+    static const double c16[1] = { 0.6324555 }, c64[2] = { 0.6172134, 0.3086067 }, c256[3] = { 0.613568, 0.306784, 0.153392 };
+    const int K = N - M;
+    if (mod_type == 1) { /* one real float per code bit, frame-major, not interleaved */
+        for (int m = 0; m < 32; ++m)
+            for (int k = 0; k < N; ++k) {
+                const int8_t q = quantise_4bit(rx[(size_t)m * N + k], scale);
+                if (k < K) fix[(size_t)m * K + k] = q;
+                else fix[(size_t)32 * K + (size_t)m * M + (k - K)] = q;
+            }
+        return;
+    }
+    const double* c = mod_type == 4 ? c16 : mod_type == 6 ? c64 : c256;
+    const long symbols = 32L * N / mod_type;
+    for (long s = 0; s < symbols; ++s) {
+        float l[8];
+        l[0] = rx[2 * s];
+        l[1] = rx[2 * s + 1];
+        for (int n = 1; n < mod_type / 2; ++n) { /* every level is stored as float before it feeds the next */
+            l[2 * n] = (float)(fabs((double)l[2 * n - 2]) - c[n - 1]);
+            l[2 * n + 1] = (float)(fabs((double)l[2 * n - 1]) - c[n - 1]);
+        }
+        for (int u = 0; u < mod_type; ++u) {
+            const long pos = (long)mod_type * s + u;
+            const int m = (int)(pos / N), p = (int)(pos % N);
+            const int k = (N / I) * (p % I) + p / I;
+            const int8_t q = quantise_4bit(l[u], scale);
+            if (k < K) fix[(size_t)m * K + k] = q;
+            else fix[(size_t)32 * K + (size_t)m * M + (k - K)] = q;
+        }
+    }
+}
+
+static int demap_host_impl(int32_t n_var, int32_t n_check, int32_t interleave, const float* rx, size_t n_groups, int32_t mod_type,
+                           float scale, void* out, bool packed)
+{
+    const int rc = demap_rules(n_var, n_check, interleave, mod_type, packed);
+    if (rc) return rc;
+    if (n_groups == 0) return LNSFAID_OK;
+    if (!rx || !out) return LNSFAID_E_INVAL;
+    const size_t per = 32 * (size_t)n_var, rx_per = mod_type == 1 ? per : 2 * (per / (size_t)mod_type);
+    std::vector<int8_t> group; /* the packed form quantises a group into bytes first, then packs: every output byte is written whole */
+    if (packed) {
+        try {
+            group.resize(per);
+        } catch (...) {
+            return LNSFAID_E_NOMEM;
+        }
+    }
+    for (size_t g = 0; g < n_groups; ++g) {
+        int8_t* fix = packed ? group.data() : (int8_t*)out + g * per;
+        demap_group_host(n_var, n_check, interleave, mod_type, rx + g * rx_per, scale, fix);
+        if (packed) {
+            const int prc = lnsfaid_pack_llr4(fix, per, (uint8_t*)out + g * (per / 2));
+            if (prc) return prc;
+        }
+    }
+    return LNSFAID_OK;
+}
+
+extern "C" int lnsfaid_demap_host(int32_t n_var, int32_t n_check, int32_t interleave_mod_type, const float* rx, size_t n_groups,
+                                  int32_t mod_type, float scale, int8_t* fixInput)
+{
+    return demap_host_impl(n_var, n_check, interleave_mod_type, rx, n_groups, mod_type, scale, fixInput, false);
+}
+
+extern "C" int lnsfaid_demap_packed_host(int32_t n_var, int32_t n_check, int32_t interleave_mod_type, const float* rx, size_t n_groups,
+                                         int32_t mod_type, float scale, uint8_t* llr4)
+{
+    return demap_host_impl(n_var, n_check, interleave_mod_type, rx, n_groups, mod_type, scale, llr4, true);
 }
 
 /* ---- systematic encoder (lnsfaid_encoder.hip) ----------------------------------------------

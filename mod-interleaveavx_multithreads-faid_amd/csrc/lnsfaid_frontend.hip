@@ -22,6 +22,7 @@
 #include <stdint.h>
 
 #include "lnsfaid.h"
+#include "lnsfaid_quantise.h"
 
 #define FE_RUN 32 /* symbols (QPSK: LLR pairs, 16-QAM: LLR quadruples) per thread */
 
@@ -46,14 +47,6 @@ __device__ __forceinline__ float wh_uniform(WH& s)
     float temp = (((float)s.ix) / ((float)61967)) + (((float)s.iy) / ((float)63443)) + (((float)s.iz) / ((float)63599));
     temp -= (float)(int)temp;
     return temp;
-}
-
-__device__ __forceinline__ int8_t quantise_4bit(float x, float scale)
-{
-    const float y = x * scale;
-    int q = (y > -2147483648.0f && y < 2147483648.0f) ? (int)y : (int)0x80000000; /* cvttps2dq */
-    q = q > 127 ? 127 : (q < -128 ? -128 : q);                                      /* saturating packs */
-    return (int8_t)(q > 7 ? 7 : (q < -7 ? -7 : q));
 }
 
 /* ---- the fast path ------------------------------------------------------------------------------------------------

@@ -92,6 +92,10 @@ SYMBOLS = {
                                                  C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "lnsfaid_frontend_draws_per_group": (C.c_uint64, [C.c_void_p, C.c_int32]),
     "lnsfaid_frontend_set_interleave": (C.c_int, [C.c_void_p, C.c_int32]),
+    "lnsfaid_demap_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_float, C.c_void_p]),
+    "lnsfaid_demap_packed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_float, C.c_void_p]),
+    "lnsfaid_demap_host": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_float, C.c_void_p]),
+    "lnsfaid_demap_packed_host": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_float, C.c_void_p]),
     "lnsfaid_frontend_set_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "lnsfaid_frontend_input_bits": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "lnsfaid_code_parity_inverse": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_size_t]),
@@ -218,6 +222,30 @@ def pack_bits(input_bits, lib=None):
     return out
 
 
+def _demap_host(fn_name, packed, n_var, n_check, interleave, rx, n_groups, mod_type, scale, lib):
+    import numpy as np
+    lib = lib or load()
+    rx = np.ascontiguousarray(rx, dtype=np.float32)
+    floats = n_groups * GROUP * n_var * (1 if mod_type == 1 else 2) // max(mod_type, 1)
+    if rx.size != floats:
+        raise ValueError("%s: rx has %d floats, %d groups of mod_type %d take %d" % (fn_name, rx.size, n_groups, mod_type, floats))
+    out = np.empty(n_groups * GROUP * n_var // (2 if packed else 1), dtype=np.uint8 if packed else np.int8)
+    rc = getattr(lib, fn_name)(n_var, n_check, interleave, rx.ctypes.data, n_groups, mod_type, scale, out.ctypes.data)
+    if rc != 0:
+        raise ValueError("%s failed: %d" % (fn_name, rc))
+    return out
+
+
+def demap_host(n_var, n_check, interleave, rx, n_groups, mod_type, scale, lib=None):
+    """lnsfaid_demap_host: received symbols (float32, the rx format of include/lnsfaid.h) -> int8 fixInput"""
+    return _demap_host("lnsfaid_demap_host", False, n_var, n_check, interleave, rx, n_groups, mod_type, scale, lib)
+
+
+def demap_packed_host(n_var, n_check, interleave, rx, n_groups, mod_type, scale, lib=None):
+    """lnsfaid_demap_packed_host: received symbols -> uint8 llr4, two elements per byte"""
+    return _demap_host("lnsfaid_demap_packed_host", True, n_var, n_check, interleave, rx, n_groups, mod_type, scale, lib)
+
+
 class Decoder:
     """Thin RAII wrapper over lnsfaid_create / lnsfaid_decode* / lnsfaid_destroy."""
 
@@ -330,6 +358,14 @@ class Decoder:
         self._check(self.lib.lnsfaid_count_errors_packed_device(self.ctx, d_bits_ptr, d_msg_ptr, n_groups, out),
                     "lnsfaid_count_errors_packed_device")
         return list(out)
+
+    def demap_device(self, d_rx_ptr, n_groups, mod_type, scale, d_fix_ptr):
+        """lnsfaid_demap_device: received symbols on the device -> int8 fixInput (InterleaveModType: the context's)"""
+        self._check(self.lib.lnsfaid_demap_device(self.ctx, d_rx_ptr, n_groups, mod_type, scale, d_fix_ptr), "lnsfaid_demap_device")
+
+    def demap_packed_device(self, d_rx_ptr, n_groups, mod_type, scale, d_llr4_ptr):
+        self._check(self.lib.lnsfaid_demap_packed_device(self.ctx, d_rx_ptr, n_groups, mod_type, scale, d_llr4_ptr),
+                    "lnsfaid_demap_packed_device")
 
     def encode(self, info, n_groups):
         """info: numpy int8 0/1, [32][K] per group.  Returns the encoder output, [32][K] then [32][M] per group."""
