@@ -446,6 +446,24 @@ int lnsfaid_kernel_waves(const lnsfaid_ctx* ctx);
 int lnsfaid_select_message_store(lnsfaid_ctx* ctx, int32_t where);
 int lnsfaid_message_store(const lnsfaid_ctx* ctx);
 
+/* The layer step without byte rotations on identity circulants (lnsfaid_kernel4z.hip).  Through a circulant of shift 0 a lane's
+ * four rows meet the four bytes of one dword in order, so nothing has to be rotated; the library orders every layer's edges
+ * zero-shift first (the order of a row's edges is free in the four-rows kernels) and runs each layer on an instance of the step
+ * that knows how many leading groups of four edges need no rotation.  Used by the group rule's int8 decode with the messages in
+ * registers (DecodeMethods 1..5) on a code that has such a layer; every other configuration runs as before.  0 (default): where
+ * it applies; LNSFAID_ZERO_SHIFT_ON: the same, LNSFAID_E_INVAL where it does not apply; LNSFAID_ZERO_SHIFT_OFF: the rotating
+ * kernel.  Identical results either way; the switch exists for tests and A/B timing.  Environment: LNSFAID_ZERO_SHIFT=off.
+ * lnsfaid_zero_shift_groups returns 1 if the next decode launches the rotation-free kernel, 0 if not, and writes the number of
+ * rotation-free groups in use for each of the first n layers (zeros when it is not in use).
+ * lnsfaid_code_zero_shift_order needs no GPU: it returns the number of layers (or an error) and writes, per layer, the number of
+ * leading groups of four zero-shift edges (groups[layer], before rounding to a compiled instance) and the edge order of the
+ * rotation-free tables (order[layer * 24 + j]: the edge of the code's own row that is edge j there; -1 beyond the degree). */
+#define LNSFAID_ZERO_SHIFT_ON 1
+#define LNSFAID_ZERO_SHIFT_OFF 2
+int lnsfaid_select_zero_shift(lnsfaid_ctx* ctx, int32_t mode);
+int lnsfaid_zero_shift_groups(const lnsfaid_ctx* ctx, int32_t* groups, int32_t n);
+int lnsfaid_code_zero_shift_order(const lnsfaid_code* code, int32_t* groups, int32_t* order);
+
 /* Workgroups (codewords) of the selected decode kernel a compute unit holds at once, from the HIP occupancy query, next to
  * what the kernel's LDS footprint alone would allow (50G-PON: 8 and 8).  A smaller first number means a build lost residency to
  * registers - about 40 % of the throughput for the one-wave-per-codeword kernel.  Also checks that the kernel has no static LDS

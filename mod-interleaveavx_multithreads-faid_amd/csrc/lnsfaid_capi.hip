@@ -37,6 +37,9 @@ extern "C" hipError_t lf_launch_unpack_llr4(const uint8_t* d_llr4, int8_t* d_fix
 extern "C" hipError_t lf_launch_pack_bits(const int8_t* d_decoded, uint32_t* d_bits, size_t n_values, hipStream_t stream);
 extern "C" hipError_t lf_launch_count_errors_packed(const uint32_t* d_bits, const uint32_t* d_msg, int n_var, int k_info, size_t n_cw,
                                                     unsigned long long* out, hipStream_t stream);
+extern "C" int lf_decode4z_inst(int deg, int zg);
+extern "C" const void* lf_decode4z_func(int method);
+extern "C" hipError_t lf_launch_decode4z(int method, const LfKernelArgs* args, size_t lds_bytes, hipStream_t stream);
 extern "C" const void* lf_decode5_func(int method);
 extern "C" int lf_decode5_threads(void);
 extern "C" hipError_t lf_launch_decode5(int method, const LfKernelArgs* args, size_t lds_bytes, hipStream_t stream);
@@ -130,6 +133,7 @@ struct lnsfaid_ctx {
     int rows_per_lane = 0; /* 0: pick per configuration; 2 / 4: forced (lnsfaid_select_kernel) */
     int waves_per_cw = 0;  /* 0 / 1: one wave per codeword; 2: lnsfaid_kernel5.hip where it applies (lnsfaid_select_waves) */
     int msg_store = 0;     /* 0: pick per code; 1: registers; 2: streamed through HBM (lnsfaid_select_message_store) */
+    int zero_shift = 0;    /* 0: the rotation-free layer step where it applies; 1: the same, asked for; 2: off (lnsfaid_select_zero_shift) */
     struct LfCombiner* comb = nullptr; /* call combiner this one-group context is a member of (see below) */
     int comb_slot = -1;
     const void* checked_fn[4] = {};           /* kernel instance kernel_check() last looked at, per early-stop rule (+ 2: packed I/O) */
@@ -220,6 +224,21 @@ static int build_code(const lnsfaid_code* code, LfDevCode* out)
             }
         }
         e += (size_t)deg * Z;
+        /* the rotation-free layer step's tables (lnsfaid_kernel4z.hip): the zero-shift edges first, ascending block column within
+         * either class (the row is ascending, the partition is stable), and the layer's instance of the step */
+        for (int j = 0; j < 32; ++j) out->zsbplain[br][j] = 0u;
+        int n = 0;
+        for (int zero = 1; zero >= 0; --zero)
+            for (int j = 0; j < deg; ++j)
+                if ((out->s4tab[br][j] == 0u) == (zero != 0)) {
+                    out->zsbplain[br][n] = out->sbplain[br][j];
+                    out->zs4tab[br][n] = out->s4tab[br][j];
+                    out->zcbtab[br][n] = out->cbtab[br][j];
+                    ++n;
+                }
+        int n_zero = 0;
+        while (n_zero < deg && out->zs4tab[br][n_zero] == 0u) ++n_zero;
+        out->zinst[br] = lf_decode4z_inst(deg, n_zero / 4);
     }
     {   /* syndrome walk table: needs the LDS layout (n_words = N / 32, p_words = M / 32) */
         const int nw = N / 32, pw = M / 32;
@@ -437,6 +456,8 @@ extern "C" int lnsfaid_create(lnsfaid_ctx** out, const lnsfaid_code* code, const
         ctx->fe_exact = (e[0] == '1') ? 1 : 0;
     if (const char* e = getenv("LNSFAID_MSG_STORE")) /* test / A-B switch, see lnsfaid_select_message_store */
         ctx->msg_store = (e[0] == 'h') ? LNSFAID_MSG_HBM : ((e[0] == 'r') ? LNSFAID_MSG_REGISTERS : 0);
+    if (const char* e = getenv("LNSFAID_ZERO_SHIFT")) /* test / A-B switch, see lnsfaid_select_zero_shift: "off" / "on" */
+        ctx->zero_shift = (e[0] == 'o' && e[1] == 'f') ? LNSFAID_ZERO_SHIFT_OFF : 0;
     g_live_contexts.fetch_add(1, std::memory_order_relaxed); /* (lnsfaid_destroy takes it back) */
     const int rc = create_impl(ctx, code, cfg);
     if (rc) { lnsfaid_destroy(ctx); return rc; }
@@ -538,6 +559,56 @@ static bool use_msg_registers(const lnsfaid_ctx* ctx)
     return ctx->msg_store != LNSFAID_MSG_HBM;
 }
 
+/* The rotation-free layer step (lnsfaid_kernel4z.hip): the group rule's int8 kernel with the messages in registers, DecodeMethods
+ * 1..5, on a code with at least one layer that leads with a group of four zero-shift edges its degree has an instance for. */
+static int layer_zero_groups(const lnsfaid_ctx* ctx, int br) { return (ctx->hcode.zinst[br] >> 8) & 0xff; }
+static bool zero_shift_possible(const lnsfaid_ctx* ctx)
+{
+    if (!use_kernel4(ctx) || use_kernel5(ctx) || !use_msg_registers(ctx)) return false;
+    if (ctx->hcfg.method < 1 || ctx->hcfg.method > 5 || !lf_decode4z_func(ctx->hcfg.method)) return false;
+    for (int br = 0; br < ctx->hcode.nbr; ++br)
+        if (layer_zero_groups(ctx, br) >= 1) return true;
+    return false;
+}
+static bool use_zero_shift(const lnsfaid_ctx* ctx) { return ctx->zero_shift != LNSFAID_ZERO_SHIFT_OFF && zero_shift_possible(ctx); }
+
+extern "C" int lnsfaid_select_zero_shift(lnsfaid_ctx* ctx, int32_t mode)
+{
+    if (!ctx || mode < 0 || mode > LNSFAID_ZERO_SHIFT_OFF) return LNSFAID_E_INVAL;
+    if (mode == LNSFAID_ZERO_SHIFT_ON && !zero_shift_possible(ctx)) return LNSFAID_E_INVAL;
+    ctx->zero_shift = mode;
+    return LNSFAID_OK;
+}
+
+extern "C" int lnsfaid_zero_shift_groups(const lnsfaid_ctx* ctx, int32_t* groups, int32_t n)
+{
+    if (!ctx || n < 0 || (n > 0 && !groups)) return LNSFAID_E_INVAL;
+    const bool on = use_zero_shift(ctx);
+    for (int br = 0; br < n; ++br) groups[br] = (on && br < ctx->hcode.nbr) ? layer_zero_groups(ctx, br) : 0;
+    return on ? 1 : 0;
+}
+
+extern "C" int lnsfaid_code_zero_shift_order(const lnsfaid_code* code, int32_t* groups, int32_t* order)
+{
+    LfDevCode* dc = new (std::nothrow) LfDevCode;
+    if (!dc) return LNSFAID_E_NOMEM;
+    const int rc = build_code(code, dc);
+    if (rc) { delete dc; return rc; }
+    const int nbr = dc->nbr;
+    for (int br = 0; br < nbr; ++br) {
+        int n_zero = 0;
+        while (n_zero < dc->deg[br] && dc->zs4tab[br][n_zero] == 0u) ++n_zero;
+        if (groups) groups[br] = n_zero / 4;
+        for (int j = 0; order && j < LF_MAX_DEG; ++j) {
+            order[br * LF_MAX_DEG + j] = -1;
+            for (int i = 0; j < dc->deg[br] && i < dc->deg[br]; ++i) /* a block column occurs once per layer */
+                if (dc->cbtab[br][i] == dc->zcbtab[br][j] && dc->s4tab[br][i] == dc->zs4tab[br][j]) order[br * LF_MAX_DEG + j] = i;
+        }
+    }
+    delete dc;
+    return nbr;
+}
+
 /* Under the per-codeword rule (lnsfaid_kernel4cw.hip) the four-rows kernel's configurations have an instance each, with the
  * same message store; the two-rows kernel and the two-waves kernel have none. */
 static bool cw_possible(const lnsfaid_ctx* ctx) { return ctx->waves_per_cw != 2 && use_kernel4(ctx); }
@@ -559,6 +630,10 @@ static const void* selected_kernel(const lnsfaid_ctx* ctx, int* threads, int rul
     if (use_kernel5(ctx)) {
         *threads = lf_decode5_threads();
         return lf_decode5_func(ctx->hcfg.method);
+    }
+    if (use_zero_shift(ctx)) {
+        *threads = lf_decode4_threads();
+        return lf_decode4z_func(ctx->hcfg.method);
     }
     if (use_kernel4(ctx)) {
         *threads = lf_decode4_threads();
@@ -751,6 +826,7 @@ static int decode_device_impl(lnsfaid_ctx* ctx, const int8_t* d_fixInput, size_t
             HIP_TRY(hipEventRecord(ctx->ev_chain[j], ctx->stream));
             if (packed) HIP_TRY(lf_launch_decode4p(ctx->hcfg.method, ctx->hcfg.ef, use_msg_registers(ctx) ? 1 : 0, &a, ctx->lds_bytes, ctx->stream));
             else if (use_kernel5(ctx)) HIP_TRY(lf_launch_decode5(ctx->hcfg.method, &a, ctx->lds_bytes, ctx->stream));
+            else if (use_zero_shift(ctx)) HIP_TRY(lf_launch_decode4z(ctx->hcfg.method, &a, ctx->lds_bytes, ctx->stream));
             else if (use_kernel4(ctx)) HIP_TRY(lf_launch_decode4(ctx->hcfg.method, ctx->hcfg.ef, use_msg_registers(ctx) ? 1 : 0, &a, ctx->lds_bytes, ctx->stream));
             else HIP_TRY(lf_launch_decode(ctx->hcfg.method, ctx->hcfg.uniform_w, &a, ctx->lds_bytes, ctx->stream));
             cur ^= 1;
@@ -1065,7 +1141,7 @@ static void comb_leave(lnsfaid_ctx* ctx, int slot)
 /* 1: decoded through the combiner (*rc_out = result); 0: not applicable now, take the direct path */
 static int comb_decode(lnsfaid_ctx* ctx, const int8_t* fixInput, int8_t* decodedBits, lnsfaid_group_stats* stats, int rule, int* rc_out)
 {
-    if (ctx->comb_slot < 0 || ctx->rows_per_lane != 0 || ctx->msg_store != 0 || ctx->waves_per_cw != 0) return 0;
+    if (ctx->comb_slot < 0 || ctx->rows_per_lane != 0 || ctx->msg_store != 0 || ctx->waves_per_cw != 0 || ctx->zero_shift != 0) return 0;
     LfCombiner* cb = ctx->comb;
     const int slot = ctx->comb_slot;
     {

@@ -48,6 +48,14 @@ struct LfDevCode {
     uint32_t era_edges[LF_MAX_BR];            /* bit j: edge j of the layer is the FIRST edge, in row order, of a block column of
                                                * weight W (EF_ELIMINATION 2 erases a variable node's V2C once per iteration)      */
     uint32_t colcirc[LF_MAX_BC][LF_MAX_COLW]; /* block row | shift << 8 for every circulant of the column         */
+    /* The edge tables of the rotation-free layer step (lnsfaid_kernel4z.hip), at the end so that no other field moves: every layer's
+     * edges with the zero-shift ones (identity circulants) first, ascending block column within either class.  The order of a row's
+     * edges is free in the four-rows kernels; everything above keeps the reference's order. */
+    uint32_t zsbplain[LF_MAX_BR][32];         /* sbplain in that order                                                           */
+    uint32_t zs4tab[LF_MAX_BR][LF_MAX_DEG];   /* s4tab in that order                                                             */
+    uint32_t zcbtab[LF_MAX_BR][LF_MAX_DEG];   /* cbtab in that order                                                             */
+    int32_t zinst[LF_MAX_BR];                 /* the layer's instance of that step: degree << 16 | leading groups of four zero-shift
+                                               * edges in use << 8 | one bit per compiled instance (lf_decode4z_inst)            */
 };
 
 struct LfDevCfg {

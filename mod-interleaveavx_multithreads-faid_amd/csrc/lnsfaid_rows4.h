@@ -383,7 +383,11 @@ __device__ __forceinline__ void regs_clear(SwRegs& R)
  *   LF4_ON_PASS(t)        statement run when it passes a decision point
  * LF4_STAGE_INPUT: the codeword's LLRs from the reference's fixInput layout into the interleaved En image (the LDS);
  * LF4_LAYERED_LOOP: the layered iterations from decision point prog on; LF4_ENTER_BF: the bit-flipping stage's entry when the
- * layered loop ran out; LF4_BF_LOOPS: the bit-flipping iterations.  parked = true when the codeword stopped clean at prog. ---- */
+ * layered loop ran out; LF4_BF_LOOPS: the bit-flipping iterations.  parked = true when the codeword stopped clean at prog.
+ * LF4_MAIN_STEP: the layered iteration the loop runs, main_step4 unless the including file names its own (lnsfaid_kernel4z.hip). ---- */
+#ifndef LF4_MAIN_STEP
+#define LF4_MAIN_STEP main_step4
+#endif
 #define LF4_STAGE_INPUT() \
         /* input staging (CDecoder_FAID.cpp:217-255): lane l of group g is information row l of the [32][K] block followed by                             \
          * parity row l of the [32][M] block; punctured tail erased; interleaved and biased for the layer step */                                         \
@@ -448,7 +452,7 @@ _Pragma("unroll")                                                               
             int tid_i = tid;                                                                                                                                                                             \
             asm volatile("" : "+v"(tid_i));                                                                                                                                                              \
             if (METHOD == 0) { /* CLDPC::Decode has no syndrome stage and no early stop (CLDPC.cpp:287-2283) */                                                                                          \
-                main_step4<METHOD, false, RM>(c, f, a.code, g_rows, R, tid_i, prog, sP, false, false, 0u);                                                                                               \
+                LF4_MAIN_STEP<METHOD, false, RM>(c, f, a.code, g_rows, R, tid_i, prog, sP, false, false, 0u);                                                                                            \
                 prog++;                                                                                                                                                                                  \
                 continue;                                                                                                                                                                                \
             }                                                                                                                                                                                            \
@@ -486,9 +490,9 @@ _Pragma("unroll")                                                               
             if (EF2 && f->ef == 2 && needs_checksums && have_par && lme) {                                                                                                                               \
                 /* EF_ELIMINATION 2 inside the window, few unsatisfied checks: this iteration erases (CDecoder_FAID.cpp:673-680) */                                                                      \
                 build_erasure_plane4(c, a.code, sHard, sP, f->W, tid_i);                                                                                                                                 \
-                main_step4<METHOD, EF2, RM>(c, f, a.code, g_rows, R, tid_i, prog, sP, true, lme, lf_lds_off_hard(N));                                                                                    \
+                LF4_MAIN_STEP<METHOD, EF2, RM>(c, f, a.code, g_rows, R, tid_i, prog, sP, true, lme, lf_lds_off_hard(N));                                                                                 \
             } else {                                                                                                                                                                                     \
-                main_step4<METHOD, false, RM>(c, f, a.code, g_rows, R, tid_i, prog, sP, have_par && needs_checksums, lme, 0u);                                                                           \
+                LF4_MAIN_STEP<METHOD, false, RM>(c, f, a.code, g_rows, R, tid_i, prog, sP, have_par && needs_checksums, lme, 0u);                                                                        \
             }                                                                                                                                                                                            \
             prog++;                                                                                                                                                                                      \
         }                                                                                                                                                                                                \

@@ -533,7 +533,13 @@ struct SwNoXch {
 };
 #define SW_OWN(j) (WAVES == 1 || (((j) & 1) == WAVE))
 
-template <int METHOD, int DEG, bool ERA = false, int WAVES = 1, int WAVE = 0, class Tab, class Xch = SwNoXch>
+/* ZG: the layer's first SW_ILP * ZG edges are known to have shift 0 (identity circulants; the caller ordered the edge table so, and
+ * the order of a row's edges is free: it only decides which of several tied edges is called the arg-min).  Lane i
+ * then reads dword i of the block column and nothing is rotated: per such edge the lane-plus-shift addition, the shift for the
+ * rotate amount, the rotate after the read, and the subtraction and the rotate in front of the write-back are not issued.  The
+ * rotating code is correct for shift 0, so a smaller ZG than the layer has is always exact.  Per-degree instances of one wave per
+ * codeword only. */
+template <int METHOD, int DEG, bool ERA = false, int WAVES = 1, int WAVE = 0, int ZG = 0, class Tab, class Xch = SwNoXch>
 SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, const SwK& K, uint32_t lane, int deg, SwRow cur, bool fresh,
                           uint32_t rowpar, bool lme, uint32_t era_edges = 0u, uint32_t era_plane = 0u, const Xch& xch = Xch())
 {
@@ -544,6 +550,8 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
      * the node was unsatisfied at this iteration's syndrome stage.  On those edges the V2C becomes 0 for such nodes and its
      * sign is the sign of En itself (the back-track of :682 with vContr == 0). */
     static_assert(!ERA || METHOD == 2, "the erasure exists in Decode_FAID only");
+    static_assert(ZG == 0 || (DEG > 0 && WAVES == 1 && !ERA && SW_ILP * ZG <= DEG), "rotation-free groups: per-degree, one-wave, non-erasing instances");
+    constexpr int NZ = SW_ILP * ZG; /* edges 0 .. NZ - 1 need no rotation */
     constexpr int NJ = DEG > 0 ? DEG : SW_MAX_DEG;
     constexpr bool MINSUM = SW_MINSUM(METHOD);
     /* the minimum search merges aligned groups of four edges (pass 1); the per-degree instances only: in the generic one every
@@ -592,7 +600,9 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
     /* ---- pass 1 (CDecoder_FAID.cpp:662-861, CDecoder_OMS.cpp:363-380): all addresses, then all reads, then the arithmetic ---- */
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
-        if ((DEG > 0 || j < deg) && SW_OWN(j)) {
+        if (j < NZ) {
+            ad[j] = tid4 | cbj[j]; /* shift 0: dword `lane` of the column, rows in byte order */
+        } else if ((DEG > 0 || j < deg) && SW_OWN(j)) {
             const uint32_t x4 = tid4 + s4j[j];
 #if SW_DEV
             uint32_t a;
@@ -616,11 +626,14 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
 #define SW_EDGES(...) _Pragma("unroll") for (int g = 0; g < SW_ILP; ++g) { const int j = j0 + g; if (j < NJ && (DEG > 0 || j < deg) && SW_OWN(j)) { __VA_ARGS__ } }
         /* byte k = En + 120 of row k.  The group's LAST read is consumed first: LDS reads return in order, so the one s_waitcnt in
          * front of it covers the group (in ascending order every edge gets a wait of its own) */
-        _Pragma("unroll") for (int g = SW_ILP - 1; g >= 0; --g) { const int j = j0 + g; if (j < NJ && (DEG > 0 || j < deg) && SW_OWN(j)) r_[g] = sw_alignbyte(ld[j], ld[j], rq[j]); }
+        _Pragma("unroll") for (int g = SW_ILP - 1; g >= 0; --g) { const int j = j0 + g; if (j < NJ && (DEG > 0 || j < deg) && SW_OWN(j)) r_[g] = j < NZ ? ld[j] : sw_alignbyte(ld[j], ld[j], rq[j]); }
         SW_EDGES(x_[g] = (j & 7) ? cur.x[j >> 3] >> (j & 7) : cur.x[j >> 3];)
         SW_EDGES(s_[g] = sw_bitop3<SW_TT_ANDOR>(x_[g], c01, c0642);)
         SW_EDGES(k_[g] = sw_perm(kt_hi, kt_lo, s_[g]);)
-        SW_EDGES(tb[j] = r_[g] + k_[g];)                          /* t + 128, VECTOR_SUB_AND_SATURATE comes in pass 2 */
+        /* t + 128, VECTOR_SUB_AND_SATURATE comes in pass 2.  (A rotation-free group has no rotate: this is the first use of its reads,
+         * so it takes their descending order) */
+        if (j0 < NZ) { _Pragma("unroll") for (int g = SW_ILP - 1; g >= 0; --g) tb[j0 + g] = r_[g] + k_[g]; }
+        else { SW_EDGES(tb[j] = r_[g] + k_[g];) }
         if (ERA) {
             SW_EDGES(x_[g] &= c01;)                               /* b: the old message on this edge is negative */
             SW_EDGES(
@@ -789,7 +802,7 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
         SW_EDGES(mo[g] = sw_mask7(mo[g], sel_sign);)     /* under or over */                                         \
         SW_EDGES(lm[g] = sw_upd2_limit<MINSUM>(ms[j], d_[g], u2, c80);)                                              \
         SW_EDGES(EN[g] = sw_upd2_en(mo[g], lm[g], zb[g], d_[g], cm27);)                                              \
-        SW_EDGES(EN[g] = sw_alignbyte(EN[g], EN[g], 4u - rq[j]);)                                                    \
+        SW_EDGES(if (j >= NZ) EN[g] = sw_alignbyte(EN[g], EN[g], 4u - rq[j]);)                                       \
         if (NSTREE) sw_sign_quad<NJ>(ns, ms, j0, deg, DEG > 0, K.c55, K.c33, K.c0f);                                 \
         else SW_EDGES(sw_sign_edge(ns, ms[j], j, cbit[j & 7]);)                                                      \
     }

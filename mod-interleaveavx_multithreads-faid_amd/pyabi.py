@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(HERE, "csrc", "liblnsfaid.so")
 
 GROUP = 32
 MSG_REGISTERS, MSG_HBM = 1, 2  # lnsfaid_select_message_store
+ZERO_SHIFT_ON, ZERO_SHIFT_OFF = 1, 2  # lnsfaid_select_zero_shift
 STOP_GROUP, STOP_CODEWORD = 0, 1  # lnsfaid_set_early_stop
 
 
@@ -119,6 +120,9 @@ SYMBOLS = {
     "lnsfaid_kernel_waves": (C.c_int, [C.c_void_p]),
     "lnsfaid_select_message_store": (C.c_int, [C.c_void_p, C.c_int32]),
     "lnsfaid_message_store": (C.c_int, [C.c_void_p]),
+    "lnsfaid_select_zero_shift": (C.c_int, [C.c_void_p, C.c_int32]),
+    "lnsfaid_zero_shift_groups": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
+    "lnsfaid_code_zero_shift_order": (C.c_int, [C.POINTER(Code), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lnsfaid_kernel_residency": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lnsfaid_kernel_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int32]),
     "lnsfaid_stream": (C.c_void_p, [C.c_void_p]),
@@ -175,6 +179,17 @@ class Code50GPON:
     @property
     def K(self):
         return self.code.n_var - self.code.n_check
+
+
+def code_zero_shift_order(code, lib=None):
+    """lnsfaid_code_zero_shift_order (no GPU needed): per layer, the leading groups of four zero-shift edges and the edge order
+    of the rotation-free tables as indices into the code's own row"""
+    lib = lib or load()
+    groups, order = (C.c_int32 * 32)(), (C.c_int32 * (32 * 24))()
+    nbr = lib.lnsfaid_code_zero_shift_order(C.byref(code), groups, order)
+    if nbr < 0:
+        raise ValueError("lnsfaid_code_zero_shift_order failed: %d" % nbr)
+    return list(groups[:nbr]), [[j for j in order[br * 24:br * 24 + 24] if j >= 0] for br in range(nbr)]
 
 
 def default_cfg(method, max_iter, lib=None):
@@ -410,6 +425,17 @@ class Decoder:
 
     def message_store(self):
         return self.lib.lnsfaid_message_store(self.ctx)
+
+    def select_zero_shift(self, mode):
+        """0 default, ZERO_SHIFT_ON, ZERO_SHIFT_OFF (lnsfaid_select_zero_shift)"""
+        self._check(self.lib.lnsfaid_select_zero_shift(self.ctx, mode), "lnsfaid_select_zero_shift")
+
+    def zero_shift_groups(self, n_layers=32):
+        """(the next decode launches the rotation-free kernel, its rotation-free groups per layer)"""
+        zg = (C.c_int32 * n_layers)()
+        on = self.lib.lnsfaid_zero_shift_groups(self.ctx, zg, n_layers)
+        self._check(min(on, 0), "lnsfaid_zero_shift_groups")
+        return on == 1, list(zg)
 
     def kernel_residency(self):
         """(workgroups per CU of the selected kernel, what its LDS alone allows)"""

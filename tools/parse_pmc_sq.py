@@ -43,21 +43,32 @@ def half_rate_fraction(kernel_name):
     root = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
     csrc = os.path.join(root, "mod-interleaveavx_multithreads-faid_amd", "csrc")
     m = re.search(r"lnsfaid_decode4_kernel<(\d), (true|false), (true|false)>", kernel_name)
-    if not m:
+    z = re.search(r"lnsfaid_decode4z_kernel<(\d)>", kernel_name)  # the rotation-free kernel
+    if not m and not z:
         return None, None
-    mangled = "lnsfaid_decode4_kernelILi%sELb%dELb%dE" % (m.group(1), m.group(2) == "true", m.group(3) == "true")
+    mangled = "lnsfaid_decode4z_kernelILi%sEE" % z.group(1) if z else "lnsfaid_decode4_kernelILi%sELb%dELb%dE" % (m.group(1), m.group(2) == "true", m.group(3) == "true")
+    source = "lnsfaid_kernel4z.hip" if z else "lnsfaid_kernel4.hip"
     with tempfile.TemporaryDirectory() as d:
         out = os.path.join(d, "k4.s")
         subprocess.run(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(root, "include"), "-I" + csrc,
-                        "-S", "--cuda-device-only", "-o", out, os.path.join(csrc, "lnsfaid_kernel4.hip")], check=True, capture_output=True)
+                        "-S", "--cuda-device-only", "-o", out, os.path.join(csrc, source)], check=True, capture_output=True)
         text = open(out).read()
     body = [b for n, b in zip(*[iter(re.split(r"^(_Z\w+):", text, flags=re.M)[1:])] * 2) if mangled in n][0].split(".end_amdhsa_kernel")[0]
     blocks = []
     for chunk in re.split(r"^\.LBB\d+_\d+:", body, flags=re.M):
         ins = [l.split(";")[0].strip() for l in chunk.split("\n")]
         valu = [isa_histogram.classify(i)[1] for i in ins if i.startswith("v_")]
-        blocks.append((len(valu), sum(1 for c in valu if c != "full")))
+        blocks.append((len(valu), sum(1 for c in valu if c != "full"), sum(1 for i in ins if i.startswith("v_alignbyte_b32"))))
     blocks.sort(reverse=True)
+    if z:
+        # one instance of the layer step per (degree, leading rotation-free groups of four edges), told apart by its 2 x rotating
+        # edges v_alignbyte_b32; weighted by the layers of the 50G-PON code that run on it
+        ways = {46: ("deg23_zg0", 6.0), 38: ("deg23_zg1", 3.0), 30: ("deg23_zg2", 1.0), 14: ("deg23_zg4", 1.0), 4: ("deg22_zg5", 1.0), 44: ("deg22_zg0", 0.0)}
+        inst = {ways[r][0]: (v, h, ways[r][1]) for v, h, r in blocks[:len(ways)] if r in ways}
+        assert len(inst) == len(ways), blocks[:8]
+        return (sum(h * w for v, h, w in inst.values()) / sum(v * w for v, h, w in inst.values()),
+                {k: {"valu": v, "half_rate": h, "layers": w} for k, (v, h, w) in sorted(inst.items())})
+    blocks = [b[:2] for b in blocks]
     (v23, h23), (v22, h22) = blocks[0], blocks[1]  # the degree-23 and the degree-22 instance of the layer step
     return (11.0 * h23 + h22) / (11.0 * v23 + v22), {"deg23": {"valu": v23, "half_rate": h23}, "deg22": {"valu": v22, "half_rate": h22}}
 
@@ -69,7 +80,7 @@ out = {
     "kernel_instance": p1["_kernel"],   # bench.py replays the file only for this template instance ...
     "library": open(os.path.join(src, "library_version.txt")).read().strip() if os.path.exists(os.path.join(src, "library_version.txt")) else None,  # ... of this build
     "valu_half_rate_fraction": half_frac,
-    "valu_half_rate_fraction_source": "hipcc -S of the layer step, tools/isa_histogram.py classes, instances weighted 11 : 1",
+    "valu_half_rate_fraction_source": "hipcc -S of the layer step, tools/isa_histogram.py classes, instances weighted by the layers of the 50G-PON code they run",
     "layer_step_instances": half_detail,
     "kernel_source_hash": open(os.path.join(src, "kernel_source_hash.txt")).read().strip(),
     "source": "profiles/%s/pmc_sq_pass1.csv (tools/gpu_pmc_sq.sh)" % tag,
