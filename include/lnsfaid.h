@@ -453,13 +453,22 @@ int lnsfaid_message_store(const lnsfaid_ctx* ctx);
  * registers (DecodeMethods 1..5) on a code that has such a layer; every other configuration runs as before.  0 (default): where
  * it applies; LNSFAID_ZERO_SHIFT_ON: the same, LNSFAID_E_INVAL where it does not apply; LNSFAID_ZERO_SHIFT_OFF: the rotating
  * kernel.  Identical results either way; the switch exists for tests and A/B timing.  Environment: LNSFAID_ZERO_SHIFT=off.
- * lnsfaid_zero_shift_groups returns 1 if the next decode launches the rotation-free kernel, 0 if not, and writes the number of
- * rotation-free groups in use for each of the first n layers (zeros when it is not in use).
+ * On the built-in 50G-PON code (any code whose zero-first edge tables equal its tables entry by entry) the rotation-free kernel
+ * has a layer-static twin (lnsfaid_kernel4s.hip): straight-line code over the twelve layers with degrees, shifts and block columns
+ * as compile-time constants, every identity circulant rotation-free.  The default and LNSFAID_ZERO_SHIFT_ON launch it where it
+ * applies; LNSFAID_ZERO_SHIFT_LOOP keeps the layer loop of lnsfaid_kernel4z.hip there too (LNSFAID_E_INVAL where the rotation-free
+ * kernel does not apply); LNSFAID_ZERO_SHIFT_STATIC asks for the twin, LNSFAID_E_INVAL where it does not apply.  Environment:
+ * LNSFAID_ZERO_SHIFT=loop.
+ * lnsfaid_zero_shift_groups returns 0 if the next decode launches the rotating kernel, 1 for the rotation-free kernel's layer loop,
+ * 2 for its layer-static twin, and writes the number of whole rotation-free groups of four edges for each of the first n layers
+ * (zeros when it is not in use; the twin also goes without rotation on the identity edges beyond them).
  * lnsfaid_code_zero_shift_order needs no GPU: it returns the number of layers (or an error) and writes, per layer, the number of
  * leading groups of four zero-shift edges (groups[layer], before rounding to a compiled instance) and the edge order of the
  * rotation-free tables (order[layer * 24 + j]: the edge of the code's own row that is edge j there; -1 beyond the degree). */
 #define LNSFAID_ZERO_SHIFT_ON 1
 #define LNSFAID_ZERO_SHIFT_OFF 2
+#define LNSFAID_ZERO_SHIFT_LOOP 3
+#define LNSFAID_ZERO_SHIFT_STATIC 4
 int lnsfaid_select_zero_shift(lnsfaid_ctx* ctx, int32_t mode);
 int lnsfaid_zero_shift_groups(const lnsfaid_ctx* ctx, int32_t* groups, int32_t n);
 int lnsfaid_code_zero_shift_order(const lnsfaid_code* code, int32_t* groups, int32_t* order);

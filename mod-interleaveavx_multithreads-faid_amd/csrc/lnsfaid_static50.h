@@ -1,0 +1,85 @@
+/*
+ * lnsfaid_static50.h - the built-in 50G-PON code as a compile-time description for the layer step: per layer the
+ * degree, the number of identity circulants, and 4 * shift / block column * 256 of every edge in the zero-shift-first order of
+ * lnsfaid_kernel4z.hip's tables (LfDevCode zs4tab / zcbtab: zero shifts first, ascending block column within either class), all
+ * derived from the base matrix of lnsfaid_gpon_base.h by a constexpr function.  Sw50Tab<BR> is the layer step's table view of layer
+ * BR with these as constants.  Compiles for the device (lnsfaid_kernel4s.hip) and for the host (tests/static_layers_emul.cpp).
+ */
+#ifndef LNSFAID_STATIC50_H
+#define LNSFAID_STATIC50_H
+
+#include "lnsfaid_gpon_base.h"
+#include "lnsfaid_swar.h"
+
+#define SW50_LAYERS LNSFAID_GPON_BLOCK_ROWS
+
+struct Sw50Layer {
+    int deg, nz;                  /* edges; leading edges with shift 0 */
+    uint32_t s4[SW_MAX_DEG];      /* 4 * shift          */
+    uint32_t cb256[SW_MAX_DEG];   /* block column * 256 */
+};
+struct Sw50Code {
+    Sw50Layer layer[SW50_LAYERS];
+};
+
+constexpr Sw50Code sw50_build()
+{
+    struct Circ { int cb, shift; };
+    constexpr int deg[SW50_LAYERS] = LNSFAID_GPON_ROW_DEG;
+    constexpr Circ base[SW50_LAYERS][LNSFAID_GPON_MAX_DEG] = LNSFAID_GPON_BASE;
+    Sw50Code c = {};
+    for (int br = 0; br < SW50_LAYERS; ++br) {
+        int n = 0;
+        for (int zero = 1; zero >= 0; --zero) /* the stable partition lnsfaid_capi.hip's build_code makes */
+            for (int j = 0; j < deg[br]; ++j)
+                if ((base[br][j].shift == 0) == (zero != 0)) {
+                    c.layer[br].s4[n] = (uint32_t)base[br][j].shift << 2;
+                    c.layer[br].cb256[n] = (uint32_t)base[br][j].cb << 8;
+                    ++n;
+                }
+        c.layer[br].deg = n;
+        int nz = 0;
+        while (nz < n && c.layer[br].s4[nz] == 0u) ++nz;
+        c.layer[br].nz = nz;
+    }
+    return c;
+}
+
+template <int BR>
+struct Sw50Tab {
+    static_assert(BR >= 0 && BR < SW50_LAYERS, "layer of the 50G-PON code");
+    static constexpr Sw50Layer L = sw50_build().layer[BR];
+    static constexpr int DEG = L.deg, NZ = L.nz;
+    uint32_t sbv; /* device, lane j < 32: (block column * 256) << 16 | 4 * shift of edge j - the loaded table of the arg-min look-up */
+    SW_MFN uint32_t s4(int j) const { return L.s4[j]; }
+    SW_MFN uint32_t cb256(int j) const { return L.cb256[j]; }
+    SW_MFN uint32_t sb_dyn4(uint32_t idx4) const
+    {
+#if SW_DEV
+        return (uint32_t)__builtin_amdgcn_ds_bpermute((int)idx4, (int)sbv);
+#else
+        return (L.cb256[idx4 >> 2] << 16) | L.s4[idx4 >> 2];
+#endif
+    }
+};
+template <int BR>
+struct SwTabStatic<Sw50Tab<BR>> {
+    static constexpr bool value = true;
+    static constexpr int nz = Sw50Tab<BR>::NZ;
+};
+
+/* every layer's immediate offset fits the DS instructions' 16-bit field, and the identity edges are the 69 the matrix has */
+constexpr bool sw50_check()
+{
+    constexpr Sw50Code c = sw50_build();
+    int zeros = 0, edges = 0;
+    for (int br = 0; br < SW50_LAYERS; ++br) {
+        for (int j = 0; j < c.layer[br].deg; ++j)
+            if (c.layer[br].cb256[j] + 255u > 0xffffu) return false;
+        zeros += c.layer[br].nz; edges += c.layer[br].deg;
+    }
+    return zeros == 69 && edges == 275;
+}
+static_assert(sw50_check(), "50G-PON base matrix: 275 circulants, 69 of them identities, block columns inside the offset field");
+
+#endif /* LNSFAID_STATIC50_H */

@@ -269,16 +269,17 @@ struct SwParams {
 struct SwLds {
     typedef __attribute__((address_space(3))) uint32_t lds_u32;
     typedef __attribute__((address_space(3))) uint8_t lds_u8;
-    SW_FN uint32_t rd32(uint32_t a) const { return *(const lds_u32*)(size_t)a; }
-    SW_FN void wr32(uint32_t a, uint32_t v) const { *(lds_u32*)(size_t)a = v; }
+    /* off: a compile-time constant below 65 536, which goes into the DS instruction's offset field (0: the plain access) */
+    SW_FN uint32_t rd32(uint32_t a, uint32_t off = 0u) const { return *(const lds_u32*)(size_t)(a + off); }
+    SW_FN void wr32(uint32_t a, uint32_t v, uint32_t off = 0u) const { *(lds_u32*)(size_t)(a + off) = v; }
     SW_FN uint32_t rd8(uint32_t a) const { return *(const lds_u8*)(size_t)a; }
     SW_FN void wr8(uint32_t a, uint32_t v) const { *(lds_u8*)(size_t)a = (uint8_t)v; }
 };
 #else
 struct SwLds {
     uint8_t* base;
-    uint32_t rd32(uint32_t a) const { return (uint32_t)base[a] | ((uint32_t)base[a + 1] << 8) | ((uint32_t)base[a + 2] << 16) | ((uint32_t)base[a + 3] << 24); }
-    void wr32(uint32_t a, uint32_t v) const { base[a] = (uint8_t)v; base[a + 1] = (uint8_t)(v >> 8); base[a + 2] = (uint8_t)(v >> 16); base[a + 3] = (uint8_t)(v >> 24); }
+    uint32_t rd32(uint32_t a, uint32_t off = 0u) const { a += off; return (uint32_t)base[a] | ((uint32_t)base[a + 1] << 8) | ((uint32_t)base[a + 2] << 16) | ((uint32_t)base[a + 3] << 24); }
+    void wr32(uint32_t a, uint32_t v, uint32_t off = 0u) const { a += off; base[a] = (uint8_t)v; base[a + 1] = (uint8_t)(v >> 8); base[a + 2] = (uint8_t)(v >> 16); base[a + 3] = (uint8_t)(v >> 24); }
     uint32_t rd8(uint32_t a) const { return base[a]; }
     void wr8(uint32_t a, uint32_t v) const { base[a] = (uint8_t)v; }
 };
@@ -533,12 +534,22 @@ struct SwNoXch {
 };
 #define SW_OWN(j) (WAVES == 1 || (((j) & 1) == WAVE))
 
+/* A table view whose s4(j) / cb256(j) are compile-time constants of (layer, j) specialises this (lnsfaid_static50.h): `value` and the
+ * layer's exact number `nz` of leading zero-shift edges.  The layer step then takes shifts and block columns as literals, puts the
+ * block column into the LDS instructions' offset fields and drops the rotation work of exactly nz edges. */
+template <class Tab>
+struct SwTabStatic {
+    static constexpr bool value = false;
+    static constexpr int nz = 0;
+};
+
 /* ZG: the layer's first SW_ILP * ZG edges are known to have shift 0 (identity circulants; the caller ordered the edge table so, and
  * the order of a row's edges is free: it only decides which of several tied edges is called the arg-min).  Lane i
  * then reads dword i of the block column and nothing is rotated: per such edge the lane-plus-shift addition, the shift for the
  * rotate amount, the rotate after the read, and the subtraction and the rotate in front of the write-back are not issued.  The
  * rotating code is correct for shift 0, so a smaller ZG than the layer has is always exact.  Per-degree instances of one wave per
- * codeword only. */
+ * codeword only.
+ * A static table view (SwTabStatic) names the exact count instead: NZ need not be a multiple of SW_ILP then. */
 template <int METHOD, int DEG, bool ERA = false, int WAVES = 1, int WAVE = 0, int ZG = 0, class Tab, class Xch = SwNoXch>
 SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, const SwK& K, uint32_t lane, int deg, SwRow cur, bool fresh,
                           uint32_t rowpar, bool lme, uint32_t era_edges = 0u, uint32_t era_plane = 0u, const Xch& xch = Xch())
@@ -551,7 +562,9 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
      * sign is the sign of En itself (the back-track of :682 with vContr == 0). */
     static_assert(!ERA || METHOD == 2, "the erasure exists in Decode_FAID only");
     static_assert(ZG == 0 || (DEG > 0 && WAVES == 1 && !ERA && SW_ILP * ZG <= DEG), "rotation-free groups: per-degree, one-wave, non-erasing instances");
-    constexpr int NZ = SW_ILP * ZG; /* edges 0 .. NZ - 1 need no rotation */
+    constexpr bool STATIC = SwTabStatic<Tab>::value;
+    static_assert(!STATIC || (ZG == 0 && DEG > 0 && WAVES == 1 && !ERA && SwTabStatic<Tab>::nz <= DEG), "static table view: per-degree, one-wave, non-erasing instances");
+    constexpr int NZ = STATIC ? SwTabStatic<Tab>::nz : SW_ILP * ZG; /* edges 0 .. NZ - 1 need no rotation */
     constexpr int NJ = DEG > 0 ? DEG : SW_MAX_DEG;
     constexpr bool MINSUM = SW_MINSUM(METHOD);
     /* the minimum search merges aligned groups of four edges (pass 1); the per-degree instances only: in the generic one every
@@ -601,21 +614,24 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
 #pragma unroll
     for (int j = 0; j < NJ; ++j) {
         if (j < NZ) {
-            ad[j] = tid4 | cbj[j]; /* shift 0: dword `lane` of the column, rows in byte order */
+            ad[j] = STATIC ? tid4 : tid4 | cbj[j]; /* shift 0: dword `lane` of the column, rows in byte order */
         } else if ((DEG > 0 || j < deg) && SW_OWN(j)) {
             const uint32_t x4 = tid4 + s4j[j];
 #if SW_DEV
             uint32_t a;
-            asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(a) : "v"(x4), "v"(cfc), "s"(cbj[j]));
+            if (STATIC) a = x4 & cfc; /* (the block column is the access's offset) */
+            else asm("v_and_or_b32 %0, %1, %2, %3" : "=v"(a) : "v"(x4), "v"(cfc), "s"(cbj[j]));
 #else
-            const uint32_t a = (x4 & cfc) | cbj[j];
+            const uint32_t a = STATIC ? x4 & cfc : (x4 & cfc) | cbj[j];
 #endif
             ad[j] = a; rq[j] = x4 >> 8;
         }
     }
+    /* static table view: ad[] is the dword inside the column, the column's base the immediate offset of every access of the edge */
+#define SW_COL(j) (STATIC ? cbj[j] : 0u)
 #pragma unroll
     for (int j = 0; j < NJ; ++j)
-        if ((DEG > 0 || j < deg) && SW_OWN(j)) ld[j] = lds.rd32(ad[j]);
+        if ((DEG > 0 || j < deg) && SW_OWN(j)) ld[j] = lds.rd32(ad[j], SW_COL(j));
     SW_SCHED_FENCE();
     /* The arithmetic of an edge is one long dependency chain and the hardware issues a wave's instructions in order, so the
      * statements below are written stage by stage over groups of SW_ILP edges: consecutive instructions then belong to
@@ -631,8 +647,8 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
         SW_EDGES(s_[g] = sw_bitop3<SW_TT_ANDOR>(x_[g], c01, c0642);)
         SW_EDGES(k_[g] = sw_perm(kt_hi, kt_lo, s_[g]);)
         /* t + 128, VECTOR_SUB_AND_SATURATE comes in pass 2.  (A rotation-free group has no rotate: this is the first use of its reads,
-         * so it takes their descending order) */
-        if (j0 < NZ) { _Pragma("unroll") for (int g = SW_ILP - 1; g >= 0; --g) tb[j0 + g] = r_[g] + k_[g]; }
+         * so it takes their descending order; a group with a rotating edge in it keeps the rotates' order) */
+        if ((j0 + SW_ILP < NJ ? j0 + SW_ILP : NJ) <= NZ) { _Pragma("unroll") for (int g = SW_ILP - 1; g >= 0; --g) if (j0 + g < NJ) tb[j0 + g] = r_[g] + k_[g]; }
         else { SW_EDGES(tb[j] = r_[g] + k_[g];) }
         if (ERA) {
             SW_EDGES(x_[g] &= c01;)                               /* b: the old message on this edge is negative */
@@ -809,7 +825,7 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
 #define SW_PASS2_STORE(J0, EN)                                                                                       \
     {                                                                                                                \
         const int j0 = (J0);                                                                                         \
-        SW_EDGES(lds.wr32(ad[j], EN[g]);)                                                                            \
+        SW_EDGES(lds.wr32(ad[j], EN[g], SW_COL(j));)                                                                 \
     }
     uint32_t en0[SW_ILP], en1[SW_ILP];
     SW_PASS2_ARITH(0, en0)
@@ -870,6 +886,7 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
 #undef SW_EDGES
 #undef SW_PASS2_ARITH
 #undef SW_PASS2_STORE
+#undef SW_COL
     if (WAVES == 2) {
         if (WAVE == 1) { xch.put(0, ns[0]); xch.put(1, ns[1]); xch.put(2, ns[2]); }
         xch.barrier(); /* D: wave 1's En is in LDS */

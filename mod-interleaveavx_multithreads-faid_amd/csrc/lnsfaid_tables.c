@@ -13,29 +13,18 @@
 #include "lnsfaid.h"
 #include <string.h>
 
+#include "lnsfaid_gpon_base.h" /* the base matrix itself: shared with the layer-static decode kernel's compile-time tables */
+
 #define GPON_Z 256
-#define GPON_BLOCK_ROWS 12
+#define GPON_BLOCK_ROWS LNSFAID_GPON_BLOCK_ROWS
 #define GPON_BLOCK_COLS 69
-#define GPON_MAX_DEG 23
+#define GPON_MAX_DEG LNSFAID_GPON_MAX_DEG
 
 typedef struct { int16_t cb; int16_t shift; } gpon_circ;
 
-static const int gpon_row_deg[GPON_BLOCK_ROWS] = { 23, 22, 23, 23, 23, 23, 23, 23, 23, 23, 23, 23 };
+static const int gpon_row_deg[GPON_BLOCK_ROWS] = LNSFAID_GPON_ROW_DEG;
 
-static const gpon_circ gpon_base[GPON_BLOCK_ROWS][GPON_MAX_DEG] = {
-    /* r0  */ { {0,80}, {3,60}, {4,169}, {6,11}, {8,143}, {11,222}, {13,59}, {15,218}, {18,178}, {24,105}, {27,19}, {30,126}, {34,211}, {40,247}, {42,255}, {45,85}, {52,246}, {53,94}, {59,242}, {64,129}, {66,19}, {67,58}, {68,27} },
-    /* r1  */ { {1,0}, {3,0}, {5,0}, {7,0}, {9,0}, {11,0}, {13,0}, {15,0}, {17,0}, {18,0}, {20,0}, {24,0}, {27,0}, {32,0}, {36,0}, {39,0}, {43,0}, {47,0}, {52,0}, {56,0}, {60,0}, {67,0} },
-    /* r2  */ { {1,91}, {3,74}, {5,237}, {6,202}, {9,201}, {10,136}, {12,178}, {14,239}, {16,183}, {19,217}, {21,232}, {25,169}, {32,129}, {33,60}, {39,19}, {40,76}, {46,77}, {50,2}, {54,101}, {57,217}, {61,48}, {67,172}, {68,42} },
-    /* r3  */ { {0,105}, {3,87}, {5,43}, {7,165}, {9,180}, {11,80}, {12,227}, {14,221}, {16,77}, {19,0}, {24,16}, {29,252}, {31,96}, {33,0}, {38,17}, {44,219}, {47,198}, {48,165}, {53,36}, {58,171}, {63,228}, {67,39}, {68,234} },
-    /* r4  */ { {1,170}, {2,250}, {5,195}, {6,139}, {9,135}, {11,92}, {13,147}, {15,1}, {20,13}, {23,98}, {26,142}, {30,225}, {36,23}, {37,108}, {44,0}, {46,0}, {51,135}, {56,121}, {57,0}, {63,0}, {66,46}, {67,242}, {68,228} },
-    /* r5  */ { {1,46}, {3,37}, {5,49}, {6,150}, {8,65}, {11,177}, {12,144}, {14,70}, {16,95}, {19,221}, {23,192}, {25,128}, {28,214}, {34,51}, {38,100}, {41,19}, {44,235}, {52,4}, {55,251}, {58,109}, {64,140}, {67,193}, {68,241} },
-    /* r6  */ { {0,137}, {2,104}, {4,238}, {7,228}, {9,225}, {10,247}, {13,191}, {15,177}, {17,255}, {22,192}, {27,51}, {32,195}, {34,0}, {37,172}, {43,219}, {46,236}, {49,136}, {53,0}, {57,159}, {60,10}, {65,5}, {67,25}, {68,94} },
-    /* r7  */ { {1,118}, {2,15}, {4,93}, {7,228}, {9,78}, {11,16}, {12,0}, {14,48}, {16,0}, {20,62}, {22,0}, {25,0}, {30,0}, {36,112}, {38,0}, {45,0}, {49,0}, {50,0}, {55,22}, {61,0}, {62,0}, {67,120}, {68,192} },
-    /* r8  */ { {1,208}, {2,0}, {4,0}, {6,0}, {8,0}, {10,0}, {13,251}, {14,0}, {17,44}, {18,123}, {23,0}, {26,0}, {31,0}, {35,0}, {40,0}, {43,153}, {48,0}, {51,0}, {55,0}, {65,0}, {66,0}, {67,16}, {68,0} },
-    /* r9  */ { {0,0}, {3,123}, {5,41}, {6,191}, {8,211}, {10,217}, {12,243}, {14,97}, {16,252}, {21,0}, {28,0}, {31,41}, {35,29}, {37,0}, {42,0}, {47,193}, {49,145}, {54,0}, {61,140}, {62,46}, {65,58}, {67,202}, {68,215} },
-    /* r10 */ { {0,209}, {2,252}, {4,39}, {7,159}, {8,69}, {10,37}, {12,134}, {15,201}, {16,49}, {21,104}, {26,129}, {29,157}, {33,222}, {41,139}, {42,39}, {48,203}, {50,94}, {56,194}, {59,3}, {62,43}, {63,153}, {67,207}, {68,109} },
-    /* r11 */ { {0,53}, {2,93}, {4,216}, {7,57}, {8,9}, {10,130}, {13,130}, {15,238}, {22,144}, {28,162}, {29,0}, {35,175}, {39,145}, {41,0}, {45,36}, {51,91}, {54,22}, {58,0}, {59,0}, {60,212}, {64,0}, {67,69}, {68,88} },
-};
+static const gpon_circ gpon_base[GPON_BLOCK_ROWS][GPON_MAX_DEG] = LNSFAID_GPON_BASE;
 
 int lnsfaid_code_50gpon(lnsfaid_code* code, uint16_t* pos_vn, int32_t* deg3, int32_t* deg_rows3)
 {

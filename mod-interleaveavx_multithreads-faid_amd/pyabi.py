@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(HERE, "csrc", "liblnsfaid.so")
 
 GROUP = 32
 MSG_REGISTERS, MSG_HBM = 1, 2  # lnsfaid_select_message_store
-ZERO_SHIFT_ON, ZERO_SHIFT_OFF = 1, 2  # lnsfaid_select_zero_shift
+ZERO_SHIFT_ON, ZERO_SHIFT_OFF, ZERO_SHIFT_LOOP, ZERO_SHIFT_STATIC = 1, 2, 3, 4  # lnsfaid_select_zero_shift
 STOP_GROUP, STOP_CODEWORD = 0, 1  # lnsfaid_set_early_stop
 
 
@@ -427,7 +427,7 @@ class Decoder:
         return self.lib.lnsfaid_message_store(self.ctx)
 
     def select_zero_shift(self, mode):
-        """0 default, ZERO_SHIFT_ON, ZERO_SHIFT_OFF (lnsfaid_select_zero_shift)"""
+        """0 default, ZERO_SHIFT_ON, ZERO_SHIFT_OFF, ZERO_SHIFT_LOOP, ZERO_SHIFT_STATIC (lnsfaid_select_zero_shift)"""
         self._check(self.lib.lnsfaid_select_zero_shift(self.ctx, mode), "lnsfaid_select_zero_shift")
 
     def zero_shift_groups(self, n_layers=32):
@@ -435,7 +435,13 @@ class Decoder:
         zg = (C.c_int32 * n_layers)()
         on = self.lib.lnsfaid_zero_shift_groups(self.ctx, zg, n_layers)
         self._check(min(on, 0), "lnsfaid_zero_shift_groups")
-        return on == 1, list(zg)
+        return on >= 1, list(zg)
+
+    def static_layers(self):
+        """the next decode launches the layer-static kernel (lnsfaid_kernel4s.hip)"""
+        on = self.lib.lnsfaid_zero_shift_groups(self.ctx, None, 0)
+        self._check(min(on, 0), "lnsfaid_zero_shift_groups")
+        return on == 2
 
     def kernel_residency(self):
         """(workgroups per CU of the selected kernel, what its LDS alone allows)"""
