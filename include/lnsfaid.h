@@ -348,6 +348,55 @@ int lnsfaid_demap_host(int32_t n_var, int32_t n_check, int32_t interleave_mod_ty
 int lnsfaid_demap_packed_host(int32_t n_var, int32_t n_check, int32_t interleave_mod_type, const float* rx, size_t n_groups,
                               int32_t mod_type, float scale, uint8_t* llr4);
 
+/* ---- pre-FEC error counters ---------------------------------------------------------------------------
+ * The counterpart of lnsfaid_count_errors on the input side of the decoder: hard decisions on the demapper's levels against
+ * the sent bits.  Replaces CModulate::ModCalErr (CModulate.cpp:382-437) and feeds the ModBER / ModSER / ModFER columns of
+ * demod.txt (reference main.cpp:183-185).  One definition for every entry point:
+ *   levels    for a group of 32 frames and mod_type in {1, 2, 4, 6, 8} exactly the levels of the demapper section above: level
+ *             u of symbol s is the LLR of stream position pos = mod_type * s + u, every level stored as float before it feeds
+ *             the next; mod_type 1: one float per code bit, frame-major, no interleaver.
+ *   code bit  frame m = pos / n_var, p = pos % n_var, k = (n_var / I) * (p % I) + p / I, I = InterleaveModType (mod_type 1: k = p).
+ *   decision  d = level > 0 ? 1 : 0 (ModCalErr's `demodseq > 0`): +0.0, -0.0 and NaN decide 0, +Inf decides 1.  The quantiser's
+ *             scale plays no part.
+ *   sent bit  sent[g][m * K + k] for k < K, else sent[g][32 * K + m * M + (k - K)]: the layout of CLDPC::outputBits, of
+ *             lnsfaid_encode* and of lnsfaid_frontend_set_frames (group g at byte g * 32 * n_var).  sent == NULL means the
+ *             all-zero codeword.  A bit is wrong when d differs from the sent byte.
+ *   scope     LNSFAID_PREFEC_INFO: only positions with k < K take part (ModCalErr's range, the denominators of demod.txt);
+ *             LNSFAID_PREFEC_CODEWORD: all n_var positions take part, the punctured tail included (the simulated channel
+ *             transmits it).
+ *   counters  out[4], ADDED to like lnsfaid_count_errors:
+ *             out[0] TestFrame       += 32 per group
+ *             out[1] ModErrorFrame   frames with at least one wrong in-scope bit
+ *             out[2] ModErrorBits    wrong in-scope bits
+ *             out[3] ModErrorSymbol  channel symbols with at least one wrong in-scope bit (mod_type 1: equals ModErrorBits)
+ *             Four words on purpose: lnsfaid_allreduce_counters sums them across ranks unchanged.
+ * Rules: those of the demapper, plus n_var % mod_type == 0 (no symbol straddles two frames) and scope 1 or 2 - LNSFAID_E_INVAL
+ * otherwise; a NULL rx or out with n_groups > 0 too.  n_groups 0 is a no-op (NULL buffers allowed).
+ * Deviations from ModCalErr, both on purpose: the sent bit is indexed correctly for every frame (the reference's index is
+ * right for frame 0 only, and its call is commented out, CSimulate.cpp:129); and a symbol is the channel's symbol, not mod_type
+ * consecutive code bits - the two coincide when I = 1 and mod_type divides K. */
+#define LNSFAID_PREFEC_INFO 1
+#define LNSFAID_PREFEC_CODEWORD 2
+/* Host only, no context, no GPU (like lnsfaid_demap_host): the reference the device paths are tested against. */
+int lnsfaid_prefec_errors_host(int32_t n_var, int32_t n_check, int32_t interleave_mod_type, const float* rx, size_t n_groups,
+                               int32_t mod_type, const int8_t* sent, int32_t scope, uint64_t out[4]);
+/* Device-resident symbols and sent bits, the context's InterleaveModType (lnsfaid_frontend_set_interleave).  d_rx: the format and
+ * the rules of lnsfaid_demap_device (4-byte aligned, n_groups <= max_groups); d_sent may have any alignment.  More alignment only
+ * widens the loads, it never changes a count.  A pure read.  Queues on the context's stream and returns when out is complete;
+ * no synchronisation by the caller is needed after a preceding *_device call. */
+int lnsfaid_prefec_errors_device(lnsfaid_ctx* ctx, const float* d_rx, size_t n_groups, int32_t mod_type, const int8_t* d_sent,
+                                 int32_t scope, uint64_t out[4]);
+/* Counting inside the device front-end, which never stores a level.  scope 0 = off (the default), LNSFAID_PREFEC_INFO /
+ * LNSFAID_PREFEC_CODEWORD = every later lnsfaid_frontend_device / _states call counts its own decisions against the bits it
+ * sent (codeword, set_frames, random_frames or all-zero) into an accumulator on the device; TestFrame advances by 32 per stream
+ * per call.  The fixInput bytes are those of a call without counting, and the counters do not depend on
+ * lnsfaid_frontend_set_exact (with counting on, the fast path also sends a symbol to the double-precision chain when a level's
+ * sign is not certain).  While a scope is set, front-end calls with n_var % mod_type != 0 return LNSFAID_E_INVAL.
+ * lnsfaid_frontend_set_prefec clears the accumulator.  lnsfaid_frontend_prefec_counters synchronises the context's stream, ADDS
+ * the accumulator to out and, with reset != 0, clears it; it is the only call that reads the accumulator back. */
+int lnsfaid_frontend_set_prefec(lnsfaid_ctx* ctx, int32_t scope);
+int lnsfaid_frontend_prefec_counters(lnsfaid_ctx* ctx, uint64_t out[4], int32_t reset);
+
 /* ---- systematic encoder and device frame source (replaces CLDPC::Encode, reference CLDPC.cpp:68-155) ---------------
  * H = [A | B], B = the last n_check columns.  The parity bits of information bits u are p = B^-1 A u; B^-1 is derived from the
  * code table (the reference's GenMatrix is not shipped) lazily, at the first lnsfaid_encode* / lnsfaid_frontend_random_frames

@@ -51,7 +51,11 @@ extern "C" hipError_t lf_launch_count_errors(const int8_t* decoded, const int8_t
 
 extern "C" hipError_t lf_launch_frontend(const uint32_t* d_seeds, const unsigned long long* d_draws, int n_streams, int mod_type,
                                          float sigma_ch, float scale, const int8_t* d_codeword, const int8_t* d_frames, int n_var,
-                                         int n_check, int interleave, int fast, int8_t* d_fix, hipStream_t stream);
+                                         int n_check, int interleave, int fast, int8_t* d_fix, int count_limit,
+                                         unsigned long long* d_frame_cnt, hipStream_t stream);
+extern "C" hipError_t lf_launch_prefec(const float* d_rx, const int8_t* d_sent, size_t n_groups, int mod_type, int n_var, int n_check,
+                                       int interleave, int scope, unsigned long long* d_out, hipStream_t stream);
+extern "C" hipError_t lf_launch_prefec_fold(unsigned long long* d_frame_cnt, size_t n_streams, unsigned long long* d_acc, hipStream_t stream);
 extern "C" hipError_t lf_launch_demap(const float* d_rx, size_t n_groups, int mod_type, float scale, int n_var, int n_check,
                                       int interleave, int packed, void* d_out, hipStream_t stream);
 extern "C" hipError_t lf_frontend_fastpath_scan(double* d_out2, hipStream_t stream);
@@ -158,6 +162,9 @@ struct lnsfaid_ctx {
     size_t fe_frames_streams = 0;  /* 0: frames not in use */
     int fe_interleave = 1;         /* InterleaveModType of the device front-end */
     int fe_exact = 0;              /* 1: every symbol through the double-precision chain (lnsfaid_frontend_set_exact) */
+    int fe_prefec = 0;             /* scope of the fused pre-FEC counting (lnsfaid_frontend_set_prefec), 0 = off */
+    unsigned long long* d_fe_prefec_frames = nullptr; /* [max_groups * 32] wrong bits | symbols << 32 per frame of one call */
+    unsigned long long* d_fe_prefec_acc = nullptr;    /* the four counters, read only by lnsfaid_frontend_prefec_counters */
     /* encoder (lnsfaid_encoder.hip): support of B^-1's first rows, derived at the first encode / random-frames call */
     int enc_state = 0;                      /* 0: not derived yet, 1: on the device, LNSFAID_E_CODE: parity part singular */
     uint32_t* d_enc_sup = nullptr;          /* entries b * z + c, block row after block row */
@@ -380,6 +387,7 @@ extern "C" void lnsfaid_destroy(lnsfaid_ctx* ctx)
     (void)hipFree(ctx->d_fe_seeds); (void)hipFree(ctx->d_fe_draws); (void)hipFree(ctx->d_fe_codeword);
     (void)hipFree(ctx->d_fe_frames); (void)hipFree(ctx->d_fe_input);
     (void)hipFree(ctx->d_enc_sup); (void)hipFree(ctx->d_enc_off); (void)hipFree(ctx->d_fe_keys);
+    (void)hipFree(ctx->d_fe_prefec_frames); (void)hipFree(ctx->d_fe_prefec_acc);
     if (ctx->h_remaining) (void)hipHostFree(ctx->h_remaining);
     if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -1594,6 +1602,7 @@ extern "C" int lnsfaid_frontend_device_states(lnsfaid_ctx* ctx, const uint32_t* 
     if (!ctx || !states || !draws_before || !d_fixInput || (mod_type != 2 && mod_type != 4 && mod_type != 6 && mod_type != 8)) return LNSFAID_E_INVAL;
     if (n_streams == 0) return LNSFAID_OK;
     if (n_streams > ctx->max_groups || (32L * ctx->n_var) % mod_type != 0) return LNSFAID_E_INVAL;
+    if (ctx->fe_prefec && ctx->n_var % mod_type != 0) return LNSFAID_E_INVAL; /* a symbol must not straddle two frames */
     HIP_TRY(hipSetDevice(ctx->device));
     if (!ctx->d_fe_seeds) {
         HIP_TRY(hipMalloc(&ctx->d_fe_seeds, ctx->max_groups * 3 * sizeof(uint32_t)));
@@ -1608,7 +1617,10 @@ extern "C" int lnsfaid_frontend_device_states(lnsfaid_ctx* ctx, const uint32_t* 
     HIP_TRY(lf_launch_frontend(ctx->d_fe_seeds, ctx->d_fe_draws, (int)n_streams, mod_type, sigma_ch, scale,
                                codeword ? ctx->d_fe_codeword : nullptr,
                                (!codeword && ctx->fe_frames_streams >= n_streams) ? ctx->d_fe_frames : nullptr, ctx->n_var,
-                               ctx->n_check, ctx->fe_interleave, ctx->fe_exact ? 0 : 1, d_fixInput, ctx->stream));
+                               ctx->n_check, ctx->fe_interleave, ctx->fe_exact ? 0 : 1, d_fixInput,
+                               ctx->fe_prefec == LNSFAID_PREFEC_INFO ? ctx->k_info : ctx->fe_prefec ? ctx->n_var : 0,
+                               ctx->fe_prefec ? ctx->d_fe_prefec_frames : nullptr, ctx->stream));
+    if (ctx->fe_prefec) HIP_TRY(lf_launch_prefec_fold(ctx->d_fe_prefec_frames, n_streams, ctx->d_fe_prefec_acc, ctx->stream));
     HIP_TRY(hipStreamSynchronize(ctx->stream)); /* states / draws_before may be reused by the caller */
     return LNSFAID_OK;
 }
@@ -1617,6 +1629,37 @@ extern "C" int lnsfaid_frontend_set_exact(lnsfaid_ctx* ctx, int32_t exact)
 {
     if (!ctx || exact < 0 || exact > 1) return LNSFAID_E_INVAL;
     ctx->fe_exact = exact;
+    return LNSFAID_OK;
+}
+
+extern "C" int lnsfaid_frontend_set_prefec(lnsfaid_ctx* ctx, int32_t scope)
+{
+    if (!ctx || (scope != 0 && scope != LNSFAID_PREFEC_INFO && scope != LNSFAID_PREFEC_CODEWORD)) return LNSFAID_E_INVAL;
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (scope && !ctx->d_fe_prefec_frames) {
+        const size_t bytes = ctx->max_groups * LNSFAID_GROUP * sizeof(unsigned long long);
+        HIP_TRY(hipMalloc(&ctx->d_fe_prefec_acc, 4 * sizeof(unsigned long long)));
+        HIP_TRY(hipMalloc(&ctx->d_fe_prefec_frames, bytes));
+        HIP_TRY(hipMemsetAsync(ctx->d_fe_prefec_frames, 0, bytes, ctx->stream)); /* from here on the fold kernel leaves it cleared */
+    }
+    if (ctx->d_fe_prefec_acc) {
+        HIP_TRY(hipMemsetAsync(ctx->d_fe_prefec_acc, 0, 4 * sizeof(unsigned long long), ctx->stream));
+        const int rcw = stream_wait(ctx);
+        if (rcw) return rcw;
+    }
+    ctx->fe_prefec = scope;
+    return LNSFAID_OK;
+}
+
+extern "C" int lnsfaid_frontend_prefec_counters(lnsfaid_ctx* ctx, uint64_t out[4], int32_t reset)
+{
+    if (!ctx || !out) return LNSFAID_E_INVAL;
+    if (!ctx->d_fe_prefec_acc) return LNSFAID_OK; /* counting was never switched on: nothing to add */
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemcpyAsync(ctx->h_counters, ctx->d_fe_prefec_acc, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    if (reset) HIP_TRY(hipMemsetAsync(ctx->d_fe_prefec_acc, 0, 4 * sizeof(unsigned long long), ctx->stream));
+    { const int rcw = stream_wait(ctx); if (rcw) return rcw; }
+    for (int i = 0; i < 4; ++i) out[i] += ctx->h_counters[i];
     return LNSFAID_OK;
 }
 
@@ -1756,6 +1799,85 @@ extern "C" int lnsfaid_demap_packed_host(int32_t n_var, int32_t n_check, int32_t
                                          int32_t mod_type, float scale, uint8_t* llr4)
 {
     return demap_host_impl(n_var, n_check, interleave_mod_type, rx, n_groups, mod_type, scale, llr4, true);
+}
+
+/* ---- pre-FEC error counters (lnsfaid_prefec.hip) ------------------------------------------- */
+static int prefec_rules(int n_var, int n_check, int interleave, int mod_type, int scope)
+{
+    const int rc = demap_rules(n_var, n_check, interleave, mod_type, false);
+    if (rc) return rc;
+    if (n_var % mod_type != 0) return LNSFAID_E_INVAL; /* no symbol straddles two frames */
+    if (scope != LNSFAID_PREFEC_INFO && scope != LNSFAID_PREFEC_CODEWORD) return LNSFAID_E_INVAL;
+    return LNSFAID_OK;
+}
+
+extern "C" int lnsfaid_prefec_errors_device(lnsfaid_ctx* ctx, const float* d_rx, size_t n_groups, int32_t mod_type, const int8_t* d_sent,
+                                            int32_t scope, uint64_t out[4])
+{
+    if (!ctx) return LNSFAID_E_INVAL;
+    const int rc = prefec_rules(ctx->n_var, ctx->n_check, ctx->fe_interleave, mod_type, scope);
+    if (rc) return rc;
+    if (n_groups > ctx->max_groups) return LNSFAID_E_INVAL;
+    if (n_groups == 0) return LNSFAID_OK;
+    if (!d_rx || !out || !dword_aligned(d_rx)) return LNSFAID_E_INVAL;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(hipMemsetAsync(ctx->d_counters, 0, 4 * sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(lf_launch_prefec(d_rx, d_sent, n_groups, mod_type, ctx->n_var, ctx->n_check, ctx->fe_interleave, scope, ctx->d_counters, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->h_counters, ctx->d_counters, 4 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    { const int rcw = stream_wait(ctx); if (rcw) return rcw; }
+    for (int i = 0; i < 4; ++i) out[i] += ctx->h_counters[i];
+    return LNSFAID_OK;
+}
+
+/* The definition of include/lnsfaid.h taken literally (no HIP call): the reference of the device paths */
+extern "C" int lnsfaid_prefec_errors_host(int32_t n_var, int32_t n_check, int32_t interleave_mod_type, const float* rx, size_t n_groups,
+                                          int32_t mod_type, const int8_t* sent, int32_t scope, uint64_t out[4])
+{
+    static const double c16[1] = { 0.6324555 }, c64[2] = { 0.6172134, 0.3086067 }, c256[3] = { 0.613568, 0.306784, 0.153392 };
+    const int rc = prefec_rules(n_var, n_check, interleave_mod_type, mod_type, scope);
+    if (rc) return rc;
+    if (n_groups == 0) return LNSFAID_OK;
+    if (!rx || !out) return LNSFAID_E_INVAL;
+    const int N = n_var, M = n_check, K = N - M, I = mod_type == 1 ? 1 : interleave_mod_type;
+    const int k_lim = scope == LNSFAID_PREFEC_INFO ? K : N;
+    const size_t per = 32 * (size_t)N, rx_per = mod_type == 1 ? per : 2 * (per / (size_t)mod_type);
+    const double* c = mod_type == 4 ? c16 : mod_type == 6 ? c64 : c256;
+    const long symbols = (long)(per / (size_t)mod_type);
+    for (size_t g = 0; g < n_groups; ++g) {
+        const float* r = rx + g * rx_per;
+        const int8_t* s = sent ? sent + g * per : nullptr;
+        uint64_t frame_bits[32] = { 0 }, sym_err = 0;
+        for (long sy = 0; sy < symbols; ++sy) {
+            float l[8];
+            if (mod_type == 1) {
+                l[0] = r[sy];
+            } else {
+                l[0] = r[2 * sy];
+                l[1] = r[2 * sy + 1];
+                for (int n = 1; n < mod_type / 2; ++n) { /* every level is stored as float before it feeds the next */
+                    l[2 * n] = (float)(fabs((double)l[2 * n - 2]) - c[n - 1]);
+                    l[2 * n + 1] = (float)(fabs((double)l[2 * n - 1]) - c[n - 1]);
+                }
+            }
+            int wrong = 0, m = 0;
+            for (int u = 0; u < mod_type; ++u) {
+                const long pos = (long)mod_type * sy + u;
+                const int p = (int)(pos % N);
+                m = (int)(pos / N); /* the same for every u: mod_type divides n_var */
+                const int k = (N / I) * (p % I) + p / I;
+                if (k >= k_lim) continue;
+                const int b = s ? (int)s[k < K ? (size_t)m * K + k : (size_t)32 * K + (size_t)m * M + (k - K)] : 0;
+                const int d = l[u] > 0.0f ? 1 : 0;
+                wrong += d != b ? 1 : 0;
+            }
+            frame_bits[m] += (uint64_t)wrong;
+            sym_err += wrong ? 1u : 0u;
+        }
+        out[0] += LNSFAID_GROUP;
+        for (int m = 0; m < 32; ++m) { out[1] += frame_bits[m] ? 1u : 0u; out[2] += frame_bits[m]; }
+        out[3] += sym_err;
+    }
+    return LNSFAID_OK;
 }
 
 /* ---- systematic encoder (lnsfaid_encoder.hip) ----------------------------------------------

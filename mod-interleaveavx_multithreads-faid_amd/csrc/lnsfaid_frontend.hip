@@ -154,13 +154,32 @@ __device__ __forceinline__ uint32_t jump_small(uint32_t x, uint32_t e)
     return x;
 }
 
-/* MOD: Profile.txt modType (bits per symbol); FAST: the fast path above / every symbol through the double-precision chain */
-template <int MOD, bool FAST>
+/* the LDS of the COUNT = true instances (the others have none) */
+template <bool COUNT>
+__device__ __forceinline__ unsigned int* frontend_count_lds()
+{
+    if constexpr (COUNT) {
+        __shared__ unsigned int s[2 * LNSFAID_GROUP];
+        return s;
+    } else {
+        return nullptr;
+    }
+}
+
+/* MOD: Profile.txt modType (bits per symbol); FAST: the fast path above / every symbol through the double-precision chain;
+ * COUNT: pre-FEC error counting (lnsfaid_frontend_set_prefec) - the kernel holds the sent bit and the levels of
+ * every position anyway.  The decision is level > 0, so with COUNT the fast path has one more threshold to be certain about:
+ * zero.  A workgroup spans frame boundaries (never a symbol: n_var is a multiple of MOD under COUNT), so the wrong bits and symbols
+ * are summed per frame in LDS and leave as one atomic per frame the workgroup touched, into
+ * frame_cnt[stream * 32 + frame] = bits | symbols << 32, which lnsfaid_prefec_fold_kernel folds after the launch.
+ * k_lim: code bits in scope (K or n_var).  The COUNT = false instances ignore k_lim and frame_cnt. */
+template <int MOD, bool FAST, bool COUNT>
 __global__ __launch_bounds__(256) void lnsfaid_frontend_kernel(const uint32_t* __restrict__ states,
                                                                const unsigned long long* __restrict__ draws_before,
                                                                float sigma_ch, float scale, const int8_t* __restrict__ codeword,
                                                                const int8_t* __restrict__ frames, int n_var, int n_check,
-                                                               int interleave, int8_t* __restrict__ fix_input)
+                                                               int interleave, int8_t* __restrict__ fix_input, uint32_t k_lim,
+                                                               unsigned long long* __restrict__ frame_cnt)
 {
     constexpr bool fast = FAST;
     /* (all positions of a stream fit 32 bits: 32 n_var <= 2^21) */
@@ -170,7 +189,9 @@ __global__ __launch_bounds__(256) void lnsfaid_frontend_kernel(const uint32_t* _
     const uint32_t bits = 32u * N;
     const uint32_t symbols = bits / Q;
     const uint32_t first = (blockIdx.x * 256u + threadIdx.x) * FE_RUN;
-    if (first >= symbols) return;
+    if constexpr (!COUNT) {
+        if (first >= symbols) return;
+    }
     int8_t* out = fix_input + (size_t)stream * (size_t)bits;
     /* sent bit: the stream's own 32 frames (encoder output layout = the fixInput layout), or one codeword repeated in every frame
      * (FakeEncoder), or all-zero */
@@ -189,7 +210,7 @@ __global__ __launch_bounds__(256) void lnsfaid_frontend_kernel(const uint32_t* _
     WHF sf;
     sf.ix = (float)si.ix; sf.iy = (float)si.iy; sf.iz = (float)si.iz;
     const double sigma = (double)sigma_ch;
-    const uint32_t last = first + FE_RUN < symbols ? first + FE_RUN : symbols;
+    const uint32_t last = first + FE_RUN < symbols ? first + FE_RUN : symbols; /* (COUNT: below first for a thread without symbols) */
     /* Modulation / Demodulation / (de)interleaver of reference CModulate.cpp:95-362 for QPSK, 16-, 64- and 256-QAM: symbol i
      * takes stream positions Q i .. Q i + Q - 1, position p of a frame carries code bit (N / I) (p mod I) + p div I. */
     const float t2[2] = { -0.707107f, 0.707107f };
@@ -212,15 +233,24 @@ __global__ __launch_bounds__(256) void lnsfaid_frontend_kernel(const uint32_t* _
      * and leave as one 4- / 8-byte store (three 2-byte stores for 64-QAM) */
     const bool wide = Q > 2 && I == 1 && (K % Q) == 0 && (N % Q) == 0 && ((size_t)out % 8) == 0;
     uint32_t pack[4] = { 0u, 0u, 0u, 0u };
+    /* COUNT: wrong bits and symbols of the frame the thread is in (a run of FE_RUN symbols meets at most two frames) */
+    [[maybe_unused]] uint32_t cnt_fm = fm, cnt_bits = 0u, cnt_syms = 0u;
+    [[maybe_unused]] unsigned int* const sCnt = frontend_count_lds<COUNT>(); /* [0..31] bits, [32..63] symbols of each frame */
+    if constexpr (COUNT) {
+        if (threadIdx.x < 2 * LNSFAID_GROUP) sCnt[threadIdx.x] = 0u;
+        __syncthreads();
+    }
 #pragma unroll 1
     for (uint32_t i = first; i < last; ++i) {
         uint32_t idx_i = 0, idx_q = 0;
+        [[maybe_unused]] uint32_t sym_fm = fm, sent_bits = 0u, in_scope = 0u; /* COUNT: the symbol's frame, its sent bits and which of them take part */
         uint32_t cidx[8]; /* index of each LLR of the symbol in the stream's fixInput ([32][K] then [32][M]) */
 #pragma unroll
         for (uint32_t u = 0; u < Q; ++u) {
             const uint32_t kbit = stride * fi + fd; /* code bit carried by this position */
             cidx[u] = kbit < K ? fm * K + kbit : 32u * K + fm * M + (kbit - K);
             const uint32_t b = fr ? (uint32_t)fr[cidx[u]] : (codeword ? (uint32_t)codeword[kbit] : 0u);
+            if constexpr (COUNT) { sent_bits |= (b & 1u) << u; in_scope |= (kbit < k_lim ? 1u : 0u) << u; }
             if (u & 1u) idx_q += b << (half - u / 2 - 1); else idx_i += b << (half - u / 2 - 1);
             if (++fi == I) { fi = 0; ++fd; }
             if (++fp == N) { fp = 0; fi = 0; fd = 0; ++fm; }
@@ -253,6 +283,8 @@ __global__ __launch_bounds__(256) void lnsfaid_frontend_kernel(const uint32_t* _
                 const float y = l[u] * scale;
                 /* (every level adds one float rounding of a value below 2) */
                 certain = certain && quantiser_certain(y, fabsf(scale) * (dl + 2.5e-7f * (float)(u / 2)) + 2.5e-7f * fabsf(y));
+                /* the decision threshold: a level not above its own bound may have the other sign in double precision */
+                if constexpr (COUNT) certain = certain && fabsf(l[u]) > dl + 2.5e-7f * (float)(u / 2);
             }
         }
         if (!certain) { /* the reference's chain in double precision */
@@ -265,6 +297,17 @@ __global__ __launch_bounds__(256) void lnsfaid_frontend_kernel(const uint32_t* _
                 l[2 * n] = (float)(fabs((double)l[2 * n - 2]) - c);
                 l[2 * n + 1] = (float)(fabs((double)l[2 * n - 1]) - c);
             }
+        }
+        if constexpr (COUNT) {
+            if (sym_fm != cnt_fm) { /* the run has entered the next frame */
+                if (cnt_bits) { atomicAdd(&sCnt[cnt_fm], cnt_bits); atomicAdd(&sCnt[LNSFAID_GROUP + cnt_fm], cnt_syms); }
+                cnt_fm = sym_fm; cnt_bits = 0u; cnt_syms = 0u;
+            }
+            uint32_t wrong = 0u;
+#pragma unroll
+            for (uint32_t u = 0; u < Q; ++u) wrong += ((in_scope >> u) & 1u) & ((l[u] > 0.0f ? 1u : 0u) ^ ((sent_bits >> u) & 1u));
+            cnt_bits += wrong;
+            cnt_syms += wrong ? 1u : 0u;
         }
         if (packed) {
             const uint32_t k = i - first;
@@ -289,12 +332,21 @@ __global__ __launch_bounds__(256) void lnsfaid_frontend_kernel(const uint32_t* _
             for (uint32_t u = 0; u < Q; ++u) out[cidx[u]] = quantise_4bit(l[u], scale);
         }
     }
+    if constexpr (COUNT) {
+        if (cnt_bits) { atomicAdd(&sCnt[cnt_fm], cnt_bits); atomicAdd(&sCnt[LNSFAID_GROUP + cnt_fm], cnt_syms); }
+        __syncthreads();
+        if (threadIdx.x < LNSFAID_GROUP && sCnt[threadIdx.x])
+            atomicAdd(&frame_cnt[(size_t)stream * LNSFAID_GROUP + threadIdx.x],
+                      (unsigned long long)sCnt[threadIdx.x] | ((unsigned long long)sCnt[LNSFAID_GROUP + threadIdx.x] << 32));
+    }
 }
 
 extern "C" hipError_t lf_launch_frontend(const uint32_t* d_seeds, const unsigned long long* d_draws, int n_streams, int mod_type,
                                          float sigma_ch, float scale, const int8_t* d_codeword, const int8_t* d_frames, int n_var,
-                                         int n_check, int interleave, int fast, int8_t* d_fix, hipStream_t stream)
+                                         int n_check, int interleave, int fast, int8_t* d_fix, int count_limit,
+                                         unsigned long long* d_frame_cnt, hipStream_t stream)
 {
+    /* count_limit: 0 = no pre-FEC counting, else the number of code bits in scope (K or n_var); d_frame_cnt: [n_streams * 32] */
     const long symbols = 32L * n_var / mod_type;
     const unsigned bx = (unsigned)((symbols + 256L * FE_RUN - 1) / (256L * FE_RUN));
     /* grid.y holds at most 65535 streams: more are launched in slices (pointers advanced per slice; the kernel indexes its
@@ -306,16 +358,22 @@ extern "C" hipError_t lf_launch_frontend(const uint32_t* d_seeds, const unsigned
         const unsigned long long* draws = d_draws + s0;
         const int8_t* fr = d_frames ? d_frames + (size_t)s0 * 32 * (size_t)n_var : nullptr;
         int8_t* fix = d_fix + (size_t)s0 * 32 * (size_t)n_var;
+        unsigned long long* fc = d_frame_cnt ? d_frame_cnt + (size_t)s0 * LNSFAID_GROUP : nullptr;
+        const uint32_t kl = (uint32_t)count_limit;
+#define FE_GO(MOD, FAST, COUNT)                                                                                                    \
+    hipLaunchKernelGGL((lnsfaid_frontend_kernel<MOD, FAST, COUNT>), grid, block, 0, stream, seeds, draws, sigma_ch, scale, d_codeword, fr, \
+                       n_var, n_check, interleave, fix, kl, fc)
 #define FE_LAUNCH(MOD)                                                                                                             \
     case MOD:                                                                                                                      \
-        if (fast) hipLaunchKernelGGL((lnsfaid_frontend_kernel<MOD, true>), grid, block, 0, stream, seeds, draws, sigma_ch, scale, d_codeword, fr, n_var, n_check, interleave, fix); \
-        else hipLaunchKernelGGL((lnsfaid_frontend_kernel<MOD, false>), grid, block, 0, stream, seeds, draws, sigma_ch, scale, d_codeword, fr, n_var, n_check, interleave, fix);     \
+        if (count_limit) { if (fast) FE_GO(MOD, true, true); else FE_GO(MOD, false, true); }                                       \
+        else { if (fast) FE_GO(MOD, true, false); else FE_GO(MOD, false, false); }                                                 \
         break;
         switch (mod_type) {
             FE_LAUNCH(2) FE_LAUNCH(4) FE_LAUNCH(6) FE_LAUNCH(8)
         default: return hipErrorInvalidValue;
         }
 #undef FE_LAUNCH
+#undef FE_GO
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return e;
     }

@@ -177,6 +177,20 @@ void CLDPC::DeviceChannel(int decode_method, const uint32_t* states, const uint6
     m_device_io = true;
 }
 
+void CLDPC::DevicePrefec(int decode_method, int scope)
+{
+    const int rc = lnsfaid_frontend_set_prefec(context(decode_method), scope);
+    if (rc) die("lnsfaid_frontend_set_prefec", rc);
+}
+
+void CLDPC::DevicePrefecCounters(int decode_method, unsigned long counters[4], bool reset)
+{
+    uint64_t c[4] = { 0, 0, 0, 0 };
+    const int rc = lnsfaid_frontend_prefec_counters(context(decode_method), c, reset ? 1 : 0);
+    if (rc) die("lnsfaid_frontend_prefec_counters", rc);
+    for (int i = 0; i < 4; ++i) counters[i] += (unsigned long)c[i];
+}
+
 uint64_t CLDPC::DrawsPerGroup(int mod_type)
 {
     return (uint64_t)32 * (uint64_t)m_N / (uint64_t)mod_type * 4u; /* 2 normals per symbol, 2 uniforms per normal */

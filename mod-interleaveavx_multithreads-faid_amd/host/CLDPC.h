@@ -75,6 +75,11 @@ public:
     void DeviceChannel(int decode_method, const uint32_t* states, const uint64_t* draws_before, int mod_type, float sigma,
                        float scale);
     uint64_t DrawsPerGroup(int mod_type);
+    /* --prefec with --device-frontend: the front-end counts its own channel decisions against the bits it sent
+     * (lnsfaid_frontend_set_prefec: 0 = off, LNSFAID_PREFEC_INFO / _CODEWORD; clears the device accumulator) and
+     * {TestFrame, ModErrorFrame, ModErrorBits, ModErrorSymbol} are ADDED to counters, once per CSimulate::Run */
+    void DevicePrefec(int decode_method, int scope);
+    void DevicePrefecCounters(int decode_method, unsigned long counters[4], bool reset);
 
     /* Factor_1 / Factor_2 as the reference re-reads them from Profile.txt on every decode call */
     void SetFactors(int factor_1, int factor_2) { m_factor_1 = factor_1; m_factor_2 = factor_2; }

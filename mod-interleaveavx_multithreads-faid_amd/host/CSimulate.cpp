@@ -20,6 +20,7 @@ static const int seed_table[] = { 101, 103, 107, 109, 113, 127, 131, 137, 139, 1
     983, 991, 997, 1009, 1013, 1019 };
 
 const char* g_dump_fixinput = nullptr;
+const char* g_dump_symbols = nullptr;
 
 int SimulationSeed(int index)
 {
@@ -65,6 +66,7 @@ void CSimulate::Configure(float Eb_N0, int _decode_method)
     /* the reference's switch sends every value outside 1..5 to Decode() (CSimulate.cpp:161-163) */
     decode_method = (_decode_method >= 1 && _decode_method <= 5) ? _decode_method : 0;
     TestFrame = ErrorFrame = ErrorBits = LT3ErrBitFrame = 0;
+    ModCounters[0] = ModCounters[1] = ModCounters[2] = ModCounters[3] = 0;
 }
 
 void CSimulate::Run()
@@ -126,6 +128,10 @@ void CSimulate::Run()
         }
         if (device_frontend) ldpc->DeviceFrames(decode_method, encode, InterleaveModType); /* the 32 frames of every stream, once per 50 calls */
     }
+    /* --prefec: the fused counting of the device front-end (read once, after the 50 calls), or lnsfaid_prefec_errors_host on
+     * every stream's received symbols */
+    if (prefec && device_frontend) ldpc->DevicePrefec(decode_method, LNSFAID_PREFEC_INFO);
+    std::vector<uint64_t> mod_counters(prefec && !device_frontend ? 4 * (size_t)m_streams : 0, 0);
     std::vector<float> llr(device_frontend ? 0 : (size_t)m_streams * bits);
     std::vector<int> BFiters_((size_t)m_streams * 51, 0); /* per stream, reference CSimulate.cpp:99 */
     std::vector<uint32_t> states(3 * (size_t)m_streams);
@@ -178,10 +184,23 @@ void CSimulate::Run()
                     }
                 }
             }
+            if (prefec) { /* ModCalErr's place in the chain (reference CSimulate.cpp:129) */
+                const float* rx = ModulationType == 1 ? ch.BPSKSymbol.data() : (const float*)ch.SymbolSeq.data();
+                const int rc = lnsfaid_prefec_errors_host(N, M, I, rx, 1, ModulationType, ldpc->outputBits + (encode ? (size_t)s * bits : 0),
+                                                          LNSFAID_PREFEC_INFO, mod_counters.data() + 4 * (size_t)s);
+                if (rc) { fprintf(stderr, "lnsfaid_prefec_errors_host failed: %d\n", rc); exit(EXIT_FAILURE); }
+            }
             /* AfterDeModulationDeInterleaver (CModulate.cpp:152-212) + float2LimitChar_4bit, frame-major -> [32][K] | [32][M] */
             for (int m = 0; m < 32; ++m) {
                 ldpc->float2LimitChar_4bit(fix + (size_t)m * K, dst + (size_t)m * N, scale, (size_t)K);
                 ldpc->float2LimitChar_4bit(fix + (size_t)32 * K + (size_t)m * M, dst + (size_t)m * N + K, scale, (size_t)M);
+            }
+        }
+        if (g_dump_symbols && !device_frontend) {
+            std::ofstream dump(g_dump_symbols, std::ios::binary | std::ios::app);
+            for (int s = 0; s < m_streams; ++s) {
+                const float* rx = ModulationType == 1 ? channel[s].BPSKSymbol.data() : (const float*)channel[s].SymbolSeq.data();
+                dump.write((const char*)rx, (std::streamsize)((ModulationType == 1 ? bits : 2 * sym) * sizeof(float)));
             }
         }
         if (g_dump_fixinput && !device_frontend) {
@@ -224,6 +243,8 @@ void CSimulate::Run()
             ldpc->CollectErrors(fl.empty() ? nullptr : fl.data(), m_Z);
         }
     }
+    if (prefec && device_frontend) ldpc->DevicePrefecCounters(decode_method, ModCounters, true);
+    for (size_t i = 0; i < mod_counters.size(); ++i) ModCounters[i % 4] += (unsigned long)mod_counters[i];
     /* reference CSimulate.cpp:171-179: every worker appends its histogram after its 50 calls */
     std::ofstream iterOut("iterCount.txt", std::ios::app);
     for (int s = 0; s < m_streams; ++s)

@@ -27,6 +27,9 @@ public:
     bool device_frontend = false; /* generate the channel output on the GPU (lnsfaid_frontend_device) */
     bool encode = false;          /* GenMsgSeq + Encode instead of FakeEncoder (reference FAKE_ENCODE 0) */
     bool device_encode = false;   /* random messages drawn and encoded on the device (needs device_frontend) */
+    bool prefec = false;          /* --prefec: count the channel's hard decisions on the information bits (CModulate::ModCalErr) */
+    /* {TestFrame, ModErrorFrame, ModErrorBits, ModErrorSymbol} of the point so far, under LNSFAID_PREFEC_INFO */
+    unsigned long ModCounters[4] = { 0, 0, 0, 0 };
     unsigned long sum_iterations = 0, sum_bf_iterations = 0, decoded_groups = 0;
 
     ~CSimulate();
@@ -41,6 +44,7 @@ private:
     std::vector<uint64_t> m_draws; /* all zero: the device front-end is handed the current generator states */
 };
 
+extern const char* g_dump_symbols;  /* --dump-symbols F: the host front-end appends every call's received symbols (the rx format of lnsfaid_demap_*) to F */
 extern const char* g_dump_fixinput; /* --dump-fixinput F: every call appends the batch's fixInput to F (tests: BPSK noise is not reproducible elsewhere) */
 int SimulationSeed(int index); /* the reference's seed table, CSimulate.cpp:11-17 */
 #endif

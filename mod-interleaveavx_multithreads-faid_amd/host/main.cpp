@@ -49,15 +49,17 @@ int main(int argc, char** argv)
     const char* run_id = "";
     int comm_timeout_s = 120;
     const int64_t started_at = (int64_t)time(nullptr);
-    bool device_frontend = false, force_collect = false, encode = false, device_encode = false;
+    bool device_frontend = false, force_collect = false, encode = false, device_encode = false, prefec = false;
     const char* profile = "Profile.txt";
     const char* resume = nullptr;
-    const char* usage = "usage: %s [--streams T] [--gpus G] [--profile Profile.txt] [--max-rounds R] [--device-frontend [--device-encode]] [--encode] [--collect] [--resume Temp.txt] [--early-stop group|codeword] [--ranks N --rank r --comm-file F [--run-id ID] [--comm-timeout S] [--device d]]\n";
+    const char* usage = "usage: %s [--streams T] [--gpus G] [--profile Profile.txt] [--max-rounds R] [--device-frontend [--device-encode]] [--encode] [--prefec] [--collect] [--resume Temp.txt] [--early-stop group|codeword] [--ranks N --rank r --comm-file F [--run-id ID] [--comm-timeout S] [--device d]]\n";
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--streams") && i + 1 < argc) streams = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--gpus") && i + 1 < argc) gpus = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--profile") && i + 1 < argc) profile = argv[++i];
         else if (!strcmp(argv[i], "--dump-fixinput") && i + 1 < argc) g_dump_fixinput = argv[++i]; /* test hook */
+        else if (!strcmp(argv[i], "--dump-symbols") && i + 1 < argc) g_dump_symbols = argv[++i]; /* test hook (host front-end) */
+        else if (!strcmp(argv[i], "--prefec")) prefec = true; /* pre-FEC error rates of the information bits into demod.txt (CModulate::ModCalErr) */
         else if (!strcmp(argv[i], "--ranks") && i + 1 < argc) ranks = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--rank") && i + 1 < argc) rank = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--device") && i + 1 < argc) device = atoi(argv[++i]);
@@ -104,6 +106,7 @@ int main(int argc, char** argv)
         simulate[g].device_frontend = device_frontend;
         simulate[g].encode = encode;
         simulate[g].device_encode = device_encode;
+        simulate[g].prefec = prefec;
         simulate[g].Initial(p_simulation, first, last - first, multi ? device : g);
     }
     if (multi) { /* RCCL communicator of this run: the id travels through --comm-file */
@@ -167,6 +170,7 @@ int main(int argc, char** argv)
 
     for (float snr = p_simulation.snr_start; snr < p_simulation.snr_end; snr += p_simulation.snr_pass) {
         unsigned long TestFrame = 0, ErrorFrame = 0, ErrorBits = 0, LT3ErrBitFrame = 0;
+        unsigned long Mod[4] = { 0, 0, 0, 0 }; /* --prefec: TestFrame, ModErrorFrame, ModErrorBits, ModErrorSymbol */
         double BER = 0, FER = 0, decode_s = 0;
         for (const char* name : { "iterCount.txt", "errorindex.txt", "errorfloat.txt", "errordecode.txt" }) { /* reference main.cpp:145-157 */
             ofstream f(name, std::ios::app);
@@ -187,6 +191,13 @@ int main(int argc, char** argv)
             }
             if (multi) simulate[0].ldpc->AllReduceCounters(add); /* the same sum over the ranks' GPUs */
             TestFrame += add[0]; ErrorFrame += add[1]; ErrorBits += add[2]; LT3ErrBitFrame += add[3];
+            if (prefec) { /* the same sums for the pre-FEC counters: over the simulators, then over the ranks */
+                unsigned long mod[4] = { 0, 0, 0, 0 };
+                for (auto& s : simulate)
+                    for (int i = 0; i < 4; ++i) mod[i] += s.ModCounters[i];
+                if (multi) simulate[0].ldpc->AllReduceCounters(mod);
+                for (int i = 0; i < 4; ++i) Mod[i] += mod[i];
+            }
             BER = (double)(ErrorBits > 0 ? ErrorBits : 1) / ((double)TestFrame * (NmoinsK - _ShortenBits));
             FER = (double)(ErrorFrame > 0 ? ErrorFrame : 1) / TestFrame;
             if (FER < 1E-5 || force_collect) collectflag = 1; /* reference main.cpp:190-192: dump the error frames from here on */
@@ -207,19 +218,25 @@ int main(int argc, char** argv)
         unsigned long groups = 0;
         for (auto& s : simulate) { decode_s = decode_s > s.decode_seconds ? decode_s : s.decode_seconds; groups += s.decoded_groups; s.decoded_groups = 0; }
         const double gbps = decode_s > 0 ? (double)groups * 32 * NmoinsK / decode_s / 1e9 : 0;
-        if (rank == 0) cout << setw(5) << snr << setw(20) << TestFrame << setw(15) << ErrorFrame << setw(20) << ErrorBits << setw(20) << FER << setw(20) << BER
-             << setw(15) << LT3ErrBitFrame << setw(15) << total_time << setw(18) << gbps << endl;
+        /* reference main.cpp:183-186: the demapper's own error rates, over the information bits */
+        const double ModBER = (double)Mod[2] / ((double)TestFrame * (NmoinsK - _ShortenBits));
+        const double ModSER = (double)Mod[3] / ((double)TestFrame * (NmoinsK - _ShortenBits) / p_simulation.mod_type);
+        const double ModFER = (double)Mod[1] / TestFrame;
+        if (rank == 0) {
+            cout << setw(5) << snr << setw(20) << TestFrame << setw(15) << ErrorFrame << setw(20) << ErrorBits << setw(20) << FER << setw(20) << BER
+                 << setw(15) << LT3ErrBitFrame << setw(15) << total_time << setw(18) << gbps;
+            if (prefec) cout << setw(15) << ModFER << setw(15) << ModBER << setw(15) << ModSER;
+            cout << endl;
+            if (prefec) cout << "pre-FEC counters: TestFrame " << Mod[0] << " ModErrorFrame " << Mod[1] << " ModErrorBits " << Mod[2]
+                             << " ModErrorSymbol " << Mod[3] << endl;
+        }
         fout.open(rank == 0 ? "Result.txt" : "/dev/null", std::ios::app);
         fout << setw(5) << snr << '\t' << setw(20) << TestFrame << '\t' << setw(15) << ErrorFrame << '\t' << setw(20) << ErrorBits << '\t' << setw(20)
              << FER << '\t' << setw(20) << BER << '\t' << setw(15) << LT3ErrBitFrame << '\t' << setw(15) << total_time << '\t' << endl;
         fout.close();
         if (rank == 0) {
-            /* reference main.cpp:183-186, :224-227: the demapper's own error rates.  The counters behind them are never
-             * incremented in the reference either (the ModCalErr call is commented out, CSimulate.cpp:129), so the row is zeros */
-            const unsigned long ModErrorBits = 0, ModErrorFrame = 0, ModErrorSymbol = 0;
-            const double ModBER = (double)ModErrorBits / ((double)TestFrame * (NmoinsK - _ShortenBits));
-            const double ModSER = (double)ModErrorSymbol / ((double)TestFrame * (NmoinsK - _ShortenBits) / p_simulation.mod_type);
-            const double ModFER = (double)ModErrorFrame / TestFrame;
+            /* reference main.cpp:224-227.  Without --prefec the counters behind the row stay zero, as in the reference, where the
+             * ModCalErr call is commented out (CSimulate.cpp:129); with --prefec they are lnsfaid's pre-FEC counters */
             ofstream demodout("demod.txt", std::ios::app);
             demodout << setw(5) << snr << '\t' << setw(20) << ModFER << '\t' << setw(20) << ModBER << '\t' << setw(20) << ModSER << '\t' << endl;
         }

@@ -97,6 +97,11 @@ SYMBOLS = {
     "lnsfaid_demap_packed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_float, C.c_void_p]),
     "lnsfaid_demap_host": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_float, C.c_void_p]),
     "lnsfaid_demap_packed_host": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_float, C.c_void_p]),
+    "lnsfaid_prefec_errors_host": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_int32,
+                                             C.POINTER(C.c_uint64)]),
+    "lnsfaid_prefec_errors_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_uint64)]),
+    "lnsfaid_frontend_set_prefec": (C.c_int, [C.c_void_p, C.c_int32]),
+    "lnsfaid_frontend_prefec_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int32]),
     "lnsfaid_frontend_set_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "lnsfaid_frontend_input_bits": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "lnsfaid_code_parity_inverse": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_size_t]),
@@ -261,6 +266,31 @@ def demap_packed_host(n_var, n_check, interleave, rx, n_groups, mod_type, scale,
     return _demap_host("lnsfaid_demap_packed_host", True, n_var, n_check, interleave, rx, n_groups, mod_type, scale, lib)
 
 
+PREFEC_INFO, PREFEC_CODEWORD = 1, 2
+
+
+def prefec_errors_host(n_var, n_check, interleave, rx, n_groups, mod_type, sent, scope, lib=None, out=None):
+    """lnsfaid_prefec_errors_host: received symbols (float32, the rx format of include/lnsfaid.h) against the sent bits (int8, the
+    encoder's output layout, or None for the all-zero codeword) -> [TestFrame, ModErrorFrame, ModErrorBits, ModErrorSymbol], added
+    to `out` (four numbers) when it is given"""
+    import numpy as np
+    lib = lib or load()
+    rx = np.ascontiguousarray(rx, dtype=np.float32)
+    floats = n_groups * GROUP * n_var * (1 if mod_type == 1 else 2) // max(mod_type, 1)
+    if rx.size != floats:
+        raise ValueError("lnsfaid_prefec_errors_host: rx has %d floats, %d groups of mod_type %d take %d" % (rx.size, n_groups, mod_type, floats))
+    if sent is not None:
+        sent = np.ascontiguousarray(sent, dtype=np.int8)
+        if sent.size != n_groups * GROUP * n_var:
+            raise ValueError("lnsfaid_prefec_errors_host: sent has %d bytes, not %d" % (sent.size, n_groups * GROUP * n_var))
+    counters = (C.c_uint64 * 4)(*([0, 0, 0, 0] if out is None else [int(x) for x in out]))
+    rc = lib.lnsfaid_prefec_errors_host(n_var, n_check, interleave, rx.ctypes.data, n_groups, mod_type,
+                                        sent.ctypes.data if sent is not None else None, scope, counters)
+    if rc != 0:
+        raise ValueError("lnsfaid_prefec_errors_host failed: %d" % rc)
+    return list(counters)
+
+
 class Decoder:
     """Thin RAII wrapper over lnsfaid_create / lnsfaid_decode* / lnsfaid_destroy."""
 
@@ -381,6 +411,24 @@ class Decoder:
     def demap_packed_device(self, d_rx_ptr, n_groups, mod_type, scale, d_llr4_ptr):
         self._check(self.lib.lnsfaid_demap_packed_device(self.ctx, d_rx_ptr, n_groups, mod_type, scale, d_llr4_ptr),
                     "lnsfaid_demap_packed_device")
+
+    def prefec_errors_device(self, d_rx_ptr, n_groups, mod_type, d_sent_ptr, scope, out=None):
+        """lnsfaid_prefec_errors_device: symbols and sent bits on the device (d_sent_ptr None: the all-zero codeword) ->
+        [TestFrame, ModErrorFrame, ModErrorBits, ModErrorSymbol], added to `out` when it is given"""
+        counters = (C.c_uint64 * 4)(*([0, 0, 0, 0] if out is None else [int(x) for x in out]))
+        self._check(self.lib.lnsfaid_prefec_errors_device(self.ctx, d_rx_ptr, n_groups, mod_type, d_sent_ptr, scope, counters),
+                    "lnsfaid_prefec_errors_device")
+        return list(counters)
+
+    def frontend_set_prefec(self, scope):
+        """lnsfaid_frontend_set_prefec: 0 = off, PREFEC_INFO / PREFEC_CODEWORD = count in every later front-end call"""
+        self._check(self.lib.lnsfaid_frontend_set_prefec(self.ctx, scope), "lnsfaid_frontend_set_prefec")
+
+    def frontend_prefec_counters(self, reset=False, out=None):
+        """lnsfaid_frontend_prefec_counters: the accumulator of the fused counting, added to `out` when it is given"""
+        counters = (C.c_uint64 * 4)(*([0, 0, 0, 0] if out is None else [int(x) for x in out]))
+        self._check(self.lib.lnsfaid_frontend_prefec_counters(self.ctx, counters, 1 if reset else 0), "lnsfaid_frontend_prefec_counters")
+        return list(counters)
 
     def encode(self, info, n_groups):
         """info: numpy int8 0/1, [32][K] per group.  Returns the encoder output, [32][K] then [32][M] per group."""
