@@ -18,6 +18,7 @@
  */
 #include <hip/hip_runtime.h>
 
+#define LF4_DIRTY_CHECK(c, lane) layer0_dirty4_edgewise(c, lane) /* the ratchets on this file's layer blocks hold with this text only (lnsfaid_rows4.h) */
 #include "lnsfaid_rows4.h"
 
 /* what a clean syndrome does under the group rule (the decode loops of lnsfaid_rows4.h): a codeword on the group's front parks,

@@ -11,12 +11,13 @@
  * and every identity circulant rotation-free.  The per-lane edge table of the arg-min look-up stays a loaded value.
  *
  * The host launches this kernel only for a code whose zero-first tables equal the compiled ones entry by entry
- * (lf_decode4s_matches); every other code stays on lnsfaid_kernel4z.hip.  Everything but the layered iteration is the text of that
- * file.  Built for DecodeMethods 1..5 like it.
+ * (lf_decode4s_matches); every other code stays on lnsfaid_kernel4z.hip.  Everything but the layered iteration and the decision
+ * points' cheap "certainly dirty" test (dirty4s) is the text of that file.  Built for DecodeMethods 1..5 like it.
  */
 #include <hip/hip_runtime.h>
 
 #define LF4_MAIN_STEP main_step4s
+#define LF4_DIRTY_CHECK(c, lane) dirty4s(lane)
 #include "lnsfaid_rows4.h"
 #include "lnsfaid_static50.h"
 
@@ -37,9 +38,24 @@ extern "C" int lf_decode4s_matches(const LfDevCode* code)
     return 1;
 }
 
+/* ---- the cheap "certainly dirty" test of a decision point on the compiled tables, two stages of straight-line code (DESIGN.md
+ * 3.1f): the row parity of the layer with the most identity circulants, and only where that finds nothing the parity of layer 0, the
+ * layer lnsfaid_rows4.h's layer0_dirty4 asks - so whatever that test proves dirty, this one does.  The comment lines in the assembly
+ * delimit what tests/test_decision_point_isa.py walks. ---- */
+__device__ __forceinline__ bool dirty4s(int lane)
+{
+    const SwLds lds = SwLds();
+    asm volatile("; lf4s check stage 1");
+    const uint32_t w1 = sw50_row_parity<SW50_CHECK_LAYER>(lds, (uint32_t)lane);
+    if (__ballot((w1 & 0x80808080u) != 0u) != 0ull) return true;
+    asm volatile("; lf4s check stage 2");
+    const uint32_t w0 = sw50_row_parity<0>(lds, (uint32_t)lane);
+    return __ballot((w0 & 0x80808080u) != 0u) != 0ull;
+}
+
 /* layer BR of the iteration: main_step4z's loop body with BR a constant */
 template <int METHOD, int BR>
-__device__ __forceinline__ void layer4s(const LfDevCode* gc, SwRegs& R, const SwLds& lds, const SwParams& p, const SwK& K, int lane, bool fresh,
+__device__ __forceinline__ void layer4s(const uint32_t (*zsb)[32], SwRegs& R, const SwLds& lds, const SwParams& p, const SwK& K, int lane, bool fresh,
                                         const uint32_t* sP, bool have_par, bool lme, uint32_t& tabv)
 {
     typedef Sw50Tab<BR> Tab;
@@ -47,7 +63,7 @@ __device__ __forceinline__ void layer4s(const LfDevCode* gc, SwRegs& R, const Sw
      * address and rotate amounts) is computed in each of them, not kept alive - spilled - from one to the other */
     asm volatile("; lf4s layer %1" : "+v"(lane) : "n"(BR));
     uint32_t tabn = 0u;
-    if (BR + 1 < SW50_LAYERS) tabn = gc->zsbplain[BR + 1][lane & 31]; /* next layer's edge table, a layer ahead of its use */
+    if (BR + 1 < SW50_LAYERS) tabn = zsb[BR + 1][lane & 31]; /* next layer's edge table, a layer ahead of its use */
     uint32_t rowpar = 0;
     if (have_par) { /* syndrome bits of rows lane + 64 k of this layer as byte masks */
 #pragma unroll
@@ -92,10 +108,16 @@ __device__ __forceinline__ void main_step4s(CCode c, CCfg f, const LfDevCode* gc
     p.ef_tables = f->ef >= 1;
     if (LF4_OMS(METHOD)) sw_oms_tables(p);
     const SwLds lds = SwLds();
-    uint32_t tabv = gc->zsbplain[0][lane & 31];
+    /* the arg-min tables of all layers behind ONE base register, the layer in the loads' offset field.  The base is made per
+     * iteration (an opaque zero added): as twelve loop-invariant addresses the compiler keeps twelve register pairs alive
+     * through the whole loop, and the scalar registers of the decode loop are spilled around them */
+    uint32_t z = 0u;
+    asm volatile("" : "+s"(z));
+    const uint32_t (*zsb)[32] = (const uint32_t (*)[32])((const char*)gc->zsbplain + z);
+    uint32_t tabv = zsb[0][lane & 31];
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("; lf4s layers begin");
-#define LF4S_LAYER(BR) layer4s<METHOD, BR>(gc, R, lds, p, K, lane, fresh, sP, have_par, lme, tabv);
+#define LF4S_LAYER(BR) layer4s<METHOD, BR>(zsb, R, lds, p, K, lane, fresh, sP, have_par, lme, tabv);
     LF4S_LAYER(0) LF4S_LAYER(1) LF4S_LAYER(2) LF4S_LAYER(3) LF4S_LAYER(4) LF4S_LAYER(5)
     LF4S_LAYER(6) LF4S_LAYER(7) LF4S_LAYER(8) LF4S_LAYER(9) LF4S_LAYER(10) LF4S_LAYER(11)
 #undef LF4S_LAYER
@@ -110,9 +132,19 @@ __device__ __forceinline__ void main_step4s(CCode c, CCfg f, const LfDevCode* gc
 
 /* ---- the decode kernel: lnsfaid_decode4_kernel<METHOD, true, false> of lnsfaid_kernel4.hip, statement for statement ---- */
 template <int METHOD>
-__global__ __launch_bounds__(LF_T4, 2) void lnsfaid_decode4s_kernel(LfKernelArgs a)
+__global__ __launch_bounds__(LF_T4, 2) void lnsfaid_decode4s_kernel(LfKernelArgs a_)
 {
     constexpr bool RM = true, EF2 = false; /* the instances this kernel is built for (the decode loops of lnsfaid_rows4.h name them) */
+    /* the two pointers the decode loop uses, split off the kernel arguments: the compiler holds those as ONE tuple of sixteen
+     * registers, spilled and reloaded whole wherever a field of it is wanted (twice inside layer 0).  An opaque zero is added
+     * instead of constraining the pointers themselves, which would lose their address space (flat loads in every layer). */
+    LfKernelArgs a = a_;
+    {
+        uint32_t z = 0u;
+        asm volatile("" : "+s"(z));
+        a.code = (const LfDevCode*)((const char*)a_.code + z);
+        a.cfg = (const LfDevCfg*)((const char*)a_.cfg + z);
+    }
     extern __shared__ __align__(16) unsigned char smem[];
     CCode c = (CCode)a.code;
     CCfg f = (CCfg)a.cfg;

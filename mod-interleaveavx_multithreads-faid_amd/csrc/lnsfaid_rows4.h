@@ -61,8 +61,7 @@ __device__ __forceinline__ void copy_out(uint32_t* __restrict__ dst, const uint3
     }
 }
 
-/* hard decision En > 0 on the biased bytes (En + 120 >= 121): bit 7 of every byte of x + 7 */
-__device__ __forceinline__ uint32_t hard_flags(uint32_t x) { return x + 0x07070707u; }
+__device__ __forceinline__ uint32_t hard_flags(uint32_t x) { return sw_hard_flags(x); } /* En > 0: bit 7 of every byte */
 
 /* ---- bit plane from the interleaved En image: hard decision (CDecoder_FAID.cpp:299, :6416-6419) or, with CONF, the 2B1C
  * confidence bit |En| >= thr (CDecoder_FAID_2B1C.cpp:6132-6136).  Lane d holds variable nodes d, d + 64, d + 128, d + 192 of a
@@ -123,8 +122,21 @@ __device__ __forceinline__ void build_plane4(CCode c, uint32_t* plane, int thr, 
 }
 
 /* ---- cheap "certainly dirty" test (DecodeMethod 2, see lnsfaid_kernels.hip): parity of the lane's four rows of layer 0
- * straight from En; the XOR of the hard-decision flags is bit 7 of the XOR of the flag words. */
+ * straight from En (sw_row_parity, lnsfaid_swar.h): any unsatisfied row proves the codeword dirty. */
+static_assert(SW_MAX_DEG == LF_MAX_DEG, "sw_row_parity reads whole rows of LfDevCode's tables");
 __device__ __forceinline__ bool layer0_dirty4(CCode c, int lane)
+{
+    uint32_t acc = sw_row_parity(SwLds(), c->s4tab[0], c->cbtab[0], c->deg[0], (uint32_t)lane);
+    /* the word is complete HERE: without this the scalar registers of lnsfaid_kernel4z.hip's layer loop are allocated differently
+     * and a byte constant is re-made inside every degree-23 layer block (one instruction above tests/test_zero_shift_isa.py) */
+    asm volatile("" : "+v"(acc));
+    return __ballot((acc & 0x80808080u) != 0u) != 0ull;
+}
+/* The same test with every table access and LDS read under `j < deg`, as all kernels had it: a basic block, a scalar load and a wait
+ * per edge and table (46 dependent round trips per decision point for the 50G-PON code).  lnsfaid_kernel4.hip stays on it
+ * (LF4_DIRTY_CHECK): with the straight-line text the register allocation of its layer blocks comes out two VALU instructions
+ * (spill reloads) above the ratchets of tests/test_layer_trip_count.py, pinned or not. */
+__device__ __forceinline__ bool layer0_dirty4_edgewise(CCode c, int lane)
 {
     const int deg = c->deg[0];
     const uint32_t tid4 = (uint32_t)lane << 2;
@@ -384,9 +396,14 @@ __device__ __forceinline__ void regs_clear(SwRegs& R)
  * LF4_STAGE_INPUT: the codeword's LLRs from the reference's fixInput layout into the interleaved En image (the LDS);
  * LF4_LAYERED_LOOP: the layered iterations from decision point prog on; LF4_ENTER_BF: the bit-flipping stage's entry when the
  * layered loop ran out; LF4_BF_LOOPS: the bit-flipping iterations.  parked = true when the codeword stopped clean at prog.
- * LF4_MAIN_STEP: the layered iteration the loop runs, main_step4 unless the including file names its own (lnsfaid_kernel4z.hip). ---- */
+ * LF4_MAIN_STEP: the layered iteration the loop runs, main_step4 unless the including file names its own (lnsfaid_kernel4z.hip).
+ * LF4_DIRTY_CHECK(c, lane): the cheap "certainly dirty" test in front of the syndrome stage, layer0_dirty4 unless the including
+ * file names its own (lnsfaid_kernel4s.hip: on compile-time tables; lnsfaid_kernel4.hip: layer0_dirty4_edgewise). ---- */
 #ifndef LF4_MAIN_STEP
 #define LF4_MAIN_STEP main_step4
+#endif
+#ifndef LF4_DIRTY_CHECK
+#define LF4_DIRTY_CHECK(c, lane) layer0_dirty4(c, lane)
 #endif
 #define LF4_STAGE_INPUT() \
         /* input staging (CDecoder_FAID.cpp:217-255): lane l of group g is information row l of the [32][K] block followed by                             \
@@ -464,7 +481,7 @@ _Pragma("unroll")                                                               
             /* behind the group's front (the snapshot shows a lane parked beyond this point) the group is known to go on, and                                                                            \
              * outside the window nothing else reads the syndrome: a catching-up codeword skips the stage altogether */                                                                                  \
             const bool must_know = needs_checksums || LF4_ON_FRONT;                                                                                                                                      \
-            if (must_know && (needs_checksums || !layer0_dirty4(c, tid_i))) {                                                                                                                            \
+            if (must_know && (needs_checksums || !LF4_DIRTY_CHECK(c, tid_i))) {                                                                                                                          \
                 build_plane4<false>(c, sHard, 0, tid_i);                                                                                                                                                 \
                 int unsat;                                                                                                                                                                               \
                 if (RM || syn_cache_fits(c->nbr)) { /* (RM: a code of up to LF4_RM_LAYERS layers always fits) all table entries of the walk loaded together: one memory round trip, not one per round */ \

@@ -68,6 +68,54 @@ struct SwTabStatic<Sw50Tab<BR>> {
     static constexpr int nz = Sw50Tab<BR>::NZ;
 };
 
+/* ---- the decision points' cheap "certainly dirty" test on the compile-time tables.  Any unsatisfied row proves
+ * the codeword dirty, so the parity of ONE layer's rows is a sufficient condition that spares the plane build and the full
+ * syndrome.  The cheapest layer to ask is the one with the most identity circulants: an identity edge is one read from the
+ * lane's own dword of its block column, no address arithmetic, no rotation. */
+constexpr int sw50_most_identities()
+{
+    constexpr Sw50Code c = sw50_build();
+    int best = 0;
+    for (int br = 1; br < SW50_LAYERS; ++br)
+        if (c.layer[br].nz > c.layer[best].nz) best = br;
+    return best;
+}
+#define SW50_CHECK_LAYER sw50_most_identities()
+
+/* Parity of the lane's four rows (lane + 64 k in byte k) of layer BR straight from the En image: bit 7 of byte k of the result is
+ * set when row lane + 64 k is unsatisfied under the hard decision En > 0 (bit 7 of En + 120 + 7); the other bits mean nothing.
+ * Straight-line: all reads from the address register 4 * lane (identity edges) or the literal-shift address (the others), the block
+ * column in the offset field; then, the last read first (LDS returns in order: one wait covers all), flags and a three-input XOR
+ * per two edges. */
+template <int BR>
+SW_FN uint32_t sw50_row_parity(const SwLds& lds, uint32_t lane)
+{
+    typedef Sw50Tab<BR> Tab;
+    constexpr int DEG = Tab::DEG, NZ = Tab::NZ;
+    const Tab tab = Tab();
+    const uint32_t tid4 = lane << 2;
+    uint32_t ad[DEG], rq[DEG], ld[DEG];
+#pragma unroll
+    for (int j = 0; j < DEG; ++j) {
+        const uint32_t x4 = tid4 + tab.s4(j);
+        ad[j] = j < NZ ? tid4 : x4 & 0xfcu;
+        rq[j] = j < NZ ? 0u : x4 >> 8;
+    }
+    SW_SCHED_FENCE();
+#pragma unroll
+    for (int j = 0; j < DEG; ++j) ld[j] = lds.rd32(ad[j], tab.cb256(j));
+    SW_SCHED_FENCE();
+    uint32_t acc = 0;
+#pragma unroll
+    for (int j = DEG - 1; j >= 0; j -= 2) {
+        const uint32_t fa = sw_hard_flags(j < NZ ? ld[j] : sw_alignbyte(ld[j], ld[j], rq[j]));
+        if (j == 0) { acc ^= fa; break; }
+        const uint32_t fb = sw_hard_flags(j - 1 < NZ ? ld[j - 1] : sw_alignbyte(ld[j - 1], ld[j - 1], rq[j - 1]));
+        acc = sw_bitop3<SW_TT_XOR3>(acc, fa, fb);
+    }
+    return acc;
+}
+
 /* every layer's immediate offset fits the DS instructions' 16-bit field, and the identity edges are the 69 the matrix has */
 constexpr bool sw50_check()
 {

@@ -290,6 +290,35 @@ struct SwLds {
 /* LDS byte position of variable node v (index inside the code word) in the interleaved image */
 SW_FN uint32_t sw_en_pos(uint32_t v) { return (v & ~255u) | ((v & 63u) << 2) | ((v >> 6) & 3u); }
 
+/* hard decision En > 0 on the biased bytes (En + 120 >= 121): bit 7 of every byte of x + 7 */
+SW_FN uint32_t sw_hard_flags(uint32_t x) { return x + 0x07070707u; }
+
+/* ---- the decision points' cheap "certainly dirty" test on run-time tables: parity of the lane's four rows
+ * (lane + 64 k in byte k) of a layer straight from En; the XOR of the hard-decision flags is bit 7 of the XOR of the flag words,
+ * the other bits of the result mean nothing.  s4row / cbrow: the layer's rows of LfDevCode's s4tab / cbtab, SW_MAX_DEG entries
+ * each, the ones beyond the degree 0.  ALL entries are loaded and all reads made, whatever the degree: the tables then arrive in
+ * a few wide scalar loads behind one wait, and the code is straight-line (an unused entry reads the lane's own dword of block
+ * column 0: a valid address); only the XOR looks at the degree.  With `j < deg` around the table accesses the compiler, which does
+ * not speculate a load, gave every edge a basic block, a scalar load and a wait of its own. */
+template <class Row> /* pointer to uint32_t: the device's tables sit in the constant address space */
+SW_FN uint32_t sw_row_parity(const SwLds& lds, Row s4row, Row cbrow, int deg, uint32_t lane)
+{
+    const uint32_t tid4 = lane << 2;
+    uint32_t x4[SW_MAX_DEG], ad[SW_MAX_DEG], d[SW_MAX_DEG];
+    /* all addresses, then all reads, then the arithmetic: one LDS round trip instead of one per circulant */
+#pragma unroll
+    for (int j = 0; j < SW_MAX_DEG; ++j) { x4[j] = tid4 + s4row[j]; ad[j] = (x4[j] & 0xfcu) | cbrow[j]; }
+    SW_SCHED_FENCE();
+#pragma unroll
+    for (int j = 0; j < SW_MAX_DEG; ++j) d[j] = lds.rd32(ad[j]);
+    SW_SCHED_FENCE();
+    uint32_t acc = 0;
+#pragma unroll
+    for (int j = SW_MAX_DEG - 1; j >= 0; --j) /* the last read first: LDS returns in order, one wait covers all */
+        acc ^= j < deg ? sw_hard_flags(sw_alignbyte(d[j], d[j], x4[j] >> 8)) : 0u;
+    return acc;
+}
+
 /* DecodeMethods whose rows follow Decode_OMS (1, 3, 4) / use the plain sign and no upper clamp on t (those and NMS, 0) */
 #define SW_OMS(M) ((M) == 1 || (M) == 3 || (M) == 4)
 #define SW_MINSUM(M) ((M) == 0 || SW_OMS(M))
