@@ -397,6 +397,64 @@ int lnsfaid_prefec_errors_device(lnsfaid_ctx* ctx, const float* d_rx, size_t n_g
 int lnsfaid_frontend_set_prefec(lnsfaid_ctx* ctx, int32_t scope);
 int lnsfaid_frontend_prefec_counters(lnsfaid_ctx* ctx, uint64_t out[4], int32_t reset);
 
+/* ---- error-frame capture -------------------------------------------------------------------------------
+ * The collect-flag branch of CLDPC::CalculateErrors (CLDPC.cpp:4877-4983) for buffers that stay on the device: the frames with
+ * wrong information bits come back as ordered, compact records, nothing else leaves the device.  One definition for both entry
+ * points:
+ *   fixInput     the decoder's input, the layout of lnsfaid_decode ([32][K] then [32][M] per group, group g at byte
+ *                g * 32 * n_var).  NULL is allowed: the LLR section of every payload is then zero.
+ *   decodedBits  the decoder's output, the layout of lnsfaid_decode ([32][n_var] per group).
+ *   sent         the sent frames in the layout of CLDPC::outputBits, of lnsfaid_encode* and of the `sent` of the pre-FEC counters:
+ *                [32][K] then [32][M] per group, group g at byte g * 32 * n_var.  NULL means the all-zero codeword.
+ *   error frame  a decision is wrong when its byte differs from the sent byte (the rule of lnsfaid_count_errors).  Frame m of group
+ *                g - codeword 32 * g + m of the batch - is an error frame when at least one of its K information decisions is wrong
+ *                (the reference's condition); wrong parity decisions alone do not make one.
+ *   order        the error frames of the batch are numbered 0, 1, ... in ascending codeword index.  A call stores error frames
+ *                skip .. skip + capacity - 1 of that numbering, in that order.  *found = the error frames of the whole batch,
+ *                whatever skip and capacity are; *stored = min(capacity, max(found - skip, 0)).  The outputs are a pure function
+ *                of the inputs: nothing depends on the order in which the device happened to run its workgroups.  A caller pages
+ *                through a batch by calling again with skip advanced by *stored until skip reaches *found.
+ *   records[i]   the i-th stored error frame.
+ *   payload      payload + i * 3 * n_var holds three sections of n_var bytes, each in code-bit order k = 0 .. n_var - 1:
+ *                [0, n_var)           the frame's LLRs: fixInput[g][m * K + k] for k < K, else fixInput[g][32 * K + m * M + (k - K)]
+ *                [n_var, 2 n_var)     decodedBits[g][m * n_var + k]
+ *                [2 n_var, 3 n_var)   the sent bits, indexed like the LLRs
+ *                Exactly *stored records and *stored * 3 * n_var payload bytes are written and nothing outside them.
+ *   out          may be NULL.  Otherwise the call ADDS exactly what lnsfaid_count_errors* adds for the same decodedBits and the
+ *                information part of sent (TestFrame, ErrorFrame, ErrorBits, LT3ErrBitFrame): a caller that captures needs no
+ *                separate counter pass, and *found equals the ErrorFrame it added.
+ * Rules: n_groups == 0 is a no-op that sets *found = *stored = 0 (every buffer may be NULL); capacity == 0 counts only (records
+ * and payload may be NULL).  LNSFAID_E_INVAL, with no output touched: a NULL ctx (device call) or a code shape outside
+ * 0 < n_check < n_var (host call); with n_groups > 0 a NULL decodedBits, found or stored, and with capacity > 0 too a NULL records
+ * or payload; n_groups > max_groups (device call). */
+typedef struct lnsfaid_error_record {
+    uint32_t codeword;      /* index in the batch: 32 * group + frame */
+    uint32_t info_errors;   /* wrong information bits, always > 0 */
+    uint32_t parity_errors; /* wrong parity bits */
+    uint32_t reserved;      /* 0 */
+} lnsfaid_error_record;
+/* The three inputs are device pointers of any alignment (more alignment only widens the loads, it never changes a byte); records,
+ * payload, found, stored and out are host pointers - records are rare and end in files.  The call stages through device buffers of
+ * the context with min(capacity, 32 * n_groups) slots (allocated at the first call, grown on demand, freed by lnsfaid_destroy) and
+ * copies back only the stored records.  A pure read of its inputs.  Queues on the context's stream and returns when the outputs
+ * are complete; no synchronisation by the caller is needed after a preceding *_device call. */
+int lnsfaid_capture_errors_device(lnsfaid_ctx* ctx, const int8_t* d_fixInput, const int8_t* d_decodedBits,
+                                  const int8_t* d_sent, size_t n_groups, size_t skip, size_t capacity,
+                                  lnsfaid_error_record* records, int8_t* payload,
+                                  uint64_t* found, uint64_t* stored, uint64_t out[4]);
+/* Host only, no context, no GPU (like lnsfaid_prefec_errors_host): the reference the device path is tested against. */
+int lnsfaid_capture_errors_host(int32_t n_var, int32_t n_check, const int8_t* fixInput, const int8_t* decodedBits,
+                                const int8_t* sent, size_t n_groups, size_t skip, size_t capacity,
+                                lnsfaid_error_record* records, int8_t* payload,
+                                uint64_t* found, uint64_t* stored, uint64_t out[4]);
+/* The device copy of the frames lnsfaid_frontend_set_frames / lnsfaid_frontend_random_frames left for the device front-end (the
+ * `sent` of the calls above and of lnsfaid_prefec_errors_device), beside lnsfaid_frontend_input_bits; NULL while no frames are
+ * set (the front-end then sends its codeword argument, or the all-zero codeword).  The pointer holds the frames of the n_streams
+ * streams they were set for, and lnsfaid_frontend_device sends them only in calls with codeword == NULL and at most that many
+ * streams: it is the `sent` of such a call's output, for at most n_streams groups.  A front-end call with more streams, or with a
+ * codeword, sent that codeword (NULL: all-zero) in every frame - pass what it was given, not this pointer. */
+int lnsfaid_frontend_sent_bits(lnsfaid_ctx* ctx, const int8_t** d_outputBits);
+
 /* ---- systematic encoder and device frame source (replaces CLDPC::Encode, reference CLDPC.cpp:68-155) ---------------
  * H = [A | B], B = the last n_check columns.  The parity bits of information bits u are p = B^-1 A u; B^-1 is derived from the
  * code table (the reference's GenMatrix is not shipped) lazily, at the first lnsfaid_encode* / lnsfaid_frontend_random_frames

@@ -56,6 +56,10 @@ extern "C" hipError_t lf_launch_frontend(const uint32_t* d_seeds, const unsigned
 extern "C" hipError_t lf_launch_prefec(const float* d_rx, const int8_t* d_sent, size_t n_groups, int mod_type, int n_var, int n_check,
                                        int interleave, int scope, unsigned long long* d_out, hipStream_t stream);
 extern "C" hipError_t lf_launch_prefec_fold(unsigned long long* d_frame_cnt, size_t n_streams, unsigned long long* d_acc, hipStream_t stream);
+extern "C" hipError_t lf_launch_capture(const int8_t* d_fix, const int8_t* d_decoded, const int8_t* d_sent, size_t n_groups, int n_var,
+                                        int n_check, uint32_t skip, uint32_t cap, uint2* d_cnt, uint32_t* d_slots,
+                                        lnsfaid_error_record* d_records, int8_t* d_payload, unsigned long long* d_meta,
+                                        unsigned long long* d_out, hipStream_t stream);
 extern "C" hipError_t lf_launch_demap(const float* d_rx, size_t n_groups, int mod_type, float scale, int n_var, int n_check,
                                       int interleave, int packed, void* d_out, hipStream_t stream);
 extern "C" hipError_t lf_frontend_fastpath_scan(double* d_out2, hipStream_t stream);
@@ -165,6 +169,14 @@ struct lnsfaid_ctx {
     int fe_prefec = 0;             /* scope of the fused pre-FEC counting (lnsfaid_frontend_set_prefec), 0 = off */
     unsigned long long* d_fe_prefec_frames = nullptr; /* [max_groups * 32] wrong bits | symbols << 32 per frame of one call */
     unsigned long long* d_fe_prefec_acc = nullptr;    /* the four counters, read only by lnsfaid_frontend_prefec_counters */
+    /* error-frame capture (lnsfaid_capture.hip), allocated at the first lnsfaid_capture_errors_device call */
+    uint2* d_cap_cnt = nullptr;                /* [max_groups * 32] wrong information / parity decisions per codeword */
+    unsigned long long* d_cap_meta = nullptr;  /* found, stored, then the four counters of the call: one copy brings all six back */
+    unsigned long long* h_cap_meta = nullptr;  /* pinned */
+    size_t cap_slots = 0;                      /* slots the three buffers below hold: grown on demand */
+    uint32_t* d_cap_slots = nullptr;           /* codeword of every slot */
+    lnsfaid_error_record* d_cap_records = nullptr;
+    int8_t* d_cap_payload = nullptr;           /* 3 * n_var bytes per slot */
     /* encoder (lnsfaid_encoder.hip): support of B^-1's first rows, derived at the first encode / random-frames call */
     int enc_state = 0;                      /* 0: not derived yet, 1: on the device, LNSFAID_E_CODE: parity part singular */
     uint32_t* d_enc_sup = nullptr;          /* entries b * z + c, block row after block row */
@@ -388,6 +400,9 @@ extern "C" void lnsfaid_destroy(lnsfaid_ctx* ctx)
     (void)hipFree(ctx->d_fe_frames); (void)hipFree(ctx->d_fe_input);
     (void)hipFree(ctx->d_enc_sup); (void)hipFree(ctx->d_enc_off); (void)hipFree(ctx->d_fe_keys);
     (void)hipFree(ctx->d_fe_prefec_frames); (void)hipFree(ctx->d_fe_prefec_acc);
+    (void)hipFree(ctx->d_cap_cnt); (void)hipFree(ctx->d_cap_meta);
+    if (ctx->h_cap_meta) (void)hipHostFree(ctx->h_cap_meta);
+    (void)hipFree(ctx->d_cap_slots); (void)hipFree(ctx->d_cap_records); (void)hipFree(ctx->d_cap_payload);
     if (ctx->h_remaining) (void)hipHostFree(ctx->h_remaining);
     if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -1241,6 +1256,13 @@ extern "C" int lnsfaid_frontend_input_bits(lnsfaid_ctx* ctx, const int8_t** d_in
     return LNSFAID_OK;
 }
 
+extern "C" int lnsfaid_frontend_sent_bits(lnsfaid_ctx* ctx, const int8_t** d_outputBits)
+{
+    if (!ctx || !d_outputBits) return LNSFAID_E_INVAL;
+    *d_outputBits = ctx->fe_frames_streams ? ctx->d_fe_frames : nullptr;
+    return LNSFAID_OK;
+}
+
 extern "C" int lnsfaid_io_buffers(lnsfaid_ctx* ctx, int8_t** d_fixInput, int8_t** d_decodedBits, lnsfaid_group_stats** d_stats)
 {
     if (!ctx) return LNSFAID_E_INVAL;
@@ -1877,6 +1899,118 @@ extern "C" int lnsfaid_prefec_errors_host(int32_t n_var, int32_t n_check, int32_
         for (int m = 0; m < 32; ++m) { out[1] += frame_bits[m] ? 1u : 0u; out[2] += frame_bits[m]; }
         out[3] += sym_err;
     }
+    return LNSFAID_OK;
+}
+
+/* ---- error-frame capture (lnsfaid_capture.hip) ---------------------------------------------- */
+static int capture_rules(size_t n_groups, size_t capacity, const int8_t* decodedBits, const lnsfaid_error_record* records,
+                         const int8_t* payload, const uint64_t* found, const uint64_t* stored)
+{
+    if (n_groups == 0) return LNSFAID_OK;
+    if (!decodedBits || !found || !stored) return LNSFAID_E_INVAL;
+    if (capacity > 0 && (!records || !payload)) return LNSFAID_E_INVAL;
+    return LNSFAID_OK;
+}
+
+/* staging for `slots` records; what a smaller call left is kept */
+static int capture_buffers(lnsfaid_ctx* ctx, size_t slots)
+{
+    /* each on its own: a call after a failed allocation asks again for what is still missing */
+    if (!ctx->d_cap_cnt) HIP_TRY(hipMalloc(&ctx->d_cap_cnt, ctx->max_groups * LNSFAID_GROUP * sizeof(uint2)));
+    if (!ctx->d_cap_meta) HIP_TRY(hipMalloc(&ctx->d_cap_meta, 6 * sizeof(unsigned long long)));
+    if (!ctx->h_cap_meta) HIP_TRY(hipHostMalloc((void**)&ctx->h_cap_meta, 6 * sizeof(unsigned long long), hipHostMallocDefault));
+    if (slots > ctx->cap_slots) {
+        { const int rcw = stream_wait(ctx); if (rcw) return rcw; } /* nothing queued may still use the old buffers */
+        (void)hipFree(ctx->d_cap_slots); (void)hipFree(ctx->d_cap_records); (void)hipFree(ctx->d_cap_payload);
+        ctx->d_cap_slots = nullptr; ctx->d_cap_records = nullptr; ctx->d_cap_payload = nullptr;
+        ctx->cap_slots = 0;
+        HIP_TRY(hipMalloc(&ctx->d_cap_slots, slots * sizeof(uint32_t)));
+        HIP_TRY(hipMalloc(&ctx->d_cap_records, slots * sizeof(lnsfaid_error_record)));
+        HIP_TRY(hipMalloc(&ctx->d_cap_payload, slots * 3 * (size_t)ctx->n_var));
+        ctx->cap_slots = slots;
+    }
+    return LNSFAID_OK;
+}
+
+extern "C" int lnsfaid_capture_errors_device(lnsfaid_ctx* ctx, const int8_t* d_fixInput, const int8_t* d_decodedBits, const int8_t* d_sent,
+                                             size_t n_groups, size_t skip, size_t capacity, lnsfaid_error_record* records,
+                                             int8_t* payload, uint64_t* found, uint64_t* stored, uint64_t out[4])
+{
+    if (!ctx || n_groups > ctx->max_groups) return LNSFAID_E_INVAL;
+    { const int rc = capture_rules(n_groups, capacity, d_decodedBits, records, payload, found, stored); if (rc) return rc; }
+    if (n_groups == 0) {
+        if (found) *found = 0;
+        if (stored) *stored = 0;
+        return LNSFAID_OK;
+    }
+    const size_t n_cw = n_groups * LNSFAID_GROUP; /* 32 * max_groups codewords fit 32 bits: create refuses more */
+    if (n_cw > 0xffffffffull) return LNSFAID_E_INVAL;
+    const size_t slots = capacity < n_cw ? capacity : n_cw;
+    HIP_TRY(hipSetDevice(ctx->device));
+    { const int rc = capture_buffers(ctx, slots); if (rc) return rc; }
+    HIP_TRY(hipMemsetAsync(ctx->d_cap_meta, 0, 6 * sizeof(unsigned long long), ctx->stream));
+    /* no error frame has a rank of n_cw or more: a larger skip stores as little */
+    HIP_TRY(lf_launch_capture(d_fixInput, d_decodedBits, d_sent, n_groups, ctx->n_var, ctx->n_check, (uint32_t)(skip < n_cw ? skip : n_cw),
+                              (uint32_t)slots, ctx->d_cap_cnt, ctx->d_cap_slots, ctx->d_cap_records, ctx->d_cap_payload, ctx->d_cap_meta,
+                              ctx->d_cap_meta + 2, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->h_cap_meta, ctx->d_cap_meta, 6 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    { const int rcw = stream_wait(ctx); if (rcw) return rcw; } /* the one wait that tells the host how much to copy */
+    const size_t n_found = (size_t)ctx->h_cap_meta[0], n_stored = (size_t)ctx->h_cap_meta[1];
+    if (n_stored > slots) return LNSFAID_E_INTERNAL;
+    if (n_stored) {
+        HIP_TRY(hipMemcpyAsync(records, ctx->d_cap_records, n_stored * sizeof(lnsfaid_error_record), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(payload, ctx->d_cap_payload, n_stored * 3 * (size_t)ctx->n_var, hipMemcpyDeviceToHost, ctx->stream));
+        { const int rcw = stream_wait(ctx); if (rcw) return rcw; }
+    }
+    *found = n_found;
+    *stored = n_stored;
+    if (out) for (int i = 0; i < 4; ++i) out[i] += ctx->h_cap_meta[2 + i];
+    return LNSFAID_OK;
+}
+
+/* The definition of include/lnsfaid.h taken literally (no HIP call): the reference of the device path */
+extern "C" int lnsfaid_capture_errors_host(int32_t n_var, int32_t n_check, const int8_t* fixInput, const int8_t* decodedBits,
+                                           const int8_t* sent, size_t n_groups, size_t skip, size_t capacity, lnsfaid_error_record* records,
+                                           int8_t* payload, uint64_t* found, uint64_t* stored, uint64_t out[4])
+{
+    if (n_check <= 0 || n_var <= n_check) return LNSFAID_E_INVAL;
+    { const int rc = capture_rules(n_groups, capacity, decodedBits, records, payload, found, stored); if (rc) return rc; }
+    if (n_groups == 0) {
+        if (found) *found = 0;
+        if (stored) *stored = 0;
+        return LNSFAID_OK;
+    }
+    const size_t N = (size_t)n_var, M = (size_t)n_check, K = N - M;
+    uint64_t n_found = 0, n_stored = 0, add[4] = { 0, 0, 0, 0 };
+    for (size_t g = 0; g < n_groups; ++g) {
+        const int8_t* sg = sent ? sent + g * 32 * N : nullptr;
+        const int8_t* fg = fixInput ? fixInput + g * 32 * N : nullptr;
+        add[0] += LNSFAID_GROUP;
+        for (size_t m = 0; m < 32; ++m) {
+            const int8_t* d = decodedBits + (g * 32 + m) * N;
+            const size_t info_at = m * K, parity_at = 32 * K + m * M;
+            uint32_t info = 0, parity = 0;
+            for (size_t k = 0; k < K; ++k) info += d[k] != (sg ? sg[info_at + k] : 0) ? 1u : 0u;
+            if (info == 0) continue;
+            add[1] += 1; add[2] += info; add[3] += info < 3 ? 1u : 0u;
+            const uint64_t rank = n_found++;
+            if (rank < skip || rank - skip >= capacity) continue;
+            for (size_t k = 0; k < M; ++k) parity += d[K + k] != (sg ? sg[parity_at + k] : 0) ? 1u : 0u;
+            lnsfaid_error_record& r = records[n_stored];
+            r.codeword = (uint32_t)(g * 32 + m); r.info_errors = info; r.parity_errors = parity; r.reserved = 0;
+            int8_t* p = payload + n_stored * 3 * N;
+            for (size_t k = 0; k < N; ++k) {
+                const size_t at = k < K ? info_at + k : parity_at + (k - K);
+                p[k] = fg ? fg[at] : (int8_t)0;
+                p[N + k] = d[k];
+                p[2 * N + k] = sg ? sg[at] : (int8_t)0;
+            }
+            ++n_stored;
+        }
+    }
+    *found = n_found;
+    *stored = n_stored;
+    if (out) for (int i = 0; i < 4; ++i) out[i] += add[i];
     return LNSFAID_OK;
 }
 

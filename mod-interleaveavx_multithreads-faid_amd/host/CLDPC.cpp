@@ -1,5 +1,6 @@
 #include "CLDPC.h"
 
+#include <algorithm>
 #include <fstream>
 #include <vector>
 
@@ -203,10 +204,53 @@ void CLDPC::Decode_FAID_2B1C() { decode_with(5); }
 int CLDPC::Decode_OMSBF() { decode_with(3); return m_stats[0].bf_iterations; }
 int CLDPC::Decode_OMS_DTBF() { decode_with(4); return m_stats[0].bf_iterations; }
 
-/* The collect-flag dump of reference CLDPC.cpp:4877-4983: one record per frame with information-bit errors appended to
- * errorindex.txt (block / index of every wrong information and parity bit), errorfloat.txt (channel output and 4-bit
- * input of the frame) and errordecode.txt (decoded, sent information and sent code bits).  bpskinput has the fixInput
- * layout ([32][K] then [32][M] per group); the reference's Z is Profile.txt's. */
+/* One record of the collect-flag dump of reference CLDPC.cpp:4877-4983, appended to errorindex.txt (block / index of every wrong
+ * information and parity bit), errorfloat.txt (channel output and 4-bit input of the frame) and errordecode.txt (decoded, sent
+ * information and sent code bits).  dec: the frame's N decisions; in: its K information bits; out_, chr_, flt_: the sent code bits,
+ * the decoder input and the channel output as an information part (K) and a parity part (M); flt_info == nullptr writes an empty
+ * ErrorFloat.  Returns false for a frame without a wrong information bit (nothing is written). */
+static bool write_error_record(int frame, int Z, int K, int M, const int8_t* dec, const int8_t* in, const int8_t* out_info,
+                               const int8_t* out_par, const int8_t* chr_info, const int8_t* chr_par, const float* flt_info,
+                               const float* flt_par)
+{
+    std::vector<int> bit_block, bit_index, chk_block, chk_index;
+    for (int j = 0; j < K; ++j)
+        if (dec[j] != in[j]) { bit_block.push_back(j / Z + 1); bit_index.push_back(j % Z); }
+    if (bit_block.empty()) return false;
+    for (int j = K; j < K + M; ++j)
+        if (dec[j] != out_par[j - K]) { chk_block.push_back(j / Z + 1); chk_index.push_back(j % Z); }
+    std::ofstream eout("errorindex.txt", std::ios::app), nout("errorfloat.txt", std::ios::app), dout("errordecode.txt", std::ios::app);
+    eout << "ErrorFrame: " << frame << std::endl << "ErrorBit Num: " << bit_block.size() << std::endl << "Errorbit Block: ";
+    for (int v : bit_block) eout << v << "\t";
+    eout << std::endl << "Errobit Index: ";
+    for (int v : bit_index) eout << v << "\t";
+    eout << std::endl << "Errorcheck Num: " << chk_block.size() << std::endl << "Errorcheck Block: ";
+    for (int v : chk_block) eout << v << "\t";
+    eout << std::endl << "Errorcheck Index: ";
+    for (int v : chk_index) eout << v << "\t";
+    eout << std::endl;
+    nout << "ErrorFloat=[ ";
+    if (flt_info) {
+        for (int j = 0; j < K; ++j) nout << flt_info[j] << "\t";
+        for (int j = 0; j < M; ++j) nout << flt_par[j] << "\t";
+    }
+    nout << "];" << std::endl << "ErrorChar=[";
+    for (int j = 0; j < K; ++j) nout << (int)chr_info[j] << "\t";
+    for (int j = 0; j < M; ++j) nout << (int)chr_par[j] << "\t";
+    nout << "];" << std::endl << std::endl;
+    dout << "Decodedbits=[";
+    for (int j = 0; j < K + M; ++j) dout << (int)dec[j] << "\t";
+    dout << "];" << std::endl << "inputbits=[";
+    for (int j = 0; j < K; ++j) dout << (int)in[j] << "\t";
+    dout << "];" << std::endl << "outputbits=[";
+    for (int j = 0; j < K; ++j) dout << (int)out_info[j] << "\t";
+    for (int j = 0; j < M; ++j) dout << (int)out_par[j] << "\t";
+    dout << "];" << std::endl << std::endl;
+    return true;
+}
+
+/* The collect-flag dump of reference CLDPC.cpp:4877-4983: one record per frame with information-bit errors.  bpskinput has the
+ * fixInput layout ([32][K] then [32][M] per group); the reference's Z is Profile.txt's. */
 void CLDPC::CollectErrors(const float* bpskinput, int Z)
 {
     if (m_device_io) {
@@ -215,50 +259,50 @@ void CLDPC::CollectErrors(const float* bpskinput, int Z)
         warned = true;
         return;
     }
-    const int N = m_N, K = m_K, M = m_M;
-    std::vector<int> bit_block, bit_index, chk_block, chk_index;
+    const size_t N = (size_t)m_N, K = (size_t)m_K, M = (size_t)m_M;
     for (int g = 0; g < m_groups; ++g) {
         const int8_t* dec = decodedBits + (size_t)g * 32 * N;
         const int8_t* in = inputBits + (size_t)g * 32 * K;
         const int8_t* outb = outputBits + (size_t)g * 32 * N;
         const int8_t* chr = fixInput + (size_t)g * 32 * N;
         const float* flt = bpskinput ? bpskinput + (size_t)g * 32 * N : nullptr;
-        for (int i = 0; i < 32; ++i) {
-            bit_block.clear(); bit_index.clear(); chk_block.clear(); chk_index.clear();
-            for (int j = 0; j < K; ++j)
-                if (dec[(size_t)i * N + j] != in[(size_t)i * K + j]) { bit_block.push_back(j / Z + 1); bit_index.push_back(j % Z); }
-            if (bit_block.empty()) continue;
-            for (int j = K; j < N; ++j)
-                if (dec[(size_t)i * N + j] != outb[(size_t)32 * K + (size_t)i * M + (j - K)]) { chk_block.push_back(j / Z + 1); chk_index.push_back(j % Z); }
-            std::ofstream eout("errorindex.txt", std::ios::app), nout("errorfloat.txt", std::ios::app), dout("errordecode.txt", std::ios::app);
-            eout << "ErrorFrame: " << i << std::endl << "ErrorBit Num: " << bit_block.size() << std::endl << "Errorbit Block: ";
-            for (int v : bit_block) eout << v << "\t";
-            eout << std::endl << "Errobit Index: ";
-            for (int v : bit_index) eout << v << "\t";
-            eout << std::endl << "Errorcheck Num: " << chk_block.size() << std::endl << "Errorcheck Block: ";
-            for (int v : chk_block) eout << v << "\t";
-            eout << std::endl << "Errorcheck Index: ";
-            for (int v : chk_index) eout << v << "\t";
-            eout << std::endl;
-            nout << "ErrorFloat=[ ";
-            if (flt) {
-                for (int j = 0; j < K; ++j) nout << flt[(size_t)i * K + j] << "\t";
-                for (int j = 0; j < M; ++j) nout << flt[(size_t)32 * K + (size_t)i * M + j] << "\t";
-            }
-            nout << "];" << std::endl << "ErrorChar=[";
-            for (int j = 0; j < K; ++j) nout << (int)chr[(size_t)i * K + j] << "\t";
-            for (int j = 0; j < M; ++j) nout << (int)chr[(size_t)32 * K + (size_t)i * M + j] << "\t";
-            nout << "];" << std::endl << std::endl;
-            dout << "Decodedbits=[";
-            for (int j = 0; j < N; ++j) dout << (int)dec[(size_t)i * N + j] << "\t";
-            dout << "];" << std::endl << "inputbits=[";
-            for (int j = 0; j < K; ++j) dout << (int)in[(size_t)i * K + j] << "\t";
-            dout << "];" << std::endl << "outputbits=[";
-            for (int j = 0; j < K; ++j) dout << (int)outb[(size_t)i * K + j] << "\t";
-            for (int j = 0; j < M; ++j) dout << (int)outb[(size_t)32 * K + (size_t)i * M + j] << "\t";
-            dout << "];" << std::endl << std::endl;
-        }
+        for (size_t i = 0; i < 32; ++i)
+            (void)write_error_record((int)i, Z, m_K, m_M, dec + i * N, in + i * K, outb + i * K, outb + 32 * K + i * M, chr + i * K,
+                                     chr + 32 * K + i * M, flt ? flt + i * K : nullptr, flt ? flt + 32 * K + i * M : nullptr);
     }
+}
+
+/* The same dump in device-resident mode (--device-collect): lnsfaid_capture_errors_device brings back the error frames of the last
+ * decode in ascending codeword order - the order of the loops above - page by page, so no frame is lost whatever their number. */
+void CLDPC::CollectErrorsDevice(size_t capacity, int Z, const std::function<bool(int, int, const int8_t*, float*)>& channel_floats)
+{
+    lnsfaid_ctx* ctx = m_last;
+    if (!ctx || !m_device_io) die("CollectErrorsDevice before a device decode", LNSFAID_E_INVAL);
+    int8_t *d_fix = nullptr, *d_out = nullptr;
+    const int8_t* d_sent = nullptr; /* NULL = all-zero codeword; the sent frames when frames are set */
+    int rc = lnsfaid_io_buffers(ctx, &d_fix, &d_out, nullptr);
+    if (!rc) rc = lnsfaid_frontend_sent_bits(ctx, &d_sent);
+    if (rc) die("lnsfaid_frontend_sent_bits", rc);
+    const size_t N = (size_t)m_N, K = (size_t)m_K;
+    const size_t slots = std::min(capacity, (size_t)m_groups * 32);
+    std::vector<lnsfaid_error_record> records(slots);
+    std::vector<int8_t> payload(slots * 3 * N);
+    std::vector<float> flt(N);
+    uint64_t found = 0, stored = 0, skip = 0;
+    do {
+        rc = lnsfaid_capture_errors_device(ctx, d_fix, d_out, d_sent, (size_t)m_groups, (size_t)skip, slots, records.data(), payload.data(),
+                                           &found, &stored, nullptr);
+        if (rc) die("lnsfaid_capture_errors_device", rc);
+        for (uint64_t i = 0; i < stored; ++i) {
+            const int8_t* chr = payload.data() + i * 3 * N;
+            const int8_t *dec = chr + N, *sent = chr + 2 * N;
+            const int group = (int)(records[i].codeword / 32), frame = (int)(records[i].codeword % 32);
+            const bool have = channel_floats && channel_floats(group, frame, sent, flt.data());
+            (void)write_error_record(frame, Z, m_K, m_M, dec, sent, sent, sent + K, chr, chr + K, have ? flt.data() : nullptr,
+                                     have ? flt.data() + K : nullptr);
+        }
+        skip += stored;
+    } while (stored > 0 && skip < found);
 }
 
 Statistic CLDPC::CalculateErrors()

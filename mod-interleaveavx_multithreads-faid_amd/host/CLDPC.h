@@ -12,6 +12,7 @@
 #define CLDPC_H
 #include <cstddef>
 #include <cstdint>
+#include <functional>
 
 #include "./Constants/Constants_SSE.h" /* generated: same macros and PosNoeudsVariable as the reference's header */
 #include "CEncoder.h"
@@ -60,6 +61,10 @@ public:
     /* collectflag == 1 part of the reference's CalculateErrors(bpskinput, charinput, collectflag) (CLDPC.h:169):
      * appends the error frames of the last decode to errorindex.txt / errorfloat.txt / errordecode.txt */
     void CollectErrors(const float* bpskinput, int Z);
+    /* --device-collect: the same records in device-resident mode, through lnsfaid_capture_errors_device in pages of `capacity`
+     * frames.  channel_floats(group, frame, sent code bits [N], out [N]) fills the frame's channel output in code-bit order for
+     * ErrorFloat and returns true, or returns false (the line then stays empty) */
+    void CollectErrorsDevice(size_t capacity, int Z, const std::function<bool(int, int, const int8_t*, float*)>& channel_floats);
 
     /* Device-resident mode (--device-frontend): the channel output of `m_groups` reference worker threads is
      * generated on the GPU straight into the decoder's input buffer, Decode_*() and CalculateErrors() then work on

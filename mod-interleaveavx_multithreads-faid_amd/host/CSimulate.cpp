@@ -135,6 +135,49 @@ void CSimulate::Run()
     std::vector<float> llr(device_frontend ? 0 : (size_t)m_streams * bits);
     std::vector<int> BFiters_((size_t)m_streams * 51, 0); /* per stream, reference CSimulate.cpp:99 */
     std::vector<uint32_t> states(3 * (size_t)m_streams);
+    /* a generator of the Wichmann-Hill triple n draws on: X <- X * a^n mod m */
+    auto jump = [](unsigned long x, unsigned long a, unsigned long m, uint64_t n) {
+        unsigned long r = 1, b = a % m; uint64_t e = n;
+        while (e) { if (e & 1) r = r * b % m; b = b * b % m; e >>= 1; }
+        return x % m * r % m;
+    };
+    /* max-log Demodulation of one symbol, every level stored as float (reference CModulate.cpp:273-362) */
+    auto demap = [half, fold](float re, float im, float* l) {
+        l[0] = re;
+        l[1] = im;
+        for (int n = 1; n < half; ++n) {
+            l[2 * n] = fabs(l[2 * n - 2]) - fold[n - 1];
+            l[2 * n + 1] = fabs(l[2 * n - 1]) - fold[n - 1];
+        }
+    };
+    /* --device-collect: the channel output of one frame of the call in flight, in code-bit order, for ErrorFloat.  The device keeps
+     * no float, but the stream's noise is reproducible: `states` holds every stream's generator state from before the call, frame m
+     * starts m * (N / Q) symbols of four draws each further on, and the host chain (modulate, CChannel, demap, de-interleave) runs on
+     * the frame's sent bits.  These are the HOST generator's floats: the device's double log / cos may differ from them in the last
+     * ulp.  A symbol that straddles two frames (N % Q != 0) leaves the line empty. */
+    auto channel_floats = [&](int s, int m, const int8_t* sent, float* out) {
+        if (N % Q != 0) return false;
+        const uint64_t skip = (uint64_t)m * (uint64_t)(N / Q) * 4u;
+        RandSeed rs;
+        rs.IX = jump(states[3 * (size_t)s], 249, 61967, skip);
+        rs.IY = jump(states[3 * (size_t)s + 1], 251, 63443, skip);
+        rs.IZ = jump(states[3 * (size_t)s + 2], 252, 63599, skip);
+        const float sigma_axis = (float)(sigma / sqrt(2)); /* reference CSimulate.cpp:126 */
+        for (int i = 0; i < N / Q; ++i) {
+            int idx_i = 0, idx_q = 0;
+            for (int u = 0; u < Q; ++u) { /* Modulation (reference CModulate.cpp:216-264) */
+                const int b = sent[code_bit(Q * i + u)];
+                if (u & 1) idx_q += b << (half - u / 2 - 1); else idx_i += b << (half - u / 2 - 1);
+            }
+            Complex8 rx; /* AWGNChannel (reference CChannel.cpp:90-97) */
+            rx.real = channel[s].Random_Norm(sigma_axis, rs) + axis[idx_i];
+            rx.imag = channel[s].Random_Norm(sigma_axis, rs) + axis[idx_q];
+            float l[8];
+            demap(rx.real, rx.imag, l);
+            for (int u = 0; u < Q; ++u) out[code_bit(Q * i + u)] = l[u];
+        }
+        return true;
+    };
     for (int call = 0; call < 50; ++call) {
         TestFrame += 32ul * m_streams;
         if (device_frontend) {
@@ -148,16 +191,10 @@ void CSimulate::Run()
             }
             ldpc->DeviceChannel(decode_method, states.data(), m_draws.data(), ModulationType, sigma, scale);
             const uint64_t n = ldpc->DrawsPerGroup(ModulationType);
-            for (int s = 0; s < m_streams; ++s) {
-                /* keep RS (the resume table of Temp.txt) where the host generator would be: X <- X * a^n mod m */
-                auto jump = [n](unsigned long x, unsigned long a, unsigned long m) {
-                    unsigned long r = 1, b = a % m; uint64_t e = n;
-                    while (e) { if (e & 1) r = r * b % m; b = b * b % m; e >>= 1; }
-                    return x % m * r % m;
-                };
-                channel[s].RS.IX = jump(channel[s].RS.IX, 249, 61967);
-                channel[s].RS.IY = jump(channel[s].RS.IY, 251, 63443);
-                channel[s].RS.IZ = jump(channel[s].RS.IZ, 252, 63599);
+            for (int s = 0; s < m_streams; ++s) { /* keep RS (the resume table of Temp.txt) where the host generator would be */
+                channel[s].RS.IX = jump(channel[s].RS.IX, 249, 61967, n);
+                channel[s].RS.IY = jump(channel[s].RS.IY, 251, 63443, n);
+                channel[s].RS.IZ = jump(channel[s].RS.IZ, 252, 63599, n);
             }
         }
 #pragma omp parallel for schedule(dynamic, 1) if (!device_frontend)
@@ -172,12 +209,7 @@ void CSimulate::Run()
                 ch.AWGNChannel(ModSeq.data() + (encode ? (size_t)s * sym : 0), (float)(sigma / sqrt(2))); /* reference CSimulate.cpp:126 */
                 for (size_t i = 0; i < bits / (size_t)Q; ++i) { /* max-log Demodulation, every level stored as float (CModulate.cpp:273-362) */
                     float l[8];
-                    l[0] = ch.SymbolSeq[i].real;
-                    l[1] = ch.SymbolSeq[i].imag;
-                    for (int n = 1; n < half; ++n) {
-                        l[2 * n] = fabs(l[2 * n - 2]) - fold[n - 1];
-                        l[2 * n + 1] = fabs(l[2 * n - 1]) - fold[n - 1];
-                    }
+                    demap(ch.SymbolSeq[i].real, ch.SymbolSeq[i].imag, l);
                     for (int u = 0; u < Q; ++u) { /* de-interleave: frame-major by code bit */
                         const size_t pos = (size_t)Q * i + u;
                         dst[pos / N * N + (size_t)code_bit((int)(pos % N))] = l[u];
@@ -229,7 +261,9 @@ void CSimulate::Run()
         ErrorFrame += Test.ErrorFrame;
         ErrorBits += Test.ErrorBits;
         LT3ErrBitFrame += Test.LT3ErrBitFrame;
-        if (collectflag == 1 && Test.ErrorFrame > 0) { /* reference CLDPC.cpp:4877: set by main once FER < 1e-5 */
+        if (collectflag == 1 && Test.ErrorFrame > 0 && device_frontend && device_collect) {
+            ldpc->CollectErrorsDevice((size_t)collect_capacity, m_Z, channel_floats);
+        } else if (collectflag == 1 && Test.ErrorFrame > 0) { /* reference CLDPC.cpp:4877: set by main once FER < 1e-5 */
             std::vector<float> fl; /* DeInterLeaveSeq layout: [32][K] then [32][M] per group */
             if (!device_frontend) {
                 fl.resize((size_t)m_streams * bits);

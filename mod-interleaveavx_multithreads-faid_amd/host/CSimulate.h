@@ -27,6 +27,8 @@ public:
     bool device_frontend = false; /* generate the channel output on the GPU (lnsfaid_frontend_device) */
     bool encode = false;          /* GenMsgSeq + Encode instead of FakeEncoder (reference FAKE_ENCODE 0) */
     bool device_encode = false;   /* random messages drawn and encoded on the device (needs device_frontend) */
+    bool device_collect = false;  /* --device-collect: with device_frontend, the collect-flag dumps through lnsfaid_capture_errors_device */
+    int collect_capacity = 256;   /* --collect-capacity: error frames per capture call (a page of 3 * N bytes each) */
     bool prefec = false;          /* --prefec: count the channel's hard decisions on the information bits (CModulate::ModCalErr) */
     /* {TestFrame, ModErrorFrame, ModErrorBits, ModErrorSymbol} of the point so far, under LNSFAID_PREFEC_INFO */
     unsigned long ModCounters[4] = { 0, 0, 0, 0 };

@@ -49,10 +49,12 @@ int main(int argc, char** argv)
     const char* run_id = "";
     int comm_timeout_s = 120;
     const int64_t started_at = (int64_t)time(nullptr);
-    bool device_frontend = false, force_collect = false, encode = false, device_encode = false, prefec = false;
+    bool device_frontend = false, force_collect = false, encode = false, device_encode = false, prefec = false, device_collect = false;
+    int collect_capacity = 256;
+    bool capacity_given = false;
     const char* profile = "Profile.txt";
     const char* resume = nullptr;
-    const char* usage = "usage: %s [--streams T] [--gpus G] [--profile Profile.txt] [--max-rounds R] [--device-frontend [--device-encode]] [--encode] [--prefec] [--collect] [--resume Temp.txt] [--early-stop group|codeword] [--ranks N --rank r --comm-file F [--run-id ID] [--comm-timeout S] [--device d]]\n";
+    const char* usage = "usage: %s [--streams T] [--gpus G] [--profile Profile.txt] [--max-rounds R] [--device-frontend [--device-encode] [--device-collect [--collect-capacity N]]] [--encode] [--prefec] [--collect] [--resume Temp.txt] [--early-stop group|codeword] [--ranks N --rank r --comm-file F [--run-id ID] [--comm-timeout S] [--device d]]\n";
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--streams") && i + 1 < argc) streams = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--gpus") && i + 1 < argc) gpus = atoi(argv[++i]);
@@ -73,12 +75,29 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--device-encode")) device_encode = true; /* messages drawn and encoded on the GPU (lnsfaid_frontend_random_frames) */
         else if (!strcmp(argv[i], "--early-stop") && i + 1 < argc && (!strcmp(argv[i + 1], "group") || !strcmp(argv[i + 1], "codeword")))
             g_early_stop = !strcmp(argv[++i], "codeword") ? LNSFAID_STOP_CODEWORD : LNSFAID_STOP_GROUP; /* lnsfaid_set_early_stop */
+        else if (!strcmp(argv[i], "--device-collect")) device_collect = true; /* the collect-flag dumps in device-resident mode (lnsfaid_capture_errors_device) */
+        else if (!strcmp(argv[i], "--collect-capacity") && i + 1 < argc) { collect_capacity = atoi(argv[++i]); capacity_given = true; } /* error frames per capture call */
         else if (!strcmp(argv[i], "--collect")) force_collect = true; /* collectflag = 1 from the first call (reference: once FER < 1e-5) */
         else { fprintf(stderr, usage, argv[0]); return 2; }
     }
     if (device_encode && !device_frontend) {
         fprintf(stderr, usage, argv[0]);
         fprintf(stderr, "--device-encode needs --device-frontend\n");
+        return 2;
+    }
+    if (device_collect && !device_frontend) {
+        fprintf(stderr, usage, argv[0]);
+        fprintf(stderr, "--device-collect needs --device-frontend\n");
+        return 2;
+    }
+    if (capacity_given && !device_collect) {
+        fprintf(stderr, usage, argv[0]);
+        fprintf(stderr, "--collect-capacity needs --device-collect\n");
+        return 2;
+    }
+    if (collect_capacity < 1) {
+        fprintf(stderr, usage, argv[0]);
+        fprintf(stderr, "--collect-capacity needs a positive number of frames\n");
         return 2;
     }
     if (streams < 1 || gpus < 1 || gpus > streams) { fprintf(stderr, "need 1 <= gpus <= streams\n"); return 2; }
@@ -107,6 +126,8 @@ int main(int argc, char** argv)
         simulate[g].encode = encode;
         simulate[g].device_encode = device_encode;
         simulate[g].prefec = prefec;
+        simulate[g].device_collect = device_collect;
+        simulate[g].collect_capacity = collect_capacity;
         simulate[g].Initial(p_simulation, first, last - first, multi ? device : g);
     }
     if (multi) { /* RCCL communicator of this run: the id travels through --comm-file */

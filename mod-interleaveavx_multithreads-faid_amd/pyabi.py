@@ -102,6 +102,11 @@ SYMBOLS = {
     "lnsfaid_prefec_errors_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p, C.c_int32, C.POINTER(C.c_uint64)]),
     "lnsfaid_frontend_set_prefec": (C.c_int, [C.c_void_p, C.c_int32]),
     "lnsfaid_frontend_prefec_counters": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int32]),
+    "lnsfaid_capture_errors_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t, C.c_void_p,
+                                                C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "lnsfaid_capture_errors_host": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
+                                              C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "lnsfaid_frontend_sent_bits": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "lnsfaid_frontend_set_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "lnsfaid_frontend_input_bits": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "lnsfaid_code_parity_inverse": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_size_t]),
@@ -291,6 +296,49 @@ def prefec_errors_host(n_var, n_check, interleave, rx, n_groups, mod_type, sent,
     return list(counters)
 
 
+def error_record_dtype():
+    """numpy view of lnsfaid_error_record"""
+    import numpy as np
+    return np.dtype([("codeword", np.uint32), ("info_errors", np.uint32), ("parity_errors", np.uint32), ("reserved", np.uint32)])
+
+
+def _capture(fn, what, n_var, n_groups, capacity, counters):
+    """runs fn(records pointer, payload pointer, found, stored, out) on buffers of min(capacity, 32 n_groups) slots"""
+    import numpy as np
+    slots = min(capacity, GROUP * n_groups)
+    records = np.zeros(slots, dtype=error_record_dtype())
+    payload = np.zeros((slots, 3, n_var), dtype=np.int8)
+    found, stored = C.c_uint64(), C.c_uint64()
+    out = None
+    if counters is not False and counters is not None:
+        out = (C.c_uint64 * 4)(*([0, 0, 0, 0] if counters is True else [int(x) for x in counters]))
+    rc = fn(records.ctypes.data if slots else None, payload.ctypes.data if slots else None, C.byref(found), C.byref(stored), out)
+    if rc != 0:
+        raise ValueError("%s failed: %d" % (what, rc))
+    res = (found.value, records[:stored.value], payload[:stored.value])
+    return res + (list(out),) if out is not None else res
+
+
+def capture_errors_host(n_var, n_check, fix_input, decoded, sent, n_groups, skip=0, capacity=256, counters=False, lib=None):
+    """lnsfaid_capture_errors_host: fix_input / sent int8 in the encoder's output layout or None, decoded int8 [n_groups * 32][n_var].
+    Returns (found, records as a structured numpy array, payload int8 [stored, 3, n_var][, counters]); counters: True, or four
+    numbers the call adds to"""
+    import numpy as np
+    lib = lib or load()
+    size = n_groups * GROUP * n_var
+    arrs = []
+    for name, a in (("fix_input", fix_input), ("decoded", decoded), ("sent", sent)):
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=np.int8)
+            if a.size != size:
+                raise ValueError("lnsfaid_capture_errors_host: %s has %d bytes, not %d" % (name, a.size, size))
+        arrs.append(a)
+    ptr = [a.ctypes.data if a is not None else None for a in arrs]
+    return _capture(lambda r, p, f, s, o: lib.lnsfaid_capture_errors_host(n_var, n_check, ptr[0], ptr[1], ptr[2], n_groups, skip, capacity,
+                                                                          r, p, f, s, o),
+                    "lnsfaid_capture_errors_host", n_var, n_groups, capacity, counters)
+
+
 class Decoder:
     """Thin RAII wrapper over lnsfaid_create / lnsfaid_decode* / lnsfaid_destroy."""
 
@@ -429,6 +477,22 @@ class Decoder:
         counters = (C.c_uint64 * 4)(*([0, 0, 0, 0] if out is None else [int(x) for x in out]))
         self._check(self.lib.lnsfaid_frontend_prefec_counters(self.ctx, counters, 1 if reset else 0), "lnsfaid_frontend_prefec_counters")
         return list(counters)
+
+    def capture_errors_device(self, d_fix_ptr, d_dec_ptr, d_sent_ptr, n_groups, skip=0, capacity=256, counters=False):
+        """lnsfaid_capture_errors_device: device pointers (d_fix_ptr / d_sent_ptr may be None).  Returns (found, records as a
+        structured numpy array, payload int8 [stored, 3, n_var][, counters]); counters: True, or four numbers the call adds to"""
+        try:
+            return _capture(lambda r, p, f, s, o: self.lib.lnsfaid_capture_errors_device(self.ctx, d_fix_ptr, d_dec_ptr, d_sent_ptr, n_groups,
+                                                                                         skip, capacity, r, p, f, s, o),
+                            "lnsfaid_capture_errors_device", self.code50.N, n_groups, capacity, counters)
+        except ValueError as e:
+            raise RuntimeError("%s (hip: %s)" % (e, self.lib.lnsfaid_last_hip_error().decode()))
+
+    def frontend_sent_bits(self):
+        """lnsfaid_frontend_sent_bits: device pointer of the frames set_frames / random_frames left, None while none are set"""
+        p = C.c_void_p()
+        self._check(self.lib.lnsfaid_frontend_sent_bits(self.ctx, C.byref(p)), "lnsfaid_frontend_sent_bits")
+        return p.value
 
     def encode(self, info, n_groups):
         """info: numpy int8 0/1, [32][K] per group.  Returns the encoder output, [32][K] then [32][M] per group."""
