@@ -455,6 +455,59 @@ int lnsfaid_capture_errors_host(int32_t n_var, int32_t n_check, const int8_t* fi
  * codeword, sent that codeword (NULL: all-zero) in every frame - pass what it was given, not this pointer. */
 int lnsfaid_frontend_sent_bits(lnsfaid_ctx* ctx, const int8_t** d_outputBits);
 
+/* ---- FEC status ------------------------------------------------------------------------------------------
+ * What a receiver can say about a decoded batch WITHOUT the sent bits - which codewords are uncorrectable, how many bits were
+ * corrected: the PON FEC performance counters - and, when the sent frames are at hand, which error frames were detected and which
+ * are miscorrections.  The decisions may come from any decode call of this library or from elsewhere.  One definition for every
+ * entry point, per codeword c = 32 g + m of the batch (frame m of group g):
+ *   bit          code bit k of the codeword is 1 when decodedBits[g][m * n_var + k] != 0 (the layout of lnsfaid_decode); packed form:
+ *                bit k % 32 of word c * n_var / 32 + k / 32 of bits (the layout of lnsfaid_decode_packed).
+ *   unsatisfied  the rows of H with an odd number of 1-bits among the row's variable nodes, over all n_var bits, the punctured tail
+ *                included: for one output the same number as lnsfaid_codeword_stats::unsatisfied.  0 means a codeword.
+ *   channel decision  of code bit k: x > 0 ? 1 : 0 with x = fixInput[g][m * K + k] for k < K, else fixInput[g][32 * K + m * M + (k - K)]
+ *                (the layout of lnsfaid_decode; the > 0 rule of the pre-FEC counters and of the decoder's output stage: 0 and every
+ *                negative value decide 0).  Packed form: x is the two's-complement nibble of llr4, 0x8 decides 0.
+ *   corrected    the k < n_var - puncture_tail at which the bit differs from the channel decision (the decoder never sees the LLRs of
+ *                the punctured tail).  fixInput == NULL: 0 for every codeword.
+ *   records[c]   {unsatisfied, corrected}, in batch order.  May be NULL.
+ *   out          may be NULL.  ADDED to; four words, so that lnsfaid_allreduce_counters sums them unchanged:
+ *                out[0] TotalCodewords          += 32 per group
+ *                out[1] UncorrectableCodewords  unsatisfied > 0
+ *                out[2] CorrectedCodewords      unsatisfied == 0 and corrected > 0
+ *                out[3] CorrectedBits           the sum of corrected over the codewords with unsatisfied == 0
+ *   vs_sent      may be NULL (sent is then not read).  ADDED to.  sent has the layout of the capture call's sent ([32][K] then [32][M]
+ *                per group, group g at byte g * 32 * n_var); only the K information bytes of a frame are read, and a decision is
+ *                wrong when its byte (packed form: its bit as a byte) differs from the sent byte: the rule of lnsfaid_count_errors.
+ *                sent == NULL means the all-zero codeword.
+ *                vs_sent[0] TestFrame             += 32 per group
+ *                vs_sent[1] ErrorFrame            a wrong information bit: what lnsfaid_count_errors* adds
+ *                vs_sent[2] UndetectedErrorFrame  a wrong information bit and unsatisfied == 0: a valid but wrong codeword
+ *                vs_sent[3] FalseAlarmFrame       no wrong information bit and unsatisfied > 0
+ * Every output is a pure function of the inputs.
+ * Rules: n_groups == 0 is a no-op (every buffer may be NULL).  LNSFAID_E_INVAL, with no output touched: a NULL ctx or code; a NULL
+ * decisions pointer with n_groups > 0; n_groups > max_groups (device forms); a code with n_var % 32 != 0 (packed forms); a code
+ * struct whose tables are missing or do not add up (host forms: 0 < n_check < n_var, 0 <= puncture_tail <= n_var, deg_rows summing
+ * to n_check, deg * deg_rows to n_edges, every pos_vn < n_var). */
+typedef struct lnsfaid_fec_record {
+    uint32_t unsatisfied; /* parity checks the decisions leave unsatisfied */
+    uint32_t corrected;   /* transmitted bits that differ from the channel's hard decision */
+} lnsfaid_fec_record;
+/* Host only, no context, no GPU: row by row from code->pos_vn, deg and deg_rows, so they serve any code the struct can describe
+ * (quasi-cyclic or not).  The reference the device forms are tested against.  Host pointers of any alignment. */
+int lnsfaid_fec_status_host(const lnsfaid_code* code, const int8_t* fixInput, const int8_t* decodedBits, const int8_t* sent,
+                            size_t n_groups, lnsfaid_fec_record* records, uint64_t out[4], uint64_t vs_sent[4]);
+int lnsfaid_fec_status_packed_host(const lnsfaid_code* code, const uint8_t* llr4, const uint32_t* bits, const int8_t* sent,
+                                   size_t n_groups, lnsfaid_fec_record* records, uint64_t out[4], uint64_t vs_sent[4]);
+/* The three inputs are device pointers of any alignment (more alignment only widens the loads, it never changes a count); d_records is
+ * a device pointer (4-byte aligned) or NULL; out and vs_sent are host pointers.  A pure read of its inputs.  Queues on the context's
+ * stream and returns when out / vs_sent are complete (the records are complete on the stream by then); no synchronisation by the
+ * caller is needed after a preceding *_device call.  The only read-back is one copy of the eight accumulators, which live on the
+ * context's device (allocated at the first call, freed by lnsfaid_destroy). */
+int lnsfaid_fec_status_device(lnsfaid_ctx* ctx, const int8_t* d_fixInput, const int8_t* d_decodedBits, const int8_t* d_sent,
+                              size_t n_groups, lnsfaid_fec_record* d_records, uint64_t out[4], uint64_t vs_sent[4]);
+int lnsfaid_fec_status_packed_device(lnsfaid_ctx* ctx, const uint8_t* d_llr4, const uint32_t* d_bits, const int8_t* d_sent,
+                                     size_t n_groups, lnsfaid_fec_record* d_records, uint64_t out[4], uint64_t vs_sent[4]);
+
 /* ---- systematic encoder and device frame source (replaces CLDPC::Encode, reference CLDPC.cpp:68-155) ---------------
  * H = [A | B], B = the last n_check columns.  The parity bits of information bits u are p = B^-1 A u; B^-1 is derived from the
  * code table (the reference's GenMatrix is not shipped) lazily, at the first lnsfaid_encode* / lnsfaid_frontend_random_frames

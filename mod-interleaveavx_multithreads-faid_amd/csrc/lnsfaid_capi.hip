@@ -60,6 +60,9 @@ extern "C" hipError_t lf_launch_capture(const int8_t* d_fix, const int8_t* d_dec
                                         int n_check, uint32_t skip, uint32_t cap, uint2* d_cnt, uint32_t* d_slots,
                                         lnsfaid_error_record* d_records, int8_t* d_payload, unsigned long long* d_meta,
                                         unsigned long long* d_out, hipStream_t stream);
+extern "C" hipError_t lf_launch_fec_status(const LfDevCode* d_code, int n_var, int packed, const void* d_fix, const void* d_decided,
+                                           const int8_t* d_sent, size_t n_groups, lnsfaid_fec_record* d_records, int want_sent,
+                                           unsigned long long* d_acc, hipStream_t stream);
 extern "C" hipError_t lf_launch_demap(const float* d_rx, size_t n_groups, int mod_type, float scale, int n_var, int n_check,
                                       int interleave, int packed, void* d_out, hipStream_t stream);
 extern "C" hipError_t lf_frontend_fastpath_scan(double* d_out2, hipStream_t stream);
@@ -177,6 +180,9 @@ struct lnsfaid_ctx {
     uint32_t* d_cap_slots = nullptr;           /* codeword of every slot */
     lnsfaid_error_record* d_cap_records = nullptr;
     int8_t* d_cap_payload = nullptr;           /* 3 * n_var bytes per slot */
+    /* FEC status (lnsfaid_fecstatus.hip), allocated at the first lnsfaid_fec_status*_device call */
+    unsigned long long* d_fec_acc = nullptr; /* out[4] then vs_sent[4] of the call in flight */
+    unsigned long long* h_fec_acc = nullptr; /* pinned */
     /* encoder (lnsfaid_encoder.hip): support of B^-1's first rows, derived at the first encode / random-frames call */
     int enc_state = 0;                      /* 0: not derived yet, 1: on the device, LNSFAID_E_CODE: parity part singular */
     uint32_t* d_enc_sup = nullptr;          /* entries b * z + c, block row after block row */
@@ -403,6 +409,8 @@ extern "C" void lnsfaid_destroy(lnsfaid_ctx* ctx)
     (void)hipFree(ctx->d_cap_cnt); (void)hipFree(ctx->d_cap_meta);
     if (ctx->h_cap_meta) (void)hipHostFree(ctx->h_cap_meta);
     (void)hipFree(ctx->d_cap_slots); (void)hipFree(ctx->d_cap_records); (void)hipFree(ctx->d_cap_payload);
+    (void)hipFree(ctx->d_fec_acc);
+    if (ctx->h_fec_acc) (void)hipHostFree(ctx->h_fec_acc);
     if (ctx->h_remaining) (void)hipHostFree(ctx->h_remaining);
     if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -2012,6 +2020,40 @@ extern "C" int lnsfaid_capture_errors_host(int32_t n_var, int32_t n_check, const
     *stored = n_stored;
     if (out) for (int i = 0; i < 4; ++i) out[i] += add[i];
     return LNSFAID_OK;
+}
+
+/* ---- FEC status (lnsfaid_fecstatus.hip; the host forms are in lnsfaid_tables.c) ------------------------- */
+static int fec_status_device(lnsfaid_ctx* ctx, int packed, const void* d_fix, const void* d_decided, const int8_t* d_sent, size_t n_groups,
+                             lnsfaid_fec_record* d_records, uint64_t out[4], uint64_t vs_sent[4])
+{
+    if (!ctx || n_groups > ctx->max_groups) return LNSFAID_E_INVAL;
+    if (packed && ctx->n_var % 32 != 0) return LNSFAID_E_INVAL;
+    if (n_groups == 0) return LNSFAID_OK;
+    if (!d_decided || n_groups * LNSFAID_GROUP > 0xffffffffull) return LNSFAID_E_INVAL;
+    HIP_TRY(hipSetDevice(ctx->device));
+    /* each on its own: a call after a failed allocation asks again for what is still missing */
+    if (!ctx->d_fec_acc) HIP_TRY(hipMalloc(&ctx->d_fec_acc, 8 * sizeof(unsigned long long)));
+    if (!ctx->h_fec_acc) HIP_TRY(hipHostMalloc((void**)&ctx->h_fec_acc, 8 * sizeof(unsigned long long), hipHostMallocDefault));
+    HIP_TRY(hipMemsetAsync(ctx->d_fec_acc, 0, 8 * sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(lf_launch_fec_status(ctx->d_code, ctx->n_var, packed, d_fix, d_decided, vs_sent ? d_sent : nullptr, n_groups, d_records,
+                                 vs_sent ? 1 : 0, ctx->d_fec_acc, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->h_fec_acc, ctx->d_fec_acc, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    { const int rcw = stream_wait(ctx); if (rcw) return rcw; }
+    if (out) for (int i = 0; i < 4; ++i) out[i] += ctx->h_fec_acc[i];
+    if (vs_sent) for (int i = 0; i < 4; ++i) vs_sent[i] += ctx->h_fec_acc[4 + i];
+    return LNSFAID_OK;
+}
+
+extern "C" int lnsfaid_fec_status_device(lnsfaid_ctx* ctx, const int8_t* d_fixInput, const int8_t* d_decodedBits, const int8_t* d_sent,
+                                         size_t n_groups, lnsfaid_fec_record* d_records, uint64_t out[4], uint64_t vs_sent[4])
+{
+    return fec_status_device(ctx, 0, d_fixInput, d_decodedBits, d_sent, n_groups, d_records, out, vs_sent);
+}
+
+extern "C" int lnsfaid_fec_status_packed_device(lnsfaid_ctx* ctx, const uint8_t* d_llr4, const uint32_t* d_bits, const int8_t* d_sent,
+                                                size_t n_groups, lnsfaid_fec_record* d_records, uint64_t out[4], uint64_t vs_sent[4])
+{
+    return fec_status_device(ctx, 1, d_llr4, d_bits, d_sent, n_groups, d_records, out, vs_sent);
 }
 
 /* ---- systematic encoder (lnsfaid_encoder.hip) ----------------------------------------------

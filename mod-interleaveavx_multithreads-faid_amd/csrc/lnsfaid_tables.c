@@ -168,3 +168,90 @@ int lnsfaid_cfg_ef_elimination(lnsfaid_cfg* cfg, int32_t mode)
     cfg->floor_iter_thresh = mode == 0 ? -1 : 6;
     return LNSFAID_OK;
 }
+
+/* ---- FEC status, host forms (include/lnsfaid.h "FEC status"): the definition taken literally, row by row from pos_vn ----
+ * No quasi-cyclic shortcut and no device code: the reference lnsfaid_fecstatus.hip is tested against. */
+#include <stdlib.h>
+
+static int fec_code_rules(const lnsfaid_code* c, int packed)
+{
+    if (!c || !c->pos_vn || !c->deg || !c->deg_rows) return LNSFAID_E_INVAL;
+    if (c->n_check <= 0 || c->n_var <= c->n_check || c->puncture_tail < 0 || c->puncture_tail > c->n_var || c->nb_degres < 0 ||
+        c->n_edges < 0)
+        return LNSFAID_E_INVAL;
+    if (packed && c->n_var % 32 != 0) return LNSFAID_E_INVAL;
+    long long rows = 0, edges = 0;
+    for (int d = 0; d < c->nb_degres; ++d) {
+        if (c->deg[d] < 0 || c->deg_rows[d] < 0) return LNSFAID_E_INVAL;
+        rows += c->deg_rows[d];
+        edges += (long long)c->deg[d] * c->deg_rows[d];
+    }
+    if (rows != c->n_check || edges != c->n_edges) return LNSFAID_E_INVAL;
+    for (long long e = 0; e < edges; ++e)
+        if ((int32_t)c->pos_vn[e] >= c->n_var) return LNSFAID_E_INVAL;
+    return LNSFAID_OK;
+}
+
+/* fix / dec: the int8 form's buffers, or llr4 / bits of the packed form (bytes of any alignment) */
+static int fec_status_host(const lnsfaid_code* code, int packed, const uint8_t* fix, const uint8_t* dec, const int8_t* sent,
+                           size_t n_groups, lnsfaid_fec_record* records, uint64_t out[4], uint64_t vs_sent[4])
+{
+    const int rc = fec_code_rules(code, packed);
+    if (rc) return rc;
+    if (n_groups == 0) return LNSFAID_OK;
+    if (!dec) return LNSFAID_E_INVAL;
+    const size_t N = (size_t)code->n_var, M = (size_t)code->n_check, K = N - M, limit = N - (size_t)code->puncture_tail;
+    uint8_t* bit = (uint8_t*)malloc(N);
+    if (!bit) return LNSFAID_E_NOMEM;
+    uint64_t add[4] = { 0, 0, 0, 0 }, vs[4] = { 0, 0, 0, 0 };
+    for (size_t g = 0; g < n_groups; ++g) {
+        for (size_t m = 0; m < LNSFAID_GROUP; ++m) {
+            const size_t c = g * LNSFAID_GROUP + m;
+            uint32_t corrected = 0, wrong = 0, unsatisfied = 0;
+            for (size_t k = 0; k < N; ++k) {
+                const size_t e = g * 32 * N + (k < K ? m * K + k : 32 * K + m * M + (k - K)); /* the element of fixInput and of sent */
+                int raw; /* the decision as lnsfaid_count_errors compares it */
+                if (packed) raw = (dec[(c * N + k) / 8] >> (k % 8)) & 1; /* little-endian words: bit k % 32 of word k / 32 */
+                else raw = (int8_t)dec[c * N + k];
+                bit[k] = raw != 0;
+                if (fix && k < limit) {
+                    int x;
+                    if (packed) { x = (fix[e / 2] >> (e % 2 ? 4 : 0)) & 15; x = x >= 8 ? x - 16 : x; }
+                    else x = (int8_t)fix[e];
+                    corrected += (uint32_t)((x > 0) != bit[k]);
+                }
+                if (vs_sent && k < K) wrong += (uint32_t)(raw != (sent ? (int)sent[e] : 0));
+            }
+            size_t e = 0;
+            for (int d = 0; d < code->nb_degres; ++d)
+                for (int r = 0; r < code->deg_rows[d]; ++r) {
+                    unsigned parity = 0;
+                    for (int j = 0; j < code->deg[d]; ++j) parity ^= bit[code->pos_vn[e++]];
+                    unsatisfied += parity;
+                }
+            if (records) { records[c].unsatisfied = unsatisfied; records[c].corrected = corrected; }
+            if (unsatisfied > 0) add[1] += 1;
+            else if (corrected > 0) { add[2] += 1; add[3] += corrected; }
+            if (wrong > 0) { vs[1] += 1; vs[2] += unsatisfied == 0; }
+            else vs[3] += unsatisfied > 0;
+        }
+        add[0] += LNSFAID_GROUP;
+        vs[0] += LNSFAID_GROUP;
+    }
+    free(bit);
+    if (out) for (int i = 0; i < 4; ++i) out[i] += add[i];
+    if (vs_sent) for (int i = 0; i < 4; ++i) vs_sent[i] += vs[i];
+    return LNSFAID_OK;
+}
+
+int lnsfaid_fec_status_host(const lnsfaid_code* code, const int8_t* fixInput, const int8_t* decodedBits, const int8_t* sent,
+                            size_t n_groups, lnsfaid_fec_record* records, uint64_t out[4], uint64_t vs_sent[4])
+{
+    return fec_status_host(code, 0, (const uint8_t*)fixInput, (const uint8_t*)decodedBits, sent, n_groups, records, out, vs_sent);
+}
+
+int lnsfaid_fec_status_packed_host(const lnsfaid_code* code, const uint8_t* llr4, const uint32_t* bits, const int8_t* sent,
+                                   size_t n_groups, lnsfaid_fec_record* records, uint64_t out[4], uint64_t vs_sent[4])
+{
+    return fec_status_host(code, 1, llr4, (const uint8_t*)bits, sent, n_groups, records, out, vs_sent);
+}

@@ -305,6 +305,20 @@ void CLDPC::CollectErrorsDevice(size_t capacity, int Z, const std::function<bool
     } while (stored > 0 && skip < found);
 }
 
+void CLDPC::FecStatusDevice(unsigned long counters[8])
+{
+    lnsfaid_ctx* ctx = m_last;
+    if (!ctx || !m_device_io) die("FecStatusDevice before a device decode", LNSFAID_E_INVAL);
+    int8_t *d_fix = nullptr, *d_out = nullptr;
+    const int8_t* d_sent = nullptr; /* NULL = all-zero codeword; the sent frames when frames are set */
+    int rc = lnsfaid_io_buffers(ctx, &d_fix, &d_out, nullptr);
+    if (!rc) rc = lnsfaid_frontend_sent_bits(ctx, &d_sent);
+    uint64_t out[4] = { 0, 0, 0, 0 }, vs[4] = { 0, 0, 0, 0 };
+    if (!rc) rc = lnsfaid_fec_status_device(ctx, d_fix, d_out, d_sent, (size_t)m_groups, nullptr, out, vs);
+    if (rc) die("lnsfaid_fec_status_device", rc);
+    for (int i = 0; i < 4; ++i) { counters[i] += (unsigned long)out[i]; counters[4 + i] += (unsigned long)vs[i]; }
+}
+
 Statistic CLDPC::CalculateErrors()
 {
     lnsfaid_ctx* ctx = m_last; /* the decoder that produced decodedBits (device mode: whose buffers hold them) */

@@ -83,6 +83,10 @@ public:
     /* --prefec with --device-frontend: the front-end counts its own channel decisions against the bits it sent
      * (lnsfaid_frontend_set_prefec: 0 = off, LNSFAID_PREFEC_INFO / _CODEWORD; clears the device accumulator) and
      * {TestFrame, ModErrorFrame, ModErrorBits, ModErrorSymbol} are ADDED to counters, once per CSimulate::Run */
+    /* --fec-status: lnsfaid_fec_status_device on the buffers of the last device decode, with the front-end's sent frames:
+     * {TotalCodewords, UncorrectableCodewords, CorrectedCodewords, CorrectedBits} are ADDED to counters[0 .. 3] and
+     * {TestFrame, ErrorFrame, UndetectedErrorFrame, FalseAlarmFrame} to counters[4 .. 7] */
+    void FecStatusDevice(unsigned long counters[8]);
     void DevicePrefec(int decode_method, int scope);
     void DevicePrefecCounters(int decode_method, unsigned long counters[4], bool reset);
 

@@ -67,6 +67,7 @@ void CSimulate::Configure(float Eb_N0, int _decode_method)
     decode_method = (_decode_method >= 1 && _decode_method <= 5) ? _decode_method : 0;
     TestFrame = ErrorFrame = ErrorBits = LT3ErrBitFrame = 0;
     ModCounters[0] = ModCounters[1] = ModCounters[2] = ModCounters[3] = 0;
+    for (unsigned long& c : FecCounters) c = 0;
 }
 
 void CSimulate::Run()
@@ -261,6 +262,7 @@ void CSimulate::Run()
         ErrorFrame += Test.ErrorFrame;
         ErrorBits += Test.ErrorBits;
         LT3ErrBitFrame += Test.LT3ErrBitFrame;
+        if (fec_status && device_frontend) ldpc->FecStatusDevice(FecCounters); /* the decode's buffers are still on the device */
         if (collectflag == 1 && Test.ErrorFrame > 0 && device_frontend && device_collect) {
             ldpc->CollectErrorsDevice((size_t)collect_capacity, m_Z, channel_floats);
         } else if (collectflag == 1 && Test.ErrorFrame > 0) { /* reference CLDPC.cpp:4877: set by main once FER < 1e-5 */

@@ -32,6 +32,9 @@ public:
     bool prefec = false;          /* --prefec: count the channel's hard decisions on the information bits (CModulate::ModCalErr) */
     /* {TestFrame, ModErrorFrame, ModErrorBits, ModErrorSymbol} of the point so far, under LNSFAID_PREFEC_INFO */
     unsigned long ModCounters[4] = { 0, 0, 0, 0 };
+    bool fec_status = false;      /* --fec-status: with device_frontend, lnsfaid_fec_status_device after every decode call */
+    /* its out[4] then vs_sent[4] of the point so far */
+    unsigned long FecCounters[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
     unsigned long sum_iterations = 0, sum_bf_iterations = 0, decoded_groups = 0;
 
     ~CSimulate();

@@ -49,12 +49,12 @@ int main(int argc, char** argv)
     const char* run_id = "";
     int comm_timeout_s = 120;
     const int64_t started_at = (int64_t)time(nullptr);
-    bool device_frontend = false, force_collect = false, encode = false, device_encode = false, prefec = false, device_collect = false;
+    bool device_frontend = false, force_collect = false, encode = false, device_encode = false, prefec = false, device_collect = false, fec_status = false;
     int collect_capacity = 256;
     bool capacity_given = false;
     const char* profile = "Profile.txt";
     const char* resume = nullptr;
-    const char* usage = "usage: %s [--streams T] [--gpus G] [--profile Profile.txt] [--max-rounds R] [--device-frontend [--device-encode] [--device-collect [--collect-capacity N]]] [--encode] [--prefec] [--collect] [--resume Temp.txt] [--early-stop group|codeword] [--ranks N --rank r --comm-file F [--run-id ID] [--comm-timeout S] [--device d]]\n";
+    const char* usage = "usage: %s [--streams T] [--gpus G] [--profile Profile.txt] [--max-rounds R] [--device-frontend [--device-encode] [--device-collect [--collect-capacity N]] [--fec-status]] [--encode] [--prefec] [--collect] [--resume Temp.txt] [--early-stop group|codeword] [--ranks N --rank r --comm-file F [--run-id ID] [--comm-timeout S] [--device d]]\n";
     for (int i = 1; i < argc; ++i) {
         if (!strcmp(argv[i], "--streams") && i + 1 < argc) streams = atoi(argv[++i]);
         else if (!strcmp(argv[i], "--gpus") && i + 1 < argc) gpus = atoi(argv[++i]);
@@ -76,6 +76,7 @@ int main(int argc, char** argv)
         else if (!strcmp(argv[i], "--early-stop") && i + 1 < argc && (!strcmp(argv[i + 1], "group") || !strcmp(argv[i + 1], "codeword")))
             g_early_stop = !strcmp(argv[++i], "codeword") ? LNSFAID_STOP_CODEWORD : LNSFAID_STOP_GROUP; /* lnsfaid_set_early_stop */
         else if (!strcmp(argv[i], "--device-collect")) device_collect = true; /* the collect-flag dumps in device-resident mode (lnsfaid_capture_errors_device) */
+        else if (!strcmp(argv[i], "--fec-status")) fec_status = true; /* FEC status of every decode call into fecstatus.txt (lnsfaid_fec_status_device) */
         else if (!strcmp(argv[i], "--collect-capacity") && i + 1 < argc) { collect_capacity = atoi(argv[++i]); capacity_given = true; } /* error frames per capture call */
         else if (!strcmp(argv[i], "--collect")) force_collect = true; /* collectflag = 1 from the first call (reference: once FER < 1e-5) */
         else { fprintf(stderr, usage, argv[0]); return 2; }
@@ -88,6 +89,11 @@ int main(int argc, char** argv)
     if (device_collect && !device_frontend) {
         fprintf(stderr, usage, argv[0]);
         fprintf(stderr, "--device-collect needs --device-frontend\n");
+        return 2;
+    }
+    if (fec_status && !device_frontend) {
+        fprintf(stderr, usage, argv[0]);
+        fprintf(stderr, "--fec-status needs --device-frontend\n");
         return 2;
     }
     if (capacity_given && !device_collect) {
@@ -128,6 +134,7 @@ int main(int argc, char** argv)
         simulate[g].prefec = prefec;
         simulate[g].device_collect = device_collect;
         simulate[g].collect_capacity = collect_capacity;
+        simulate[g].fec_status = fec_status;
         simulate[g].Initial(p_simulation, first, last - first, multi ? device : g);
     }
     if (multi) { /* RCCL communicator of this run: the id travels through --comm-file */
@@ -186,11 +193,19 @@ int main(int argc, char** argv)
         if (!demodout.is_open()) { cerr << "Cannot open demod.txt\n"; exit(EXIT_FAILURE); }
         demodout << setw(5) << " Eb/N0" << '\t' << setw(20) << " ModFER" << '\t' << setw(20) << "ModBER" << '\t' << setw(20) << "ModSER" << '\t' << endl;
     }
+    if (fec_status && rank == 0) {
+        ofstream fecout("fecstatus.txt", std::ios::app);
+        if (!fecout.is_open()) { cerr << "Cannot open fecstatus.txt\n"; exit(EXIT_FAILURE); }
+        fecout << setw(5) << "Eb/N0" << '\t' << setw(16) << "TotalCodewords" << '\t' << setw(24) << "UncorrectableCodewords" << '\t' << setw(20)
+               << "CorrectedCodewords" << '\t' << setw(16) << "CorrectedBits" << '\t' << setw(16) << "TestFrame" << '\t' << setw(12) << "ErrorFrame"
+               << '\t' << setw(22) << "UndetectedErrorFrame" << '\t' << setw(16) << "FalseAlarmFrame" << '\t' << endl;
+    }
     if (rank == 0) cout << setw(5) << "Eb_N0" << setw(20) << "TestFrame" << setw(15) << "ErrorFrame" << setw(20) << "ErrorBits" << setw(20) << "FER"
          << setw(20) << "BER" << setw(15) << "LT3ErrBitFrame" << setw(15) << "Time(s)" << setw(18) << "decode info Gb/s" << endl;
 
     for (float snr = p_simulation.snr_start; snr < p_simulation.snr_end; snr += p_simulation.snr_pass) {
         unsigned long TestFrame = 0, ErrorFrame = 0, ErrorBits = 0, LT3ErrBitFrame = 0;
+        unsigned long Fec[8] = { 0, 0, 0, 0, 0, 0, 0, 0 }; /* --fec-status: out[4] then vs_sent[4] of lnsfaid_fec_status_device */
         unsigned long Mod[4] = { 0, 0, 0, 0 }; /* --prefec: TestFrame, ModErrorFrame, ModErrorBits, ModErrorSymbol */
         double BER = 0, FER = 0, decode_s = 0;
         for (const char* name : { "iterCount.txt", "errorindex.txt", "errorfloat.txt", "errordecode.txt" }) { /* reference main.cpp:145-157 */
@@ -218,6 +233,13 @@ int main(int argc, char** argv)
                     for (int i = 0; i < 4; ++i) mod[i] += s.ModCounters[i];
                 if (multi) simulate[0].ldpc->AllReduceCounters(mod);
                 for (int i = 0; i < 4; ++i) Mod[i] += mod[i];
+            }
+            if (fec_status) { /* and for the FEC status: two sets of four words, each summed like the counters above */
+                unsigned long fec[8] = { 0, 0, 0, 0, 0, 0, 0, 0 };
+                for (auto& s : simulate)
+                    for (int i = 0; i < 8; ++i) fec[i] += s.FecCounters[i];
+                if (multi) { simulate[0].ldpc->AllReduceCounters(fec); simulate[0].ldpc->AllReduceCounters(fec + 4); }
+                for (int i = 0; i < 8; ++i) Fec[i] += fec[i];
             }
             BER = (double)(ErrorBits > 0 ? ErrorBits : 1) / ((double)TestFrame * (NmoinsK - _ShortenBits));
             FER = (double)(ErrorFrame > 0 ? ErrorFrame : 1) / TestFrame;
@@ -255,6 +277,12 @@ int main(int argc, char** argv)
         fout << setw(5) << snr << '\t' << setw(20) << TestFrame << '\t' << setw(15) << ErrorFrame << '\t' << setw(20) << ErrorBits << '\t' << setw(20)
              << FER << '\t' << setw(20) << BER << '\t' << setw(15) << LT3ErrBitFrame << '\t' << setw(15) << total_time << '\t' << endl;
         fout.close();
+        if (fec_status && rank == 0) {
+            ofstream fecout("fecstatus.txt", std::ios::app);
+            fecout << setw(5) << snr;
+            for (int i = 0; i < 8; ++i) fecout << '\t' << setw(16) << Fec[i];
+            fecout << '\t' << endl;
+        }
         if (rank == 0) {
             /* reference main.cpp:224-227.  Without --prefec the counters behind the row stay zero, as in the reference, where the
              * ModCalErr call is commented out (CSimulate.cpp:129); with --prefec they are lnsfaid's pre-FEC counters */

@@ -107,6 +107,14 @@ SYMBOLS = {
     "lnsfaid_capture_errors_host": (C.c_int, [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_size_t, C.c_size_t,
                                               C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "lnsfaid_frontend_sent_bits": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
+    "lnsfaid_fec_status_host": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                          C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "lnsfaid_fec_status_packed_host": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                 C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "lnsfaid_fec_status_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                            C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "lnsfaid_fec_status_packed_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p,
+                                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "lnsfaid_frontend_set_frames": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t]),
     "lnsfaid_frontend_input_bits": (C.c_int, [C.c_void_p, C.POINTER(C.c_void_p)]),
     "lnsfaid_code_parity_inverse": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_size_t]),
@@ -339,12 +347,60 @@ def capture_errors_host(n_var, n_check, fix_input, decoded, sent, n_groups, skip
                     "lnsfaid_capture_errors_host", n_var, n_groups, capacity, counters)
 
 
+def fec_record_dtype():
+    """numpy view of lnsfaid_fec_record"""
+    import numpy as np
+    return np.dtype([("unsatisfied", np.uint32), ("corrected", np.uint32)])
+
+
+def _fec_counters(v):
+    """None / False: not asked for; True: start from zero; four numbers: the call adds to them"""
+    if v is None or v is False:
+        return None
+    return (C.c_uint64 * 4)(*([0, 0, 0, 0] if v is True else [int(x) for x in v]))
+
+
+def _fec_status_host(fn_name, packed, code, fix, decided, sent, n_groups, records, out, vs_sent, lib):
+    import numpy as np
+    lib = lib or load()
+    n_var = code.n_var
+    sizes = (n_groups * GROUP * n_var // (2 if packed else 1), n_groups * GROUP * n_var // (32 if packed else 1), n_groups * GROUP * n_var)
+    types = (np.uint8, np.uint32, np.int8) if packed else (np.int8, np.int8, np.int8)
+    arrs = []
+    for name, a, size, t in zip(("fix_input", "decisions", "sent"), (fix, decided, sent), sizes, types):
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=t)
+            if a.size != size:
+                raise ValueError("%s: %s has %d elements, not %d" % (fn_name, name, a.size, size))
+        arrs.append(a)
+    ptr = [a.ctypes.data if a is not None else None for a in arrs]
+    rec = np.zeros(n_groups * GROUP, dtype=fec_record_dtype()) if records else None
+    o, v = _fec_counters(out), _fec_counters(vs_sent)
+    rc = getattr(lib, fn_name)(C.byref(code), ptr[0], ptr[1], ptr[2], n_groups, rec.ctypes.data if records else None, o, v)
+    if rc != 0:
+        raise ValueError("%s failed: %d" % (fn_name, rc))
+    return rec, (list(o) if o is not None else None), (list(v) if v is not None else None)
+
+
+def fec_status_host(code, fix_input, decoded, sent, n_groups, records=True, out=True, vs_sent=None, lib=None):
+    """lnsfaid_fec_status_host: code a Code struct (Code50GPON().code); fix_input / sent int8 in the encoder's output layout or None,
+    decoded int8 [n_groups * 32][n_var].  Returns (records as a structured numpy array or None, out or None, vs_sent or None); out /
+    vs_sent: True, four numbers the call adds to, or None / False for a NULL pointer"""
+    return _fec_status_host("lnsfaid_fec_status_host", False, code, fix_input, decoded, sent, n_groups, records, out, vs_sent, lib)
+
+
+def fec_status_packed_host(code, llr4, bits, sent, n_groups, records=True, out=True, vs_sent=None, lib=None):
+    """lnsfaid_fec_status_packed_host: llr4 uint8 (pack_llr4) or None, bits uint32 (the packed decisions), sent int8 or None"""
+    return _fec_status_host("lnsfaid_fec_status_packed_host", True, code, llr4, bits, sent, n_groups, records, out, vs_sent, lib)
+
+
 class Decoder:
     """Thin RAII wrapper over lnsfaid_create / lnsfaid_decode* / lnsfaid_destroy."""
 
     def __init__(self, code50, cfg, device=0, max_groups=64, lib=None):
         self.lib = lib or load()
         self.code50 = code50
+        self.device = device
         self.ctx = C.c_void_p()
         rc = self.lib.lnsfaid_create(C.byref(self.ctx), C.byref(code50.code), C.byref(cfg), device, max_groups)
         if rc != 0:
@@ -487,6 +543,34 @@ class Decoder:
                             "lnsfaid_capture_errors_device", self.code50.N, n_groups, capacity, counters)
         except ValueError as e:
             raise RuntimeError("%s (hip: %s)" % (e, self.lib.lnsfaid_last_hip_error().decode()))
+
+    def _fec_status_device(self, fn_name, d_fix_ptr, d_dec_ptr, d_sent_ptr, n_groups, records, out, vs_sent, d_records_ptr):
+        import numpy as np
+        rec = None
+        if records and d_records_ptr is None:
+            import torch
+            rec = torch.zeros(max(n_groups, 1) * GROUP * 2, dtype=torch.int32, device="cuda:%d" % self.device)
+            torch.cuda.synchronize()  # the zero fill runs on torch's stream, the call on the context's
+            d_records_ptr = rec.data_ptr()
+        o, v = _fec_counters(out), _fec_counters(vs_sent)
+        self._check(getattr(self.lib, fn_name)(self.ctx, d_fix_ptr, d_dec_ptr, d_sent_ptr, n_groups, d_records_ptr, o, v), fn_name)
+        if rec is not None:
+            # complete on the context's stream: the call has waited for it
+            rec = rec.cpu().numpy().view(np.uint32)[:n_groups * GROUP * 2].copy().view(fec_record_dtype())
+        return rec, (list(o) if o is not None else None), (list(v) if v is not None else None)
+
+    def fec_status_device(self, d_fix_ptr, d_dec_ptr, d_sent_ptr, n_groups, records=True, out=True, vs_sent=None, d_records_ptr=None):
+        """lnsfaid_fec_status_device: device pointers (d_fix_ptr / d_sent_ptr may be None).  Returns (records, out, vs_sent) like
+        fec_status_host; records=True stages them through a torch buffer and returns a structured numpy array, d_records_ptr hands the
+        call a device buffer of the caller's instead (records is then returned as None)"""
+        return self._fec_status_device("lnsfaid_fec_status_device", d_fix_ptr, d_dec_ptr, d_sent_ptr, n_groups, records, out, vs_sent,
+                                       d_records_ptr)
+
+    def fec_status_packed_device(self, d_llr4_ptr, d_bits_ptr, d_sent_ptr, n_groups, records=True, out=True, vs_sent=None,
+                                 d_records_ptr=None):
+        """lnsfaid_fec_status_packed_device: d_llr4_ptr (or None) / d_bits_ptr in the packed decode I/O formats, d_sent_ptr int8"""
+        return self._fec_status_device("lnsfaid_fec_status_packed_device", d_llr4_ptr, d_bits_ptr, d_sent_ptr, n_groups, records, out,
+                                       vs_sent, d_records_ptr)
 
     def frontend_sent_bits(self):
         """lnsfaid_frontend_sent_bits: device pointer of the frames set_frames / random_frames left, None while none are set"""
