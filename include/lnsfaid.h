@@ -633,6 +633,16 @@ int lnsfaid_select_zero_shift(lnsfaid_ctx* ctx, int32_t mode);
 int lnsfaid_zero_shift_groups(const lnsfaid_ctx* ctx, int32_t* groups, int32_t n);
 int lnsfaid_code_zero_shift_order(const lnsfaid_code* code, int32_t* groups, int32_t* order);
 
+/* The syndrome walk tables of the bit-flipping stage, without a GPU (for tests).  The stage flips block columns of weight
+ * col_weight (REGULAR_COL_WEIGHT) only, so the library walks their circulants in every iteration (`flipped`) and all others once
+ * when a codeword enters the stage (`fixed`); `full` is the walk of the layered stage's syndrome.  Per layer, slot and 32-row word
+ * k two uint32: the LDS byte addresses of the two hard-plane words (low / high 16 bits) and the bit offset; unused slots point at
+ * a word that holds zero.  full and fixed: [layers][24][8][2], flipped: [layers][info[2]][8][2].  info[0]: LDS byte offset of the
+ * hard plane, info[1]: of the zero word, info[2]: slots per layer of `flipped`, info[3]: 1 if every layer's circulants of such
+ * columns fit them (0: the stage walks `full` without register tables, and the contents of `flipped` are undefined: it lacks the
+ * circulants that did not fit), info[4]: number of such block columns.  Returns the number of layers or an error. */
+int lnsfaid_code_bf_walk(const lnsfaid_code* code, int32_t col_weight, uint32_t* full, uint32_t* flipped, uint32_t* fixed, int32_t* info);
+
 /* Workgroups (codewords) of the selected decode kernel a compute unit holds at once, from the HIP occupancy query, next to
  * what the kernel's LDS footprint alone would allow (50G-PON: 8 and 8).  A smaller first number means a build lost residency to
  * registers - about 40 % of the throughput for the one-wave-per-codeword kernel.  Also checks that the kernel has no static LDS

@@ -205,6 +205,23 @@ static int stream_wait(lnsfaid_ctx* ctx)
 /* ---- code analysis: PosNoeudsVariable -> circulants ------------------------------------------------- */
 static int weight_class(int w) { return w == 3 ? 0 : (w == 6 ? 1 : (w == 11 ? 2 : 3)); } /* CDecoder_FAID.cpp:692-705 */
 
+/* one entry of a syndrome walk table (LfDevCode::synw): word k of the 32-row words of circulant sb, hard plane at LDS offset hard0 */
+static uint2 syn_entry(uint32_t hard0, uint32_t sb, int k)
+{
+    const uint32_t cb = sb / (uint32_t)LF_Z, sh = sb % (uint32_t)LF_Z;
+    const uint32_t o = (32u * (uint32_t)k + sh) & 255u, q = o >> 5;
+    uint2 e;
+    e.x = (hard0 + 4u * (cb * 8u + q)) | ((hard0 + 4u * (cb * 8u + ((q + 1u) & 7u))) << 16);
+    e.y = o & 31u;
+    return e;
+}
+static uint2 syn_zero_entry(uint32_t zero)
+{
+    uint2 e;
+    e.x = zero | (zero << 16); e.y = 0;
+    return e;
+}
+
 static int build_code(const lnsfaid_code* code, LfDevCode* out)
 {
     memset(out, 0, sizeof(*out));
@@ -277,16 +294,8 @@ static int build_code(const lnsfaid_code* code, LfDevCode* out)
         if (lf_lds_bytes(N, nw, pw) > 0xffffu) return LNSFAID_E_CODE; /* 16-bit addresses */
         for (int br = 0; br < LF_MAX_BR; ++br)
             for (int j = 0; j < LF_MAX_DEG; ++j)
-                for (int k = 0; k < 8; ++k) {
-                    uint2 e; e.x = zero | (zero << 16); e.y = 0;
-                    if (br < nbr && j < out->deg[br]) {
-                        const uint32_t sb = out->circ[br][j].sb, cb = sb / (uint32_t)Z, sh = sb % (uint32_t)Z;
-                        const uint32_t o = (32u * (uint32_t)k + sh) & 255u, q = o >> 5;
-                        e.x = (hard0 + 4u * (cb * 8u + q)) | ((hard0 + 4u * (cb * 8u + ((q + 1u) & 7u))) << 16);
-                        e.y = o & 31u;
-                    }
-                    out->synw[br][j][k] = e;
-                }
+                for (int k = 0; k < 8; ++k)
+                    out->synw[br][j][k] = (br < nbr && j < out->deg[br]) ? syn_entry(hard0, out->circ[br][j].sb, k) : syn_zero_entry(zero);
     }
     for (int br = 0; br < nbr; ++br)
         for (int j = 0; j < out->deg[br]; ++j)
@@ -311,6 +320,24 @@ static void build_wcols(LfDevCode* code, int W)
             const int cb = (int)(code->circ[br][j].sb / LF_Z);
             if (code->col_weight[cb] == W && !seen[cb]) { seen[cb] = true; code->era_edges[br] |= 1u << j; }
         }
+    }
+    /* the syndrome walk split for the bit-flipping stage: circulants of weight-W block columns / all others, in row order */
+    const uint32_t hard0 = lf_lds_off_hard(code->n_var), zero = lf_lds_off_zero(code->n_var, code->n_words, code->p_words);
+    code->bfw_fits = 1;
+    for (int br = 0; br < LF_MAX_BR; ++br) {
+        int nw = 0, nc = 0;
+        for (int j = 0; br < code->nbr && j < code->deg[br]; ++j) {
+            const uint32_t sb = code->circ[br][j].sb;
+            const bool w = code->col_weight[sb / LF_Z] == W;
+            /* more than the table holds: synw_w stays incomplete and is not used - the stage takes the uncached walk of synw */
+            if (w && nw == 2 * LF_BFW_JP) { code->bfw_fits = 0; continue; }
+            for (int k = 0; k < 8; ++k) (w ? code->synw_w[br][nw] : code->synw_c[br][nc])[k] = syn_entry(hard0, sb, k);
+            ++(w ? nw : nc);
+        }
+        for (; nw < 2 * LF_BFW_JP; ++nw)
+            for (int k = 0; k < 8; ++k) code->synw_w[br][nw][k] = syn_zero_entry(zero);
+        for (; nc < LF_MAX_DEG; ++nc)
+            for (int k = 0; k < 8; ++k) code->synw_c[br][nc][k] = syn_zero_entry(zero);
     }
 }
 
@@ -655,6 +682,36 @@ extern "C" int lnsfaid_code_zero_shift_order(const lnsfaid_code* code, int32_t* 
                 if (dc->cbtab[br][i] == dc->zcbtab[br][j] && dc->s4tab[br][i] == dc->zs4tab[br][j]) order[br * LF_MAX_DEG + j] = i;
         }
     }
+    delete dc;
+    return nbr;
+}
+
+extern "C" int lnsfaid_code_bf_walk(const lnsfaid_code* code, int32_t col_weight, uint32_t* full, uint32_t* flipped, uint32_t* fixed, int32_t* info)
+{
+    if (!full || !flipped || !fixed || !info || col_weight < 0 || col_weight > LF_MAX_COLW) return LNSFAID_E_INVAL;
+    LfDevCode* dc = new (std::nothrow) LfDevCode;
+    if (!dc) return LNSFAID_E_NOMEM;
+    const int rc = build_code(code, dc);
+    if (rc) { delete dc; return rc; }
+    build_wcols(dc, col_weight);
+    const int nbr = dc->nbr;
+    for (int br = 0; br < nbr; ++br)
+        for (int k = 0; k < 8; ++k) {
+            for (int j = 0; j < LF_MAX_DEG; ++j) {
+                uint32_t* o = full + ((br * LF_MAX_DEG + j) * 8 + k) * 2, *x = fixed + ((br * LF_MAX_DEG + j) * 8 + k) * 2;
+                o[0] = dc->synw[br][j][k].x; o[1] = dc->synw[br][j][k].y;
+                x[0] = dc->synw_c[br][j][k].x; x[1] = dc->synw_c[br][j][k].y;
+            }
+            for (int j = 0; j < 2 * LF_BFW_JP; ++j) {
+                uint32_t* o = flipped + ((br * 2 * LF_BFW_JP + j) * 8 + k) * 2;
+                o[0] = dc->synw_w[br][j][k].x; o[1] = dc->synw_w[br][j][k].y;
+            }
+        }
+    info[0] = (int32_t)lf_lds_off_hard(dc->n_var);
+    info[1] = (int32_t)lf_lds_off_zero(dc->n_var, dc->n_words, dc->p_words);
+    info[2] = 2 * LF_BFW_JP;
+    info[3] = dc->bfw_fits;
+    info[4] = dc->n_wcols;
     delete dc;
     return nbr;
 }

@@ -15,6 +15,7 @@
 #define LF_MAX_DEG 24   /* check degree;        50G-PON: 23   */
 #define LF_MAX_BC 256   /* block columns;       50G-PON: 69   */
 #define LF_MAX_COLW 16  /* column weight;       50G-PON: 12   */
+#define LF_BFW_JP 7     /* circulants of weight-W block columns per half layer in the bit-flipping stage's walk; 50G-PON: 12 or 13 per layer */
 
 #define LF_DONE 0x40000000 /* status flag: codeword finished; low bits keep its last decision point */
 #define LF_PROG_MASK 0x0fffffff
@@ -56,6 +57,12 @@ struct LfDevCode {
     uint32_t zcbtab[LF_MAX_BR][LF_MAX_DEG];   /* cbtab in that order                                                             */
     int32_t zinst[LF_MAX_BR];                 /* the layer's instance of that step: degree << 16 | leading groups of four zero-shift
                                                * edges in use << 8 | one bit per compiled instance (lf_decode4z_inst)            */
+    /* synw split by what the bit-flipping stage can change: it flips block columns of weight W only, so the
+     * other columns' share of every parity word is fixed while a codeword is in the stage.  Entries as in synw, unused slots the
+     * zero word; rebuilt with wcol when REGULAR_COL_WEIGHT changes. */
+    uint2 synw_w[LF_MAX_BR][2 * LF_BFW_JP][8]; /* the circulants of weight-W block columns (walked in every iteration)            */
+    uint2 synw_c[LF_MAX_BR][LF_MAX_DEG][8];    /* all other circulants (walked once per stage)                                   */
+    int32_t bfw_fits;                          /* no layer has more than 2 * LF_BFW_JP circulants of weight-W block columns       */
 };
 
 struct LfDevCfg {

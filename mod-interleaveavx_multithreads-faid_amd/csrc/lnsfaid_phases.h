@@ -77,15 +77,21 @@ struct SynCache {
     uint2 e[LF_SYN_ROUNDS][LF_SYN_JP];
 };
 __device__ __forceinline__ bool syn_cache_fits(int nbr) { return nbr * 16 <= LF_SYN_ROUNDS * 64; }
-__device__ __forceinline__ void syn_cache_load(const LfDevCode* gc, int nbr, int tid, SynCache& sc)
+/* this lane's entries of a walk table of 2 * JP slots per layer: half task tid + 64 r is half (ht & 1) of task ht >> 1 = (layer, word) */
+template <int JP>
+__device__ __forceinline__ void syn_table_load(const uint2 (*tab)[2 * JP][8], int nbr, int tid, uint2 (&e)[LF_SYN_ROUNDS][JP])
 {
 #pragma unroll
     for (int r = 0; r < LF_SYN_ROUNDS; ++r) {
         const int ht = tid + 64 * r;
         const int task = ht < nbr * 16 ? ht >> 1 : 0, part = ht & 1;
 #pragma unroll
-        for (int j = 0; j < LF_SYN_JP; ++j) sc.e[r][j] = gc->synw[task >> 3][part * LF_SYN_JP + j][task & 7];
+        for (int j = 0; j < JP; ++j) e[r][j] = tab[task >> 3][part * JP + j][task & 7];
     }
+}
+__device__ __forceinline__ void syn_cache_load(const LfDevCode* gc, int nbr, int tid, SynCache& sc)
+{
+    syn_table_load<LF_SYN_JP>(gc->synw, nbr, tid, sc.e);
 }
 
 template <int T, bool ROWBITS, bool CACHED = false>
@@ -183,20 +189,37 @@ __device__ __forceinline__ void bf_cache_load(CCode c, const LfDevCode* gc, int 
     }
 }
 
+/* threshold state machine on int8 lanes (CDecoder_FAID.cpp:6787-6799): the iteration's threshold and the counters after it.  Its
+ * five parameters are read through BfThr so that the staged path can read them once per stage: left to the iteration, every one
+ * is a scalar load with a wait of its own on whichever branch of the machine asks for it. */
+struct BfThr {
+    int W, alpha, delta, L0, L1;
+};
+__device__ __forceinline__ BfThr bf_thr_load(CCfg f)
+{
+    BfThr p;
+    p.W = f->W; p.alpha = f->alpha; p.delta = f->delta; p.L0 = f->L0; p.L1 = f->L1;
+    return p;
+}
+__device__ __forceinline__ void bf_threshold(const BfThr& p, const LfLaneState& ls, int& Th, int& l0, int& l1)
+{
+    Th = ls.Th; l0 = ls.l0; l1 = ls.l1;
+    if (!ls.t) Th = imax(Th - p.delta, -128);
+    const bool max_Th = ls.t && (l0 < (int)(int8_t)p.L0);
+    if (max_Th) { Th = (int8_t)(p.W + p.alpha); l0 = imin(l0 + 1, 127); }
+    const bool submax_Th = ls.t && !max_Th && (l1 < (int)(int8_t)p.L1);
+    if (submax_Th) { Th = (int8_t)(p.W + p.alpha - p.delta); l1 = imin(l1 + 1, 127); }
+    if (ls.t && !max_Th && !submax_Th) Th = (int8_t)(p.W + p.alpha - 2 * p.delta);
+    Th = imax(Th, 1);
+}
+
 template <int T, int METHOD, bool CACHED = false>
 __device__ __forceinline__ void bf_step(CCode c, CCfg f, const LfDevCode* gc, uint32_t* sHard, const uint32_t* sHard0, uint32_t* sHard2,
                         const uint32_t* sP, int tid, LfLaneState& ls, int* sRed, const BfCache* bc = nullptr)
 {
     const int W = f->W;
-    /* threshold state machine on int8 lanes (CDecoder_FAID.cpp:6787-6799) */
-    int Th = ls.Th, l0 = ls.l0, l1 = ls.l1;
-    if (!ls.t) Th = imax(Th - f->delta, -128);
-    const bool max_Th = ls.t && (l0 < (int)(int8_t)f->L0);
-    if (max_Th) { Th = (int8_t)(W + f->alpha); l0 = imin(l0 + 1, 127); }
-    const bool submax_Th = ls.t && !max_Th && (l1 < (int)(int8_t)f->L1);
-    if (submax_Th) { Th = (int8_t)(W + f->alpha - f->delta); l1 = imin(l1 + 1, 127); }
-    if (ls.t && !max_Th && !submax_Th) Th = (int8_t)(W + f->alpha - 2 * f->delta);
-    Th = imax(Th, 1);
+    int Th, l0, l1;
+    bf_threshold(bf_thr_load(f), ls, Th, l0, l1);
     const bool big = Th >= (int)(int8_t)W; /* mask_big_jump, 2B1C only */
     const int alpha = (int8_t)f->alpha;
     int any = 0;
@@ -283,6 +306,179 @@ __device__ __forceinline__ void bf_step(CCode c, CCfg f, const LfDevCode* gc, ui
     ls.Th = Th; ls.l0 = l0; ls.l1 = l1;
     const unsigned long long anyw = __ballot(any);
     ls.t = block_sum<T>(anyw != 0ull ? 1 : 0, tid, sRed) != 0; /* barriers also order the plane updates */
+}
+
+/* ---- the bit-flipping stage of the one-wave kernels with what is constant in it taken out of its iterations.
+ * bf_step flips block columns of weight W only, so the share of all other columns in every parity word is fixed from the moment
+ * a codeword enters the stage (fresh from the layered loop or resumed: the planes are in the LDS then): each lane computes it once
+ * for its half tasks (synw_c) and an iteration walks only the circulants of weight-W columns (synw_w, LF_BFW_JP slots per half
+ * against LF_SYN_JP).  The flip's LDS addresses and bit offsets depend on the lane and the code only: finished once per stage.
+ * sP and the unsatisfied count are bit for bit those of the full walk. */
+typedef __attribute__((address_space(3))) uint32_t lf_lds_u32;
+struct BfStage {
+    uint2 e[LF_SYN_ROUNDS][LF_BFW_JP]; /* this lane's entries of synw_w                                                 */
+    uint32_t base[LF_SYN_ROUNDS];      /* XOR over its entries of synw_c (this half of the circulant list, not merged)   */
+    uint32_t wa[LF_BF_ROUNDS][3][3];   /* flip unit: LDS byte addresses of the three parity words under each window      */
+    uint32_t wr[LF_BF_ROUNDS][3];      /* and the windows' bit offsets                                                   */
+    uint32_t ah[LF_BF_ROUNDS];         /* LDS byte address of the unit's two words of the hard plane                     */
+    /* wave-uniform (scalar registers): read or worked out once per stage */
+    BfThr thr;
+    int half_tasks, units;             /* 16 per layer; 4 per block column of weight W                                   */
+    uint32_t h0_off, h2_off;           /* from a word of the hard plane to the same word of hard_ch (at 0) / hard2 (at 4 n_words) */
+    uint32_t amask;                    /* alpha != 0: all ones                                                           */
+};
+__device__ __forceinline__ bool bf_stage_fits(CCode c, CCfg f) { return bf_cache_fits(c, f) && c->bfw_fits; }
+__device__ __forceinline__ void bf_stage_load(CCode c, CCfg f, const LfDevCode* gc, int tid, BfStage& bs)
+{
+    const int nbr = c->nbr;
+    const uint32_t hard0 = lf_lds_off_hard(c->n_var), par0 = lf_lds_off_p(c->n_var, c->n_words);
+    bs.thr = bf_thr_load(f);
+    bs.half_tasks = nbr * 16; bs.units = c->n_wcols * 4;
+    bs.h0_off = 0u - hard0; bs.h2_off = 4u * (uint32_t)c->n_words - hard0;
+    bs.amask = (int8_t)bs.thr.alpha ? 0xffffffffu : 0u;
+    {
+        uint2 ec[LF_SYN_ROUNDS][LF_SYN_JP];
+        syn_table_load<LF_SYN_JP>(gc->synw_c, nbr, tid, ec);
+#pragma unroll
+        for (int r = 0; r < LF_SYN_ROUNDS; ++r) {
+            uint32_t w0[LF_SYN_JP], w1[LF_SYN_JP], acc = 0;
+#pragma unroll
+            for (int j = 0; j < LF_SYN_JP; ++j) {
+                w0[j] = *(const lf_lds_u32*)(size_t)(ec[r][j].x & 0xffffu); w1[j] = *(const lf_lds_u32*)(size_t)(ec[r][j].x >> 16);
+            }
+            __builtin_amdgcn_sched_barrier(0); /* (as in syndrome: the round's reads in flight together) */
+#pragma unroll
+            for (int j = 0; j < LF_SYN_JP; ++j) acc ^= __builtin_amdgcn_alignbit(w1[j], w0[j], ec[r][j].y);
+            bs.base[r] = acc;
+        }
+    }
+    syn_table_load<LF_BFW_JP>(gc->synw_w, nbr, tid, bs.e);
+    const int units = bs.units;
+#pragma unroll
+    for (int r = 0; r < LF_BF_ROUNDS; ++r) {
+        const int u = tid + 64 * r;
+        const int cb = gc->wcol[u < units ? u >> 2 : 0];
+        const uint32_t win = (uint32_t)(u & 3);
+        bs.ah[r] = hard0 + 4u * ((uint32_t)cb * 8u + 2u * win);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { /* window64 on block colcirc & 0xff of sP at bit 64 win - shift */
+            const uint32_t cc = gc->colcirc[cb][k];
+            const uint32_t o = (64u * win - ((cc >> 8) & 0xffu)) & 255u, q = o >> 5;
+            bs.wr[r][k] = o & 31u;
+#pragma unroll
+            for (uint32_t i = 0; i < 3; ++i) bs.wa[r][k][i] = par0 + 4u * ((cc & 0xffu) * 8u + ((q + i) & 7u));
+        }
+    }
+}
+
+/* the syndrome of an iteration of the stage: syndrome<64, false, true> on the weight-W circulants, started from the fixed share */
+__device__ __forceinline__ int syndrome_staged(uint32_t* sP, int tid, int* sRed, const BfStage& bs)
+{
+    uint32_t w0[LF_SYN_ROUNDS][LF_BFW_JP], w1[LF_SYN_ROUNDS][LF_BFW_JP];
+#pragma unroll
+    for (int r = 0; r < LF_SYN_ROUNDS; ++r)
+#pragma unroll
+        for (int j = 0; j < LF_BFW_JP; ++j) {
+            w0[r][j] = *(const lf_lds_u32*)(size_t)(bs.e[r][j].x & 0xffffu); w1[r][j] = *(const lf_lds_u32*)(size_t)(bs.e[r][j].x >> 16);
+        }
+    __builtin_amdgcn_sched_barrier(0); /* every read of the walk in flight before the first use */
+    int cnt = 0;
+#pragma unroll
+    for (int r = 0; r < LF_SYN_ROUNDS; ++r) {
+        const int ht = tid + 64 * r;
+        uint32_t acc = bs.base[r];
+#pragma unroll
+        for (int j = 0; j < LF_BFW_JP; ++j) acc ^= __builtin_amdgcn_alignbit(w1[r][j], w0[r][j], bs.e[r][j].y);
+        acc ^= (uint32_t)__builtin_amdgcn_mov_dpp((int)acc, 0xb1, 0xf, 0xf, false); /* the other half of the circulant list */
+        if (!(ht & 1) && ht < bs.half_tasks) { /* (lanes beyond the last task walked task 0) */
+            sP[ht >> 1] = acc;
+            cnt += __popc(acc);
+        }
+    }
+    cnt = add_reduce32(cnt);
+    const int wave_cnt = __builtin_amdgcn_readlane(cnt, 31) + __builtin_amdgcn_readlane(cnt, 63);
+    return block_sum<64>(wave_cnt, tid, sRed); /* its fence also publishes sP */
+}
+
+/* bf_step<64, METHOD> of a configuration with bf_fast on the finished addresses of BfStage: every LDS read of the iteration in
+ * flight before the first use, the vote planes of all units, ONE choice of the (wave-uniform) threshold for the flip masks of all
+ * of them, then the stores.  bf_fast means W == 3, so mask_big_jump of the 2B1C is Th >= 3. */
+template <int TH>
+__device__ __forceinline__ void bf_masks_staged(uint32_t (&m)[LF_BF_ROUNDS][2], const uint32_t (&s0)[LF_BF_ROUNDS][2],
+                                                const uint32_t (&cy)[LF_BF_ROUNDS][2], const uint32_t (&fl)[LF_BF_ROUNDS][2])
+{
+#pragma unroll
+    for (int r = 0; r < LF_BF_ROUNDS; ++r)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) /* votes + fl >= TH, votes = s0 + 2 cy */
+            m[r][h] = TH == 1 ? (s0[r][h] | cy[r][h] | fl[r][h]) : TH == 2 ? (cy[r][h] | (s0[r][h] & fl[r][h]))
+                    : TH == 3 ? (cy[r][h] & (s0[r][h] | fl[r][h])) : (cy[r][h] & s0[r][h] & fl[r][h]);
+}
+
+template <int METHOD>
+__device__ __forceinline__ void bf_step_staged(int tid, LfLaneState& ls, int* sRed, const BfStage& bs)
+{
+    int Th, l0, l1;
+    bf_threshold(bs.thr, ls, Th, l0, l1);
+    const int units = bs.units;
+    const uint32_t h2_off = bs.h2_off, amask = bs.amask;
+    uint32_t pw[LF_BF_ROUNDS][3][3], hd[LF_BF_ROUNDS][2], h0[LF_BF_ROUNDS][2], h2[LF_BF_ROUNDS][2];
+#pragma unroll
+    for (int r = 0; r < LF_BF_ROUNDS; ++r) { /* (lanes beyond the last unit read unit 0's words and store nothing) */
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+#pragma unroll
+            for (int i = 0; i < 3; ++i) pw[r][k][i] = *(const lf_lds_u32*)(size_t)bs.wa[r][k][i];
+        const lf_lds_u32* ph = (const lf_lds_u32*)(size_t)bs.ah[r];
+        const lf_lds_u32* p0 = (const lf_lds_u32*)(size_t)(bs.ah[r] + bs.h0_off);
+        const lf_lds_u32* p2 = (const lf_lds_u32*)(size_t)(bs.ah[r] + h2_off);
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            hd[r][h] = ph[h]; h0[r][h] = p0[h];
+            h2[r][h] = METHOD == 5 ? p2[h] : 0u;
+        }
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    uint32_t s0[LF_BF_ROUNDS][2], cy[LF_BF_ROUNDS][2], fl[LF_BF_ROUNDS][2], m[LF_BF_ROUNDS][2];
+#pragma unroll
+    for (int r = 0; r < LF_BF_ROUNDS; ++r)
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            uint32_t p[3]; /* window64: the low / high 32 bits of the window under circulant k */
+#pragma unroll
+            for (int k = 0; k < 3; ++k) p[k] = __builtin_amdgcn_alignbit(pw[r][k][h + 1], pw[r][k][h], bs.wr[r][k]);
+            s0[r][h] = p[0] ^ p[1] ^ p[2]; cy[r][h] = (p[0] & p[1]) | (p[0] & p[2]) | (p[1] & p[2]);
+            fl[r][h] = (hd[r][h] ^ h0[r][h]) & amask; /* already flipped once: +alpha */
+        }
+    if (Th <= 1) bf_masks_staged<1>(m, s0, cy, fl);
+    else if (Th == 2) bf_masks_staged<2>(m, s0, cy, fl);
+    else if (Th == 3) bf_masks_staged<3>(m, s0, cy, fl);
+    else if (Th == 4) bf_masks_staged<4>(m, s0, cy, fl);
+    else {
+#pragma unroll
+        for (int r = 0; r < LF_BF_ROUNDS; ++r) m[r][0] = m[r][1] = 0u;
+    }
+    const bool big = Th >= 3; /* mask_big_jump, 2B1C only */
+    uint32_t anym = 0;
+#pragma unroll
+    for (int r = 0; r < LF_BF_ROUNDS; ++r)
+        if (tid + 64 * r < units) {
+            anym |= m[r][0] | m[r][1];
+            lf_lds_u32* ph = (lf_lds_u32*)(size_t)bs.ah[r];
+            if (METHOD == 5) {
+                lf_lds_u32* p2 = (lf_lds_u32*)(size_t)(bs.ah[r] + h2_off);
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    ph[h] = hd[r][h] ^ (big ? m[r][h] : m[r][h] & ~h2[r][h]);
+                    p2[h] = big ? h2[r][h] ^ m[r][h] : h2[r][h] & ~m[r][h];
+                }
+            } else {
+                ph[0] = hd[r][0] ^ m[r][0]; ph[1] = hd[r][1] ^ m[r][1];
+            }
+        }
+    ls.Th = Th; ls.l0 = l0; ls.l1 = l1;
+    const unsigned long long anyw = __ballot(anym != 0u);
+    ls.t = block_sum<64>(anyw != 0ull ? 1 : 0, tid, sRed) != 0; /* its fence also orders the plane updates */
 }
 
 /* ---- plain bit flipping of Decode_OMSBF (CDecoder_OMSBF.cpp:2969-3514): flip every variable node whose vote count

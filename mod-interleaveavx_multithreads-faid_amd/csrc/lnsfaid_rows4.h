@@ -540,17 +540,26 @@ _Pragma("unroll")                                                               
 
 #define LF4_BF_LOOPS() \
     if (in_bf && !parked) {                                                                                                                 \
-        if ((RM || syn_cache_fits(c->nbr)) && (METHOD == 3 || bf_cache_fits(c, f))) {                                                       \
+        if (METHOD != 3 && (RM || syn_cache_fits(c->nbr)) && bf_stage_fits(c, f)) {                                                         \
+            /* the stage's constants out of its iterations (lnsfaid_phases.h BfStage) */                                                    \
+            BfStage bs;                                                                                                                     \
+            bf_stage_load(c, f, a.code, tid, bs);                                                                                           \
+            while (prog < t_end) {                                                                                                          \
+                const int unsat = syndrome_staged(sP, tid, sRed, bs);                                                                       \
+                if (unsat == 0 && LF4_CLEAN_STOPS(tid)) { parked = true; break; }                                                           \
+                LF4_ON_PASS(tid)                                                                                                            \
+                bf_step_staged<METHOD>(tid, ls, sRed, bs);                                                                                  \
+                prog++;                                                                                                                     \
+            }                                                                                                                               \
+        } else if (METHOD == 3 && (RM || syn_cache_fits(c->nbr))) {                                                                         \
+            /* the plain flip may change every column: the full walk, its table entries in registers */                                     \
             SynCache sc;                                                                                                                    \
-            BfCache bc;                                                                                                                     \
             syn_cache_load(a.code, c->nbr, tid, sc);                                                                                        \
-            if (METHOD != 3) bf_cache_load(c, a.code, tid, bc);                                                                             \
             while (prog < t_end) {                                                                                                          \
                 const int unsat = syndrome<LF_T4, false, true>(c, a.code, sP, tid, pA, pB, sRed, &sc);                                      \
                 if (unsat == 0 && LF4_CLEAN_STOPS(tid)) { parked = true; break; }                                                           \
                 LF4_ON_PASS(tid)                                                                                                            \
-                if (METHOD == 3) bf_step_plain<LF_T4>(c, f, a.code, sHard, sHard2 + nw /* 4 count planes in the dead En */, sP, tid, sRed); \
-                else bf_step<LF_T4, METHOD, true>(c, f, a.code, sHard, sHard0, sHard2, sP, tid, ls, sRed, &bc);                             \
+                bf_step_plain<LF_T4>(c, f, a.code, sHard, sHard2 + nw /* 4 count planes in the dead En */, sP, tid, sRed);                  \
                 prog++;                                                                                                                     \
             }                                                                                                                               \
         } else {                                                                                                                            \

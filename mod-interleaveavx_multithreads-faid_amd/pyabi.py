@@ -141,6 +141,8 @@ SYMBOLS = {
     "lnsfaid_select_zero_shift": (C.c_int, [C.c_void_p, C.c_int32]),
     "lnsfaid_zero_shift_groups": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
     "lnsfaid_code_zero_shift_order": (C.c_int, [C.POINTER(Code), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "lnsfaid_code_bf_walk": (C.c_int, [C.POINTER(Code), C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                      C.POINTER(C.c_int32)]),
     "lnsfaid_kernel_residency": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lnsfaid_kernel_time": (C.c_int, [C.c_void_p, C.POINTER(C.c_double), C.POINTER(C.c_uint64), C.c_int32]),
     "lnsfaid_stream": (C.c_void_p, [C.c_void_p]),
@@ -208,6 +210,22 @@ def code_zero_shift_order(code, lib=None):
     if nbr < 0:
         raise ValueError("lnsfaid_code_zero_shift_order failed: %d" % nbr)
     return list(groups[:nbr]), [[j for j in order[br * 24:br * 24 + 24] if j >= 0] for br in range(nbr)]
+
+
+def code_bf_walk(code, col_weight, lib=None):
+    """lnsfaid_code_bf_walk (no GPU needed): the syndrome walk tables (full, flipped, fixed) as uint32 arrays [layers][slots][8][2]
+    and info = (hard plane offset, zero word offset, slots of `flipped`, fits, block columns of that weight)"""
+    import numpy as np
+    lib = lib or load()
+    full, fixed = np.zeros((32, 24, 8, 2), np.uint32), np.zeros((32, 24, 8, 2), np.uint32)
+    flipped = np.zeros((32 * 24 * 8 * 2,), np.uint32)  # at least [32][info[2]][8][2]
+    info = (C.c_int32 * 5)()
+    u32 = lambda x: x.ctypes.data_as(C.POINTER(C.c_uint32))
+    nbr = lib.lnsfaid_code_bf_walk(C.byref(code), col_weight, u32(full), u32(flipped), u32(fixed), info)
+    if nbr < 0:
+        raise ValueError("lnsfaid_code_bf_walk failed: %d" % nbr)
+    slots = info[2]
+    return full[:nbr], flipped[:nbr * slots * 16].reshape(nbr, slots, 8, 2), fixed[:nbr], tuple(info)
 
 
 def default_cfg(method, max_iter, lib=None):
