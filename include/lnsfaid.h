@@ -254,6 +254,60 @@ int lnsfaid_pack_llr4(const int8_t* fixInput, size_t n_values, uint8_t* llr4);
 int lnsfaid_unpack_bits(const uint32_t* bits, size_t n_bits, int8_t* decodedBits);
 int lnsfaid_pack_bits(const int8_t* inputBits, size_t n_bits, uint8_t* packed);
 
+/* ---- line-format decode --------------------------------------------------------------------------------
+ * Decode on the format a line delivers: codeword after codeword in transmission order, one bit or one 4-bit LLR per transmitted
+ * code bit, any number of codewords; the K payload bits out, contiguous.  Let L = n_var - puncture_tail (50G-PON: 17 280) and
+ * K = n_var - n_check (14 592).  Both must be multiples of 32, LNSFAID_E_INVAL otherwise.
+ *   line, LNSFAID_LINE_HARD   L / 32 little-endian 32-bit words per codeword, codeword c at word c * L / 32.  Bit b of word w is
+ *            the received bit of code-bit position 32 w + b, in the order of decodedBits: the information bits, then the
+ *            transmitted parity bits.  A 1 bit enters the decoder as +magnitude, a 0 bit as -magnitude (positive means bit 1, as
+ *            everywhere in this library), magnitude in 1 .. 7.
+ *   line, LNSFAID_LINE_LLR4   L / 2 bytes per codeword, codeword c at byte c * L / 2.  Element k (code-bit position k) is a
+ *            two's-complement nibble in byte k / 2, the low nibble when k is even: the nibble rule of llr4, -8 included.  magnitude
+ *            is ignored.
+ *   payload  K / 32 words per codeword, codeword c at word c * K / 32; bit b of word w is decoded bit 32 w + b: the msg format of
+ *            lnsfaid_count_errors_packed, so the payloads of consecutive codewords are one contiguous bit stream
+ *            (lnsfaid_unpack_bits(payload, n_codewords * K, ...) gives them as int8 0 / 1).
+ *   bits     optional (NULL: not written): the packed decisions of the packed decode I/O, n_var / 32 words per codeword, so that
+ *            lnsfaid_fec_status_packed_* and lnsfaid_count_errors_packed_* can follow (with the llr4 of lnsfaid_line_to_llr4).
+ *   stats    optional, [n_codewords] lnsfaid_line_stats.
+ * No gaps, no padding: the calls read exactly n_codewords * L / 32 words (LLR4: n_codewords * L / 2 bytes) and write exactly
+ * n_codewords entries of each output, nothing outside.
+ * Decoding is always under the per-codeword rule (LNSFAID_STOP_CODEWORD), whatever lnsfaid_set_early_stop says: a group rule has
+ * no meaning on a line.  lnsfaid_line_to_llr4 is the definition of what is decoded: for every codeword the line calls return what
+ * lnsfaid_decode_codewords_packed* returns for that llr4 - the first K / 32 words as payload, all words as bits, and iterations,
+ * bf_iterations and unsatisfied.
+ * n_codewords: 0 (a no-op, the buffers may be NULL) .. 32 * max_groups.  LNSFAID_E_INVAL: more codewords than that; a format
+ * other than the two; LNSFAID_LINE_HARD with a magnitude outside 1 .. 7; a NULL line or payload with n_codewords > 0; a device
+ * pointer that is not 4-byte aligned (more alignment only widens loads and stores; host pointers may have any alignment, they go
+ * through staging buffers of the context); a configuration without a per-codeword decoder (the two-rows kernel,
+ * lnsfaid_select_waves(ctx, 2)), as lnsfaid_decode_codewords.  The device call queues on the context's stream and returns when
+ * the outputs are complete. */
+#define LNSFAID_LINE_HARD 0
+#define LNSFAID_LINE_LLR4 1
+typedef struct lnsfaid_line_stats {
+    int32_t iterations;    /* as lnsfaid_codeword_stats */
+    int32_t bf_iterations; /* as lnsfaid_codeword_stats */
+    int32_t unsatisfied;   /* as lnsfaid_codeword_stats: 0 means payload and bits are those of a codeword */
+    int32_t corrected;     /* lnsfaid_fec_record::corrected: the positions k < L at which the decoded bit differs from the channel's
+                            * own decision - the line bit (HARD), nibble > 0 (LLR4) */
+} lnsfaid_line_stats;
+int lnsfaid_decode_line(lnsfaid_ctx* ctx, const void* line, int32_t format, int32_t magnitude, size_t n_codewords,
+                        uint32_t* payload, uint32_t* bits, lnsfaid_line_stats* stats);
+int lnsfaid_decode_line_device(lnsfaid_ctx* ctx, const void* d_line, int32_t format, int32_t magnitude, size_t n_codewords,
+                               uint32_t* d_payload, uint32_t* d_bits, lnsfaid_line_stats* d_stats);
+/* Host only, no context, no GPU; of the code only n_var, n_check and puncture_tail are read.  Host pointers of any alignment.
+ * lnsfaid_line_from_fixinput: the int8 group layout of lnsfaid_decode (ceil(n_codewords / 32) whole groups on the input side
+ *   only) -> line of n_codewords codewords.  LLR4: a re-layout that drops the punctured tail; a transmitted value outside
+ *   -8 .. 7 is LNSFAID_E_INVAL (the output is then incomplete).  HARD: the bit is x > 0.  The tail's values are never read.
+ * lnsfaid_line_to_llr4: line -> the llr4 group layout of ceil(n_codewords / 32) groups; the punctured tail and the padding
+ *   codewords are nibble 0.  HARD: +-magnitude (1 .. 7, else LNSFAID_E_INVAL); LLR4: magnitude is ignored.
+ * Both: LNSFAID_E_INVAL for a NULL code, a bad format, L or K not a multiple of 32, a NULL buffer with n_codewords > 0;
+ * n_codewords 0 is a no-op. */
+int lnsfaid_line_from_fixinput(const lnsfaid_code* code, const int8_t* fixInput, size_t n_codewords, int32_t format, void* line);
+int lnsfaid_line_to_llr4(const lnsfaid_code* code, const void* line, int32_t format, int32_t magnitude, size_t n_codewords,
+                         uint8_t* llr4);
+
 /* ---- front-end on the device (optional, the host generator stays the parity source) ---- */
 
 /*

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "lnsfaid_device.h"
+#include "lnsfaid_line.h"
 #include "lnsfaid_quantise.h"
 #include "lnsfaid_swar.h" /* sw_nms_fits / sw_nms_tables (host side) */
 
@@ -33,6 +34,8 @@ extern "C" hipError_t lf_launch_decode4cw(int method, int ef, int rm, const LfCw
 extern "C" const void* lf_decode4p_func(int method, int ef, int rm, int per_codeword);
 extern "C" hipError_t lf_launch_decode4p(int method, int ef, int rm, const LfKernelArgs* args, size_t lds_bytes, hipStream_t stream);
 extern "C" hipError_t lf_launch_decode4pcw(int method, int ef, int rm, const LfCwArgs* args, size_t lds_bytes, hipStream_t stream);
+extern "C" const void* lf_decode4l_func(int method, int ef, int rm);
+extern "C" hipError_t lf_launch_decode4l(int method, int ef, int rm, const LfLineArgs* args, size_t lds_bytes, hipStream_t stream);
 extern "C" hipError_t lf_launch_unpack_llr4(const uint8_t* d_llr4, int8_t* d_fix, size_t n_values, hipStream_t stream);
 extern "C" hipError_t lf_launch_pack_bits(const int8_t* d_decoded, uint32_t* d_bits, size_t n_values, hipStream_t stream);
 extern "C" hipError_t lf_launch_count_errors_packed(const uint32_t* d_bits, const uint32_t* d_msg, int n_var, int k_info, size_t n_cw,
@@ -143,6 +146,10 @@ struct lnsfaid_ctx {
     uint8_t* d_pk_in = nullptr;   /* llr4, 16 * n_var bytes per group */
     uint32_t* d_pk_out = nullptr; /* bits, n_var words per group */
     lnsfaid_group_stats* d_pk_stats = nullptr;
+    /* staging for lnsfaid_decode_line, allocated at its first call; line and bits go through d_pk_in / d_pk_out */
+    uint32_t* d_ln_payload = nullptr;       /* K words per group */
+    lnsfaid_line_stats* d_ln_stats = nullptr;
+    const void* checked_line_fn = nullptr;  /* line kernel instance whose static LDS has been looked at */
     int early_stop = LNSFAID_STOP_GROUP; /* rule of lnsfaid_decode / lnsfaid_decode_device (lnsfaid_set_early_stop) */
     int rows_per_lane = 0; /* 0: pick per configuration; 2 / 4: forced (lnsfaid_select_kernel) */
     int waves_per_cw = 0;  /* 0 / 1: one wave per codeword; 2: lnsfaid_kernel5.hip where it applies (lnsfaid_select_waves) */
@@ -429,6 +436,7 @@ extern "C" void lnsfaid_destroy(lnsfaid_ctx* ctx)
     (void)hipFree(ctx->d_io_in); (void)hipFree(ctx->d_io_out); (void)hipFree(ctx->d_io_stats);
     (void)hipFree(ctx->d_io_cw_stats);
     (void)hipFree(ctx->d_pk_in); (void)hipFree(ctx->d_pk_out); (void)hipFree(ctx->d_pk_stats);
+    (void)hipFree(ctx->d_ln_payload); (void)hipFree(ctx->d_ln_stats);
     (void)hipFree(ctx->d_fe_seeds); (void)hipFree(ctx->d_fe_draws); (void)hipFree(ctx->d_fe_codeword);
     (void)hipFree(ctx->d_fe_frames); (void)hipFree(ctx->d_fe_input);
     (void)hipFree(ctx->d_enc_sup); (void)hipFree(ctx->d_enc_off); (void)hipFree(ctx->d_fe_keys);
@@ -1639,6 +1647,98 @@ extern "C" int lnsfaid_count_errors_packed(lnsfaid_ctx* ctx, const uint32_t* bit
         d_msg = ctx->d_pk_in;
     }
     return lnsfaid_count_errors_packed_device(ctx, ctx->d_pk_out, d_msg, n_groups, out);
+}
+
+/* ---- line-format decode (include/lnsfaid.h "line-format decode", DESIGN.md 3.14, lnsfaid_kernel4l.hip) ------------------ */
+/* everything that can be refused without looking at the buffers; 1: nothing to do */
+static int line_rules(const lnsfaid_ctx* ctx, int32_t format, int32_t magnitude, size_t n_codewords)
+{
+    if (!ctx || (format != LNSFAID_LINE_HARD && format != LNSFAID_LINE_LLR4)) return LNSFAID_E_INVAL;
+    if (format == LNSFAID_LINE_HARD && (magnitude < 1 || magnitude > 7)) return LNSFAID_E_INVAL;
+    const int L = ctx->n_var - ctx->hcode.puncture_tail;
+    if (L <= 0 || L % 32 != 0 || ctx->k_info % 32 != 0) return LNSFAID_E_INVAL;
+    if (n_codewords > ctx->max_groups * LNSFAID_GROUP) return LNSFAID_E_INVAL;
+    if (!cw_possible(ctx)) return LNSFAID_E_INVAL;
+    return n_codewords == 0 ? 1 : LNSFAID_OK;
+}
+
+static size_t line_bytes(const lnsfaid_ctx* ctx, int32_t format)
+{
+    const size_t L = (size_t)(ctx->n_var - ctx->hcode.puncture_tail);
+    return format == LNSFAID_LINE_HARD ? L / 8 : L / 2;
+}
+
+/* one launch, one wait: the per-codeword rule (decode_cw_device_impl) without group records */
+static int decode_line_launch(lnsfaid_ctx* ctx, const void* d_line, int32_t format, int32_t magnitude, size_t n_codewords,
+                              uint32_t* d_payload, uint32_t* d_bits, lnsfaid_line_stats* d_stats)
+{
+    const int rm = use_msg_registers(ctx) ? 1 : 0;
+    const void* fn = lf_decode4l_func(ctx->hcfg.method, ctx->hcfg.ef, rm);
+    if (!fn) return LNSFAID_E_INVAL;
+    if (fn != ctx->checked_line_fn) { /* as kernel_check: the En image must start at LDS offset 0 */
+        hipFuncAttributes at;
+        HIP_TRY(hipFuncGetAttributes(&at, fn));
+        if (at.sharedSizeBytes != 0) {
+            snprintf(g_hip_err, sizeof(g_hip_err), "line decode kernel has %zu bytes of static LDS: its En image would not start at LDS offset 0",
+                     (size_t)at.sharedSizeBytes);
+            return LNSFAID_E_INTERNAL;
+        }
+        ctx->checked_line_fn = fn;
+    }
+    LfLineArgs a;
+    a.code = ctx->d_code; a.cfg = ctx->d_cfg;
+    a.line = d_line; a.payload = d_payload; a.bits = d_bits;
+    a.st_rows = ctx->d_rows;
+    a.stats = d_stats;
+    a.format = format; a.magnitude = magnitude; a.n_cw = (int32_t)n_codewords;
+    static const bool trace = getenv("LNSFAID_TRACE") != nullptr;
+    HIP_TRY(hipEventRecord(ctx->ev_chain[0], ctx->stream));
+    HIP_TRY(lf_launch_decode4l(ctx->hcfg.method, ctx->hcfg.ef, rm, &a, ctx->lds_bytes, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev_chain[1], ctx->stream));
+    { const int rcw = stream_wait(ctx); if (rcw) return rcw; }
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_chain[0], ctx->ev_chain[1]));
+    ctx->kernel_ms += ms;
+    ctx->kernel_launches += 1;
+    if (trace) fprintf(stderr, "[lnsfaid] line launch: %.3f ms, %zu codewords\n", ms, n_codewords);
+    return LNSFAID_OK;
+}
+
+extern "C" int lnsfaid_decode_line_device(lnsfaid_ctx* ctx, const void* d_line, int32_t format, int32_t magnitude, size_t n_codewords,
+                                          uint32_t* d_payload, uint32_t* d_bits, lnsfaid_line_stats* d_stats)
+{
+    const int rc = line_rules(ctx, format, magnitude, n_codewords);
+    if (rc) return rc < 0 ? rc : LNSFAID_OK;
+    if (!d_line || !d_payload) return LNSFAID_E_INVAL;
+    if (!dword_aligned(d_line) || !dword_aligned(d_payload) || !dword_aligned(d_bits) || !dword_aligned(d_stats)) return LNSFAID_E_INVAL;
+    HIP_TRY(hipSetDevice(ctx->device));
+    return decode_line_launch(ctx, d_line, format, magnitude, n_codewords, d_payload, d_bits, d_stats);
+}
+
+/* host buffers of any alignment: one copy each way through staging buffers of the context, on its own stream */
+extern "C" int lnsfaid_decode_line(lnsfaid_ctx* ctx, const void* line, int32_t format, int32_t magnitude, size_t n_codewords,
+                                   uint32_t* payload, uint32_t* bits, lnsfaid_line_stats* stats)
+{
+    int rc = line_rules(ctx, format, magnitude, n_codewords);
+    if (rc) return rc < 0 ? rc : LNSFAID_OK;
+    if (!line || !payload) return LNSFAID_E_INVAL;
+    HIP_TRY(hipSetDevice(ctx->device));
+    rc = ensure_packed_io(ctx); /* d_pk_in holds a line of 32 * max_groups codewords in either format, d_pk_out their bits */
+    if (rc) return rc;
+    if (!ctx->d_ln_payload) {
+        HIP_TRY(hipMalloc(&ctx->d_ln_payload, ctx->max_groups * LNSFAID_GROUP * (size_t)ctx->k_info / 8));
+        HIP_TRY(hipMalloc(&ctx->d_ln_stats, ctx->max_groups * LNSFAID_GROUP * sizeof(lnsfaid_line_stats)));
+    }
+    const size_t k_bytes = (size_t)ctx->k_info / 8, n_bytes = (size_t)ctx->n_var / 8;
+    HIP_TRY(hipMemcpyAsync(ctx->d_pk_in, line, n_codewords * line_bytes(ctx, format), hipMemcpyHostToDevice, ctx->stream));
+    rc = decode_line_launch(ctx, ctx->d_pk_in, format, magnitude, n_codewords, ctx->d_ln_payload, bits ? ctx->d_pk_out : nullptr,
+                            stats ? ctx->d_ln_stats : nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(payload, ctx->d_ln_payload, n_codewords * k_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (bits) HIP_TRY(hipMemcpyAsync(bits, ctx->d_pk_out, n_codewords * n_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (stats)
+        HIP_TRY(hipMemcpyAsync(stats, ctx->d_ln_stats, n_codewords * sizeof(lnsfaid_line_stats), hipMemcpyDeviceToHost, ctx->stream));
+    return stream_wait(ctx);
 }
 
 /* host-only format helpers (no context, no GPU) */

@@ -255,3 +255,72 @@ int lnsfaid_fec_status_packed_host(const lnsfaid_code* code, const uint8_t* llr4
 {
     return fec_status_host(code, 1, llr4, (const uint8_t*)bits, sent, n_groups, records, out, vs_sent);
 }
+
+/* ---- line formats, host helpers (include/lnsfaid.h "line-format decode") ----
+ * Byte by byte, so that host pointers of any alignment do and the little-endian word order of the formats is spelled out: bit b
+ * of word w is bit b % 8 of byte 4 w + b / 8. */
+static int line_code_rules(const lnsfaid_code* c, int32_t format)
+{
+    if (!c || (format != LNSFAID_LINE_HARD && format != LNSFAID_LINE_LLR4)) return LNSFAID_E_INVAL;
+    if (c->n_check <= 0 || c->n_var <= c->n_check || c->puncture_tail < 0 || c->puncture_tail >= c->n_var) return LNSFAID_E_INVAL;
+    if ((c->n_var - c->puncture_tail) % 32 != 0 || (c->n_var - c->n_check) % 32 != 0) return LNSFAID_E_INVAL;
+    return LNSFAID_OK;
+}
+
+/* element of fixInput / llr4 that holds code bit k of codeword cw: [32][K] information LLRs, then [32][M] parity LLRs per group */
+static size_t line_group_element(size_t cw, size_t k, size_t N, size_t K)
+{
+    const size_t g = cw / LNSFAID_GROUP, m = cw % LNSFAID_GROUP;
+    return g * LNSFAID_GROUP * N + (k < K ? m * K + k : LNSFAID_GROUP * K + m * (N - K) + (k - K));
+}
+
+int lnsfaid_line_from_fixinput(const lnsfaid_code* code, const int8_t* fixInput, size_t n_codewords, int32_t format, void* line)
+{
+    const int rc = line_code_rules(code, format);
+    if (rc) return rc;
+    if (n_codewords == 0) return LNSFAID_OK;
+    if (!fixInput || !line) return LNSFAID_E_INVAL;
+    const size_t N = (size_t)code->n_var, K = N - (size_t)code->n_check, L = N - (size_t)code->puncture_tail;
+    uint8_t* out = (uint8_t*)line;
+    for (size_t cw = 0; cw < n_codewords; ++cw) {
+        if (format == LNSFAID_LINE_LLR4) {
+            uint8_t* o = out + cw * (L / 2);
+            for (size_t k = 0; k < L; k += 2) {
+                const int a = fixInput[line_group_element(cw, k, N, K)], b = fixInput[line_group_element(cw, k + 1, N, K)];
+                if (a < -8 || a > 7 || b < -8 || b > 7) return LNSFAID_E_INVAL;
+                o[k / 2] = (uint8_t)((a & 15) | ((b & 15) << 4));
+            }
+        } else {
+            uint8_t* o = out + cw * (L / 8);
+            for (size_t k = 0; k < L; k += 8) {
+                unsigned v = 0;
+                for (size_t b = 0; b < 8; ++b) v |= (unsigned)(fixInput[line_group_element(cw, k + b, N, K)] > 0) << b;
+                o[k / 8] = (uint8_t)v;
+            }
+        }
+    }
+    return LNSFAID_OK;
+}
+
+int lnsfaid_line_to_llr4(const lnsfaid_code* code, const void* line, int32_t format, int32_t magnitude, size_t n_codewords,
+                         uint8_t* llr4)
+{
+    const int rc = line_code_rules(code, format);
+    if (rc) return rc;
+    if (format == LNSFAID_LINE_HARD && (magnitude < 1 || magnitude > 7)) return LNSFAID_E_INVAL;
+    if (n_codewords == 0) return LNSFAID_OK;
+    if (!line || !llr4) return LNSFAID_E_INVAL;
+    const size_t N = (size_t)code->n_var, K = N - (size_t)code->n_check, L = N - (size_t)code->puncture_tail;
+    const size_t n_groups = (n_codewords + LNSFAID_GROUP - 1) / LNSFAID_GROUP;
+    const uint8_t* in = (const uint8_t*)line;
+    memset(llr4, 0, n_groups * LNSFAID_GROUP * N / 2); /* the punctured tail and the padding codewords: nibble 0 */
+    for (size_t cw = 0; cw < n_codewords; ++cw)
+        for (size_t k = 0; k < L; ++k) {
+            unsigned nib;
+            if (format == LNSFAID_LINE_LLR4) nib = (in[cw * (L / 2) + k / 2] >> (k % 2 ? 4 : 0)) & 15u;
+            else nib = (unsigned)(((in[cw * (L / 8) + k / 8] >> (k % 8)) & 1) ? magnitude : -magnitude) & 15u;
+            const size_t e = line_group_element(cw, k, N, K);
+            llr4[e / 2] |= (uint8_t)(nib << (e % 2 ? 4 : 0));
+        }
+    return LNSFAID_OK;
+}

@@ -15,6 +15,7 @@ GROUP = 32
 MSG_REGISTERS, MSG_HBM = 1, 2  # lnsfaid_select_message_store
 ZERO_SHIFT_ON, ZERO_SHIFT_OFF, ZERO_SHIFT_LOOP, ZERO_SHIFT_STATIC = 1, 2, 3, 4  # lnsfaid_select_zero_shift
 STOP_GROUP, STOP_CODEWORD = 0, 1  # lnsfaid_set_early_stop
+LINE_HARD, LINE_LLR4 = 0, 1  # lnsfaid_decode_line: one bit / one 4-bit LLR per transmitted code bit
 
 
 class Code(C.Structure):
@@ -61,6 +62,10 @@ class CodewordStats(C.Structure):
     _fields_ = [("iterations", C.c_int32), ("bf_iterations", C.c_int32), ("unsatisfied", C.c_int32)]
 
 
+class LineStats(C.Structure):
+    _fields_ = [("iterations", C.c_int32), ("bf_iterations", C.c_int32), ("unsatisfied", C.c_int32), ("corrected", C.c_int32)]
+
+
 # every symbol include/lnsfaid.h declares: name -> (restype, argtypes)
 SYMBOLS = {
     "lnsfaid_code_50gpon": (C.c_int, [C.POINTER(Code), C.POINTER(C.c_uint16), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
@@ -87,6 +92,10 @@ SYMBOLS = {
     "lnsfaid_pack_llr4": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "lnsfaid_unpack_bits": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
     "lnsfaid_pack_bits": (C.c_int, [C.c_void_p, C.c_size_t, C.c_void_p]),
+    "lnsfaid_decode_line": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lnsfaid_decode_line_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lnsfaid_line_from_fixinput": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
+    "lnsfaid_line_to_llr4": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_int32, C.c_int32, C.c_size_t, C.c_void_p]),
     "lnsfaid_frontend_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_size_t, C.c_int32,
                                           C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "lnsfaid_frontend_device_states": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_size_t, C.c_int32,
@@ -270,6 +279,52 @@ def pack_bits(input_bits, lib=None):
     rc = lib.lnsfaid_pack_bits(input_bits.ctypes.data, input_bits.size, out.ctypes.data)
     if rc != 0:
         raise ValueError("lnsfaid_pack_bits failed: %d" % rc)
+    return out
+
+
+def line_stats_dtype():
+    """numpy view of lnsfaid_line_stats"""
+    import numpy as np
+    return np.dtype([("iterations", np.int32), ("bf_iterations", np.int32), ("unsatisfied", np.int32), ("corrected", np.int32)])
+
+
+def line_sizes(code, fmt):
+    """(elements of `line` per codeword, their numpy type, payload words per codeword) for a Code struct and a format"""
+    import numpy as np
+    L, K = code.n_var - code.puncture_tail, code.n_var - code.n_check
+    return (L // 32, np.uint32, K // 32) if fmt == LINE_HARD else (L // 2, np.uint8, K // 32)
+
+
+def line_from_fixinput(code, fix_input, n_codewords, fmt, lib=None):
+    """lnsfaid_line_from_fixinput: int8 fixInput of ceil(n_codewords / 32) groups -> line (uint32 words for LINE_HARD, uint8 for
+    LINE_LLR4) of n_codewords codewords; code is a Code struct (Code50GPON().code)"""
+    import numpy as np
+    lib = lib or load()
+    fix_input = np.ascontiguousarray(fix_input, dtype=np.int8)
+    groups = (n_codewords + GROUP - 1) // GROUP
+    if fix_input.size != groups * GROUP * code.n_var:
+        raise ValueError("lnsfaid_line_from_fixinput: fix_input has %d bytes, not %d" % (fix_input.size, groups * GROUP * code.n_var))
+    per, dtype, _ = line_sizes(code, fmt)
+    out = np.empty(n_codewords * per, dtype=dtype)
+    rc = lib.lnsfaid_line_from_fixinput(C.byref(code), fix_input.ctypes.data, n_codewords, fmt, out.ctypes.data)
+    if rc != 0:
+        raise ValueError("lnsfaid_line_from_fixinput failed: %d" % rc)
+    return out
+
+
+def line_to_llr4(code, line, fmt, magnitude, n_codewords, lib=None):
+    """lnsfaid_line_to_llr4: line -> uint8 llr4 of ceil(n_codewords / 32) groups (what lnsfaid_decode_line* decodes)"""
+    import numpy as np
+    lib = lib or load()
+    per, dtype, _ = line_sizes(code, fmt)
+    line = np.ascontiguousarray(line, dtype=dtype)
+    if line.size != n_codewords * per:
+        raise ValueError("lnsfaid_line_to_llr4: line has %d elements, not %d" % (line.size, n_codewords * per))
+    groups = (n_codewords + GROUP - 1) // GROUP
+    out = np.empty(groups * GROUP * code.n_var // 2, dtype=np.uint8)
+    rc = lib.lnsfaid_line_to_llr4(C.byref(code), line.ctypes.data, fmt, magnitude, n_codewords, out.ctypes.data)
+    if rc != 0:
+        raise ValueError("lnsfaid_line_to_llr4 failed: %d" % rc)
     return out
 
 
@@ -512,6 +567,25 @@ class Decoder:
     def decode_codewords_packed_device(self, d_llr4_ptr, n_groups, d_bits_ptr, d_cw_stats_ptr=None):
         self._check(self.lib.lnsfaid_decode_codewords_packed_device(self.ctx, d_llr4_ptr, n_groups, d_bits_ptr, d_cw_stats_ptr),
                     "lnsfaid_decode_codewords_packed_device")
+
+    def decode_line(self, line, fmt, n_codewords, magnitude=4, with_bits=False, with_stats=True):
+        """lnsfaid_decode_line: line uint32 words (LINE_HARD) or uint8 (LINE_LLR4), any number of codewords.  Returns (payload
+        uint32 [n_codewords, K / 32], packed decisions uint32 [n_codewords, n_var / 32] or None, lnsfaid_line_stats array or None)"""
+        import numpy as np
+        code = self.code50.code
+        per, dtype, k_words = line_sizes(code, fmt)
+        assert line.dtype == dtype and line.size == n_codewords * per and line.flags.c_contiguous
+        payload = np.empty((n_codewords, k_words), dtype=np.uint32)
+        bits = np.empty((n_codewords, code.n_var // 32), dtype=np.uint32) if with_bits else None
+        stats = np.zeros(n_codewords, dtype=line_stats_dtype()) if with_stats else None
+        self._check(self.lib.lnsfaid_decode_line(self.ctx, line.ctypes.data, fmt, magnitude, n_codewords, payload.ctypes.data,
+                                                 bits.ctypes.data if with_bits else None, stats.ctypes.data if with_stats else None),
+                    "lnsfaid_decode_line")
+        return payload, bits, stats
+
+    def decode_line_device(self, d_line_ptr, fmt, n_codewords, d_payload_ptr, d_bits_ptr=None, d_stats_ptr=None, magnitude=4):
+        self._check(self.lib.lnsfaid_decode_line_device(self.ctx, d_line_ptr, fmt, magnitude, n_codewords, d_payload_ptr, d_bits_ptr,
+                                                        d_stats_ptr), "lnsfaid_decode_line_device")
 
     def count_errors_packed(self, bits, msg, n_groups):
         """lnsfaid_count_errors_packed: bits uint32 (decode_packed), msg uint8 (pack_bits) or None for the all-zero codeword"""
