@@ -308,6 +308,40 @@ int lnsfaid_line_from_fixinput(const lnsfaid_code* code, const int8_t* fixInput,
 int lnsfaid_line_to_llr4(const lnsfaid_code* code, const void* line, int32_t format, int32_t magnitude, size_t n_codewords,
                          uint8_t* llr4);
 
+/* ---- line-format encode --------------------------------------------------------------------------------
+ * The transmit side of the line-format decode: the payload bit stream in, codeword after codeword in transmission order out, any
+ * number of codewords, nothing one byte per bit.  Let L = n_var - puncture_tail (50G-PON: 17 280), K = n_var - n_check (14 592) and
+ * N = n_var (17 664).  All three must be multiples of 32 and L must not be below K (the information bits are all transmitted),
+ * LNSFAID_E_INVAL otherwise.
+ *   payload  exactly the payload of lnsfaid_decode_line: K / 32 little-endian 32-bit words per codeword, codeword c at word
+ *            c * K / 32; bit b of word w is information bit 32 w + b.  The payloads of consecutive codewords are one contiguous bit
+ *            stream.
+ *   line     exactly LNSFAID_LINE_HARD: L / 32 words per codeword, codeword c at word c * L / 32; bit b of word w is code bit
+ *            32 w + b in the order of decodedBits.  The first K / 32 words are the payload's own words, the next (L - K) / 32 the
+ *            transmitted parity bits p = B^-1 A u (H = [A | B], see the systematic encoder below).  No gaps, no padding.
+ *   bits     optional (NULL: not written, and the punctured parity rows are not computed): the whole mother codeword in the format
+ *            of the packed decode I/O's bits, N / 32 words per codeword, codeword c at word c * N / 32.  Its first L / 32 words are
+ *            the codeword's line words, the rest the punctured parity bits: the "sent" word of a simulator, and what
+ *            lnsfaid_fec_status_packed_* and lnsfaid_count_errors_packed_* take as bits.
+ * The calls read exactly n_codewords * K / 32 words and write exactly n_codewords entries of each output, nothing outside.
+ * n_codewords: 0 (a no-op, the buffers may be NULL) .. 32 * max_groups.  LNSFAID_E_INVAL: a NULL context; more codewords than that;
+ * a NULL payload or line with n_codewords > 0; a device pointer (payload, line or bits) that is not 4-byte aligned (more alignment
+ * only widens loads and stores: 16-byte accesses when a buffer starts on 16 bytes and its codewords are a multiple of four words
+ * long).  Host pointers may have any alignment: they go through the context's packed staging buffers (one copy each way), as
+ * lnsfaid_decode_line's do.  A refused call writes nothing.
+ * B^-1 is the one the systematic encoder below derives, lazily and once per context: a code whose parity part is singular gives
+ * LNSFAID_E_CODE from these calls too, and decoding on that context is not affected.  The calls do not depend on the decoder
+ * configuration: no DecodeMethod, kernel selection (two-rows kernel, lnsfaid_select_waves(ctx, 2)) or early-stop rule refuses them
+ * or changes their output.  The device call queues on the context's stream and returns when the outputs are complete.
+ * lnsfaid_encode_line_host: host only, no context, no GPU, host pointers of any alignment; the definition of what the two calls
+ * above return, for any quasi-cyclic code lnsfaid_create accepts.  From the code it reads the dimensions (z included), deg,
+ * deg_rows and pos_vn; circ is what lnsfaid_code_parity_inverse returned for that code (a NULL circ or circ_bytes below
+ * mb * mb * z / 8, mb = n_check / z: LNSFAID_E_INVAL, n_codewords 0 included).  No limit on n_codewords. */
+int lnsfaid_encode_line(lnsfaid_ctx* ctx, const uint32_t* payload, size_t n_codewords, uint32_t* line, uint32_t* bits);
+int lnsfaid_encode_line_device(lnsfaid_ctx* ctx, const uint32_t* d_payload, size_t n_codewords, uint32_t* d_line, uint32_t* d_bits);
+int lnsfaid_encode_line_host(const lnsfaid_code* code, const uint8_t* circ, size_t circ_bytes, const uint32_t* payload,
+                             size_t n_codewords, uint32_t* line, uint32_t* bits);
+
 /* ---- front-end on the device (optional, the host generator stays the parity source) ---- */
 
 /*

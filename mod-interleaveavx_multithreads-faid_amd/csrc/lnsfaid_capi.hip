@@ -73,6 +73,9 @@ extern "C" void lf_frontend_fastpath_assumed(double* eps2);
 extern "C" hipError_t lf_launch_encode(const LfDevCode* d_code, int n_check, const uint32_t* d_bsup, const uint32_t* d_bsup_off,
                                        const int8_t* d_in, const unsigned long long* d_keys, size_t n_groups, int8_t* d_out,
                                        int8_t* d_info, hipStream_t stream);
+extern "C" hipError_t lf_launch_encode_line(const LfDevCode* d_code, int n_check, const uint32_t* d_bsup, const uint32_t* d_bsup_off,
+                                            const uint32_t* d_payload, size_t n_codewords, uint32_t* d_line, uint32_t* d_bits,
+                                            hipStream_t stream);
 
 #include <atomic>
 #include <chrono>
@@ -2342,6 +2345,55 @@ extern "C" int lnsfaid_encode(lnsfaid_ctx* ctx, const int8_t* inputBits, size_t 
     HIP_TRY(lf_launch_encode(ctx->d_code, ctx->n_check, ctx->d_enc_sup, ctx->d_enc_off, ctx->d_io_in, nullptr, n_groups, ctx->d_io_out,
                              nullptr, ctx->stream));
     HIP_TRY(hipMemcpyAsync(outputBits, ctx->d_io_out, n_groups * LNSFAID_GROUP * (size_t)ctx->n_var, hipMemcpyDeviceToHost, ctx->stream));
+    return stream_wait(ctx);
+}
+
+/* ---- line-format encode (include/lnsfaid.h "line-format encode", DESIGN.md 3.15, lnsfaid_encoder_line.hip) ---------------- */
+/* everything that can be refused without looking at the buffers; 1: nothing to do.  Nothing of the decoder configuration. */
+static int encode_line_rules(const lnsfaid_ctx* ctx, size_t n_codewords)
+{
+    if (!ctx) return LNSFAID_E_INVAL;
+    const int L = ctx->n_var - ctx->hcode.puncture_tail;
+    if (L % 32 != 0 || ctx->k_info % 32 != 0 || ctx->n_var % 32 != 0 || L < ctx->k_info) return LNSFAID_E_INVAL;
+    if (n_codewords > ctx->max_groups * LNSFAID_GROUP) return LNSFAID_E_INVAL;
+    return n_codewords == 0 ? 1 : LNSFAID_OK;
+}
+
+extern "C" int lnsfaid_encode_line_device(lnsfaid_ctx* ctx, const uint32_t* d_payload, size_t n_codewords, uint32_t* d_line, uint32_t* d_bits)
+{
+    int rc = encode_line_rules(ctx, n_codewords);
+    if (rc) return rc < 0 ? rc : LNSFAID_OK;
+    if (!d_payload || !d_line) return LNSFAID_E_INVAL;
+    if (!dword_aligned(d_payload) || !dword_aligned(d_line) || !dword_aligned(d_bits)) return LNSFAID_E_INVAL;
+    rc = ensure_encoder(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(lf_launch_encode_line(ctx->d_code, ctx->n_check, ctx->d_enc_sup, ctx->d_enc_off, d_payload, n_codewords, d_line, d_bits,
+                                  ctx->stream));
+    return stream_wait(ctx);
+}
+
+/* host buffers of any alignment: one copy each way through the packed staging buffers, on the context's own stream.  d_pk_in
+ * (n_var / 2 bytes per codeword) holds the payload of 32 * max_groups codewords and, behind it, their line; d_pk_out their bits. */
+extern "C" int lnsfaid_encode_line(lnsfaid_ctx* ctx, const uint32_t* payload, size_t n_codewords, uint32_t* line, uint32_t* bits)
+{
+    int rc = encode_line_rules(ctx, n_codewords);
+    if (rc) return rc < 0 ? rc : LNSFAID_OK;
+    if (!payload || !line) return LNSFAID_E_INVAL;
+    rc = ensure_encoder(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipSetDevice(ctx->device));
+    rc = ensure_packed_io(ctx);
+    if (rc) return rc;
+    const size_t k_bytes = (size_t)ctx->k_info / 8, n_bytes = (size_t)ctx->n_var / 8;
+    const size_t l_bytes = (size_t)(ctx->n_var - ctx->hcode.puncture_tail) / 8;
+    uint32_t* d_payload = (uint32_t*)ctx->d_pk_in;
+    uint32_t* d_line = (uint32_t*)(ctx->d_pk_in + ctx->max_groups * LNSFAID_GROUP * k_bytes); /* a multiple of 128 bytes in */
+    HIP_TRY(hipMemcpyAsync(d_payload, payload, n_codewords * k_bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(lf_launch_encode_line(ctx->d_code, ctx->n_check, ctx->d_enc_sup, ctx->d_enc_off, d_payload, n_codewords, d_line,
+                                  bits ? ctx->d_pk_out : nullptr, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(line, d_line, n_codewords * l_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (bits) HIP_TRY(hipMemcpyAsync(bits, ctx->d_pk_out, n_codewords * n_bytes, hipMemcpyDeviceToHost, ctx->stream));
     return stream_wait(ctx);
 }
 

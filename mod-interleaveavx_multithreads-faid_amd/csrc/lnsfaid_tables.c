@@ -324,3 +324,83 @@ int lnsfaid_line_to_llr4(const lnsfaid_code* code, const void* line, int32_t for
         }
     return LNSFAID_OK;
 }
+
+/* ---- line-format encode, host form (include/lnsfaid.h "line-format encode") ----
+ * The definition of what lnsfaid_encode_line* return, for any quasi-cyclic code: s = A u row by row from pos_vn (the entries below
+ * K), then p[a z + t] = XOR over the set bits (b, c) of block row a of circ of s[b z + (c + t) mod z].  Nothing of the built-in code
+ * is used.  Bytes in and out, so that host pointers of any alignment do: bit b of word w is bit b % 8 of byte 4 w + b / 8. */
+int lnsfaid_encode_line_host(const lnsfaid_code* code, const uint8_t* circ, size_t circ_bytes, const uint32_t* payload,
+                             size_t n_codewords, uint32_t* line, uint32_t* bits)
+{
+    int rc = line_code_rules(code, LNSFAID_LINE_HARD);
+    if (rc) return rc;
+    rc = fec_code_rules(code, 1);
+    if (rc) return rc;
+    if (code->z <= 0 || code->z % 8 != 0 || code->n_check % code->z != 0 || code->puncture_tail > code->n_check) return LNSFAID_E_INVAL;
+    const size_t N = (size_t)code->n_var, M = (size_t)code->n_check, K = N - M, L = N - (size_t)code->puncture_tail;
+    const size_t z = (size_t)code->z, mb = M / z;
+    if (!circ || circ_bytes < mb * mb * (z / 8)) return LNSFAID_E_INVAL;
+    if (n_codewords == 0) return LNSFAID_OK;
+    if (!payload || !line) return LNSFAID_E_INVAL;
+    const size_t n_par = bits ? M : L - K; /* parity rows that leave: without bits the punctured tail is never formed */
+    /* the support of circ as offsets into s2, where every block of s is stored twice in a row so that (c + t) needs no modulo */
+    size_t n_sup = 0;
+    for (size_t i = 0; i < mb * mb * (z / 8); ++i)
+        for (unsigned v = circ[i]; v; v &= v - 1) n_sup += 1;
+    uint32_t* sup = (uint32_t*)malloc((n_sup + 1) * sizeof(uint32_t));
+    size_t* sup_off = (size_t*)malloc((mb + 1) * sizeof(size_t));
+    uint8_t* s2 = (uint8_t*)malloc(2 * M);
+    uint8_t* p = (uint8_t*)malloc(M);
+    if (!sup || !sup_off || !s2 || !p) {
+        free(sup); free(sup_off); free(s2); free(p);
+        return LNSFAID_E_NOMEM;
+    }
+    n_sup = 0;
+    for (size_t a = 0; a < mb; ++a) {
+        sup_off[a] = n_sup;
+        for (size_t b = 0; b < mb; ++b)
+            for (size_t c = 0; c < z; ++c)
+                if ((circ[(a * mb + b) * (z / 8) + c / 8] >> (c % 8)) & 1u) sup[n_sup++] = (uint32_t)(b * 2 * z + c);
+    }
+    sup_off[mb] = n_sup;
+    const uint8_t* in = (const uint8_t*)payload;
+    for (size_t cw = 0; cw < n_codewords; ++cw) {
+        const uint8_t* u = in + cw * (K / 8);
+        size_t e = 0, r = 0;
+        for (int d = 0; d < code->nb_degres; ++d)
+            for (int i = 0; i < code->deg_rows[d]; ++i, ++r) {
+                unsigned parity = 0;
+                for (int j = 0; j < code->deg[d]; ++j) {
+                    const size_t k = code->pos_vn[e++];
+                    if (k < K) parity ^= (unsigned)(u[k / 8] >> (k % 8)) & 1u;
+                }
+                s2[(r / z) * 2 * z + r % z] = s2[(r / z) * 2 * z + z + r % z] = (uint8_t)parity;
+            }
+        for (size_t a = 0; a * z < n_par; ++a) {
+            uint8_t* pa = p + a * z;
+            memset(pa, 0, z);
+            for (size_t i = sup_off[a]; i < sup_off[a + 1]; ++i) {
+                const uint8_t* sr = s2 + sup[i];
+                for (size_t t = 0; t < z; ++t) pa[t] ^= sr[t];
+            }
+        }
+        uint8_t* lo = (uint8_t*)line + cw * (L / 8);
+        memcpy(lo, u, K / 8);
+        for (size_t k = 0; k < L - K; k += 8) {
+            unsigned v = 0;
+            for (size_t b = 0; b < 8; ++b) v |= (unsigned)p[k + b] << b;
+            lo[(K + k) / 8] = (uint8_t)v;
+        }
+        if (bits) {
+            uint8_t* bo = (uint8_t*)bits + cw * (N / 8);
+            memcpy(bo, u, K / 8);
+            for (size_t k = 0; k < M; k += 8) {
+                unsigned v = 0;
+                for (size_t b = 0; b < 8; ++b) v |= (unsigned)p[k + b] << b;
+                bo[(K + k) / 8] = (uint8_t)v;
+            }
+        }
+    }
+    free(sup); free(sup_off); free(s2); free(p);
+    return LNSFAID_OK;
+}

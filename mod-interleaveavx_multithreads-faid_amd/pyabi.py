@@ -96,6 +96,9 @@ SYMBOLS = {
     "lnsfaid_decode_line_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_size_t, C.c_void_p, C.c_void_p, C.c_void_p]),
     "lnsfaid_line_from_fixinput": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_size_t, C.c_int32, C.c_void_p]),
     "lnsfaid_line_to_llr4": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_int32, C.c_int32, C.c_size_t, C.c_void_p]),
+    "lnsfaid_encode_line": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "lnsfaid_encode_line_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "lnsfaid_encode_line_host": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "lnsfaid_frontend_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_size_t, C.c_int32,
                                           C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "lnsfaid_frontend_device_states": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_size_t, C.c_int32,
@@ -326,6 +329,40 @@ def line_to_llr4(code, line, fmt, magnitude, n_codewords, lib=None):
     if rc != 0:
         raise ValueError("lnsfaid_line_to_llr4 failed: %d" % rc)
     return out
+
+
+def code_parity_inverse(code, lib=None):
+    """lnsfaid_code_parity_inverse: the compact B^-1 of a Code struct as uint8 [mb * mb * z / 8]; ValueError with the library's code
+    (-2 for a singular parity part)"""
+    import numpy as np
+    lib = lib or load()
+    mb = code.n_check // code.z
+    circ = np.zeros(mb * mb * code.z // 8, dtype=np.uint8)
+    rc = lib.lnsfaid_code_parity_inverse(C.byref(code), circ.ctypes.data, circ.size)
+    if rc != 0:
+        raise ValueError("lnsfaid_code_parity_inverse failed: %d" % rc)
+    return circ
+
+
+def encode_line_host(code, payload, n_codewords, with_bits=False, lib=None, circ=None):
+    """lnsfaid_encode_line_host: payload uint32 [n_codewords, K / 32] -> (line uint32 [n_codewords, L / 32], the whole codewords
+    uint32 [n_codewords, n_var / 32] or None); code is a Code struct.  B^-1 is derived with lnsfaid_code_parity_inverse unless the
+    caller passes the `circ` of an earlier code_parity_inverse(code)."""
+    import numpy as np
+    lib = lib or load()
+    if circ is None:
+        circ = code_parity_inverse(code, lib)
+    L, K = code.n_var - code.puncture_tail, code.n_var - code.n_check
+    payload = np.ascontiguousarray(payload, dtype=np.uint32)
+    if payload.size != n_codewords * (K // 32):
+        raise ValueError("lnsfaid_encode_line_host: payload has %d words, not %d" % (payload.size, n_codewords * (K // 32)))
+    line = np.empty((n_codewords, L // 32), dtype=np.uint32)
+    bits = np.empty((n_codewords, code.n_var // 32), dtype=np.uint32) if with_bits else None
+    rc = lib.lnsfaid_encode_line_host(C.byref(code), circ.ctypes.data, circ.size, payload.ctypes.data, n_codewords, line.ctypes.data,
+                                      bits.ctypes.data if with_bits else None)
+    if rc != 0:
+        raise ValueError("lnsfaid_encode_line_host failed: %d" % rc)
+    return line, bits
 
 
 def _demap_host(fn_name, packed, n_var, n_check, interleave, rx, n_groups, mod_type, scale, lib):
@@ -586,6 +623,23 @@ class Decoder:
     def decode_line_device(self, d_line_ptr, fmt, n_codewords, d_payload_ptr, d_bits_ptr=None, d_stats_ptr=None, magnitude=4):
         self._check(self.lib.lnsfaid_decode_line_device(self.ctx, d_line_ptr, fmt, magnitude, n_codewords, d_payload_ptr, d_bits_ptr,
                                                         d_stats_ptr), "lnsfaid_decode_line_device")
+
+    def encode_line(self, payload, n_codewords, with_bits=False):
+        """lnsfaid_encode_line: payload uint32 [n_codewords, K / 32] (the payload of decode_line).  Returns (line uint32
+        [n_codewords, L / 32] in the LINE_HARD format, the whole codewords uint32 [n_codewords, n_var / 32] or None)"""
+        import numpy as np
+        code = self.code50.code
+        L, K = code.n_var - code.puncture_tail, code.n_var - code.n_check
+        assert payload.dtype == np.uint32 and payload.size == n_codewords * (K // 32) and payload.flags.c_contiguous
+        line = np.empty((n_codewords, L // 32), dtype=np.uint32)
+        bits = np.empty((n_codewords, code.n_var // 32), dtype=np.uint32) if with_bits else None
+        self._check(self.lib.lnsfaid_encode_line(self.ctx, payload.ctypes.data, n_codewords, line.ctypes.data,
+                                                 bits.ctypes.data if with_bits else None), "lnsfaid_encode_line")
+        return line, bits
+
+    def encode_line_device(self, d_payload_ptr, n_codewords, d_line_ptr, d_bits_ptr=None):
+        self._check(self.lib.lnsfaid_encode_line_device(self.ctx, d_payload_ptr, n_codewords, d_line_ptr, d_bits_ptr),
+                    "lnsfaid_encode_line_device")
 
     def count_errors_packed(self, bits, msg, n_groups):
         """lnsfaid_count_errors_packed: bits uint32 (decode_packed), msg uint8 (pack_bits) or None for the all-zero codeword"""
