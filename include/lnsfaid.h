@@ -342,6 +342,66 @@ int lnsfaid_encode_line_device(lnsfaid_ctx* ctx, const uint32_t* d_payload, size
 int lnsfaid_encode_line_host(const lnsfaid_code* code, const uint8_t* circ, size_t circ_bytes, const uint32_t* payload,
                              size_t n_codewords, uint32_t* line, uint32_t* bits);
 
+/* ---- line-format link -----------------------------------------------------------------------------------
+ * What sits between and around lnsfaid_encode_line_device and lnsfaid_decode_line_device, so that a hard-decision sweep - post-FEC
+ * error rate against the pre-FEC bit error rate of a binary symmetric channel (BSC) - runs on the device in the line's own formats:
+ * payload drawn on the device -> encode_line -> BSC -> decode_line (LNSFAID_LINE_HARD) -> counters; only the counters leave it.
+ * L = n_var - puncture_tail (50G-PON: 17 280) and K = n_var - n_check (14 592) as in the two sections above.
+ *
+ * Generator (stateless, counter-based).  With mix64 as defined for lnsfaid_frontend_random_frames below and all arithmetic mod 2^64:
+ *   cwkey(key, C, d)   = mix64(mix64(key + d) + (C + 1) * 0xD1B54A32D192ED03)      d = 1: payload, d = 2: BSC
+ *   draw(key, C, d, q) = mix64(cwkey(key, C, d) + (q + 1) * 0x9E3779B97F4A7C15)
+ * C = first_codeword + i is the global number of codeword i of the call, a uint64_t that wraps.  A run split into calls of any size,
+ * or over ranks, therefore produces the bytes of the one-shot run.
+ *
+ * Payload source.  payload is the payload of the line calls (K / 32 words per codeword, codeword i of the call at word i * K / 32).
+ * For codeword C, word 2 q is the low half of draw(key, C, 1, q) and word 2 q + 1 its high half; an odd K / 32 leaves the last high
+ * half unused.  Exactly n_codewords * K / 32 words are written.
+ *
+ * BSC.  line_in and line_out are LNSFAID_LINE_HARD (L / 32 words per codeword).  Position 2 q of codeword C (bit (2 q) % 32 of its word
+ * (2 q) / 32) is inverted iff (uint32_t)draw(key, C, 2, q) < threshold, position 2 q + 1 iff draw(key, C, 2, q) >> 32 < threshold, for
+ * q < L / 2: every position flips with probability exactly threshold / 2^32, independently.  threshold 0 copies the line.
+ *   line_out == line_in is allowed (in place); any other overlap of the two is undefined.
+ *   flips        optional uint32_t [n_codewords] (the _device form: a device pointer): the positions inverted per codeword.
+ *   total_flips  optional host uint64_t, ADDED to: the positions inverted in the call.
+ * lnsfaid_line_bsc_threshold (host only): *threshold = floor(p * 2^32) for 0 <= p < 1; LNSFAID_E_INVAL otherwise (1.0, a negative p,
+ * NaN) and for a NULL threshold, which is then not written.
+ *
+ * Counters.  payload and sent are payload streams (K / 32 words per codeword); sent == NULL means the all-zero payload.  stats is the
+ * lnsfaid_line_stats [n_codewords] of the decode call, or NULL.  errors, fec and vs_sent are host uint64_t[4]; each may be NULL, each
+ * is ADDED to, and each is four words so that lnsfaid_allreduce_counters sums it unchanged.  w = the bits of a codeword's payload that
+ * differ from sent:
+ *   errors   the words of lnsfaid_count_errors: [0] TestFrame += n_codewords, [1] ErrorFrame w > 0, [2] ErrorBits += w,
+ *            [3] LT3ErrBitFrame w == 1 or w == 2.
+ *   fec      the words of lnsfaid_fec_status_*'s out: [0] TotalCodewords += n_codewords, [1] UncorrectableCodewords unsatisfied > 0,
+ *            [2] CorrectedCodewords unsatisfied == 0 and corrected > 0, [3] CorrectedBits the sum of corrected over unsatisfied == 0.
+ *   vs_sent  as in that section: [0] TestFrame += n_codewords, [1] ErrorFrame w > 0, [2] UndetectedErrorFrame w > 0 and
+ *            unsatisfied == 0, [3] FalseAlarmFrame w == 0 and unsatisfied > 0.
+ * fec or vs_sent non-NULL with stats NULL is LNSFAID_E_INVAL.  iterations and bf_iterations of stats are not read.
+ *
+ * Rules for all of these, as for the line calls: n_codewords 0 is a no-op (every buffer may be NULL).  LNSFAID_E_INVAL: a NULL
+ * context or code; L or K not a multiple of 32; more than 32 * max_groups codewords (device forms); a NULL required buffer (payload,
+ * line_in, line_out); a device pointer, optional ones included, that is not 4-byte aligned (more alignment only widens loads and
+ * stores: 16-byte accesses when every buffer of the call starts on 16 bytes and its codewords are a multiple of four words long,
+ * 8-byte ones likewise).  A refused call writes nothing and adds nothing.
+ * The device forms queue on the context's stream and return when their host outputs are complete (the device outputs are complete
+ * on the stream by then); no synchronisation by the caller is needed between them and the line calls.  They do not depend on the
+ * decoder configuration.  Their accumulators - the twelve counters, read back in one copy, and the flipped bits - live on the
+ * context's device, are allocated at first use and freed by lnsfaid_destroy.
+ * The host forms need no context and no GPU, read only n_var, n_check and puncture_tail of the code, take pointers of any alignment
+ * and have no limit on n_codewords: they are the definition of what the device forms return. */
+int lnsfaid_line_payload_random_device(lnsfaid_ctx* ctx, uint64_t key, uint64_t first_codeword, size_t n_codewords, uint32_t* d_payload);
+int lnsfaid_line_payload_random_host(const lnsfaid_code* code, uint64_t key, uint64_t first_codeword, size_t n_codewords, uint32_t* payload);
+int lnsfaid_line_bsc_threshold(double p, uint32_t* threshold);
+int lnsfaid_line_bsc_device(lnsfaid_ctx* ctx, const uint32_t* d_line_in, size_t n_codewords, uint64_t key, uint64_t first_codeword,
+                            uint32_t threshold, uint32_t* d_line_out, uint32_t* d_flips, uint64_t* total_flips);
+int lnsfaid_line_bsc_host(const lnsfaid_code* code, const uint32_t* line_in, size_t n_codewords, uint64_t key, uint64_t first_codeword,
+                          uint32_t threshold, uint32_t* line_out, uint32_t* flips, uint64_t* total_flips);
+int lnsfaid_line_count_errors_device(lnsfaid_ctx* ctx, const uint32_t* d_payload, const uint32_t* d_sent, const lnsfaid_line_stats* d_stats,
+                                     size_t n_codewords, uint64_t errors[4], uint64_t fec[4], uint64_t vs_sent[4]);
+int lnsfaid_line_count_errors_host(const lnsfaid_code* code, const uint32_t* payload, const uint32_t* sent, const lnsfaid_line_stats* stats,
+                                   size_t n_codewords, uint64_t errors[4], uint64_t fec[4], uint64_t vs_sent[4]);
+
 /* ---- front-end on the device (optional, the host generator stays the parity source) ---- */
 
 /*

@@ -77,6 +77,12 @@ extern "C" hipError_t lf_launch_encode_line(const LfDevCode* d_code, int n_check
                                             const uint32_t* d_payload, size_t n_codewords, uint32_t* d_line, uint32_t* d_bits,
                                             hipStream_t stream);
 
+extern "C" hipError_t lf_launch_line_bsc(const uint32_t* d_in, uint32_t* d_out, size_t n_cw, uint32_t lw, uint64_t key, uint64_t first,
+                                         uint32_t threshold, uint32_t* d_flips, unsigned long long* d_total, hipStream_t stream);
+extern "C" hipError_t lf_launch_line_payload(uint32_t* d_payload, size_t n_cw, uint32_t kw, uint64_t key, uint64_t first, hipStream_t stream);
+extern "C" hipError_t lf_launch_line_count(const uint32_t* d_payload, const uint32_t* d_sent, const lnsfaid_line_stats* d_stats, size_t n_cw,
+                                           uint32_t kw, unsigned long long* d_acc, hipStream_t stream);
+
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -193,6 +199,9 @@ struct lnsfaid_ctx {
     /* FEC status (lnsfaid_fecstatus.hip), allocated at the first lnsfaid_fec_status*_device call */
     unsigned long long* d_fec_acc = nullptr; /* out[4] then vs_sent[4] of the call in flight */
     unsigned long long* h_fec_acc = nullptr; /* pinned */
+    /* line-format link (lnsfaid_line_link.hip), allocated at the first lnsfaid_line_bsc_device / lnsfaid_line_count_errors_device call */
+    unsigned long long* d_link_acc = nullptr; /* errors[4], fec[4], vs_sent[4] of the call in flight, then the channel's flipped bits */
+    unsigned long long* h_link_acc = nullptr; /* pinned */
     /* encoder (lnsfaid_encoder.hip): support of B^-1's first rows, derived at the first encode / random-frames call */
     int enc_state = 0;                      /* 0: not derived yet, 1: on the device, LNSFAID_E_CODE: parity part singular */
     uint32_t* d_enc_sup = nullptr;          /* entries b * z + c, block row after block row */
@@ -449,6 +458,8 @@ extern "C" void lnsfaid_destroy(lnsfaid_ctx* ctx)
     (void)hipFree(ctx->d_cap_slots); (void)hipFree(ctx->d_cap_records); (void)hipFree(ctx->d_cap_payload);
     (void)hipFree(ctx->d_fec_acc);
     if (ctx->h_fec_acc) (void)hipHostFree(ctx->h_fec_acc);
+    (void)hipFree(ctx->d_link_acc);
+    if (ctx->h_link_acc) (void)hipHostFree(ctx->h_link_acc);
     if (ctx->h_remaining) (void)hipHostFree(ctx->h_remaining);
     if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -2395,6 +2406,82 @@ extern "C" int lnsfaid_encode_line(lnsfaid_ctx* ctx, const uint32_t* payload, si
     HIP_TRY(hipMemcpyAsync(line, d_line, n_codewords * l_bytes, hipMemcpyDeviceToHost, ctx->stream));
     if (bits) HIP_TRY(hipMemcpyAsync(bits, ctx->d_pk_out, n_codewords * n_bytes, hipMemcpyDeviceToHost, ctx->stream));
     return stream_wait(ctx);
+}
+
+/* ---- line-format link (include/lnsfaid.h "line-format link", DESIGN.md 3.16, lnsfaid_line_link.hip; host forms in lnsfaid_tables.c) -- */
+#define LF_LINK_ACC 13 /* twelve counters and the flipped bits */
+/* everything that can be refused without looking at the buffers; 1: nothing to do.  Nothing of the decoder configuration. */
+static int line_link_rules(const lnsfaid_ctx* ctx, size_t n_codewords)
+{
+    if (!ctx) return LNSFAID_E_INVAL;
+    const int L = ctx->n_var - ctx->hcode.puncture_tail;
+    if (L <= 0 || L % 32 != 0 || ctx->k_info <= 0 || ctx->k_info % 32 != 0) return LNSFAID_E_INVAL;
+    if (n_codewords > ctx->max_groups * LNSFAID_GROUP || n_codewords > 0x7fffffffull) return LNSFAID_E_INVAL;
+    return n_codewords == 0 ? 1 : LNSFAID_OK;
+}
+
+/* each on its own: a call after a failed allocation asks again for what is still missing */
+static int ensure_link_acc(lnsfaid_ctx* ctx)
+{
+    if (!ctx->d_link_acc) HIP_TRY(hipMalloc(&ctx->d_link_acc, LF_LINK_ACC * sizeof(unsigned long long)));
+    if (!ctx->h_link_acc) HIP_TRY(hipHostMalloc((void**)&ctx->h_link_acc, LF_LINK_ACC * sizeof(unsigned long long), hipHostMallocDefault));
+    return LNSFAID_OK;
+}
+
+extern "C" int lnsfaid_line_payload_random_device(lnsfaid_ctx* ctx, uint64_t key, uint64_t first_codeword, size_t n_codewords,
+                                                  uint32_t* d_payload)
+{
+    const int rc = line_link_rules(ctx, n_codewords);
+    if (rc) return rc < 0 ? rc : LNSFAID_OK;
+    if (!d_payload || !dword_aligned(d_payload)) return LNSFAID_E_INVAL;
+    HIP_TRY(hipSetDevice(ctx->device));
+    HIP_TRY(lf_launch_line_payload(d_payload, n_codewords, (uint32_t)ctx->k_info / 32u, key, first_codeword, ctx->stream));
+    return stream_wait(ctx);
+}
+
+extern "C" int lnsfaid_line_bsc_device(lnsfaid_ctx* ctx, const uint32_t* d_line_in, size_t n_codewords, uint64_t key, uint64_t first_codeword,
+                                       uint32_t threshold, uint32_t* d_line_out, uint32_t* d_flips, uint64_t* total_flips)
+{
+    int rc = line_link_rules(ctx, n_codewords);
+    if (rc) return rc < 0 ? rc : LNSFAID_OK;
+    if (!d_line_in || !d_line_out) return LNSFAID_E_INVAL;
+    if (!dword_aligned(d_line_in) || !dword_aligned(d_line_out) || !dword_aligned(d_flips)) return LNSFAID_E_INVAL;
+    HIP_TRY(hipSetDevice(ctx->device));
+    rc = ensure_link_acc(ctx);
+    if (rc) return rc;
+    unsigned long long* d_total = ctx->d_link_acc + 12;
+    HIP_TRY(hipMemsetAsync(d_total, 0, sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(lf_launch_line_bsc(d_line_in, d_line_out, n_codewords, (uint32_t)(ctx->n_var - ctx->hcode.puncture_tail) / 32u, key, first_codeword,
+                               threshold, d_flips, d_total, ctx->stream));
+    if (total_flips) HIP_TRY(hipMemcpyAsync(ctx->h_link_acc + 12, d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    rc = stream_wait(ctx);
+    if (rc) return rc;
+    if (total_flips) *total_flips += ctx->h_link_acc[12];
+    return LNSFAID_OK;
+}
+
+extern "C" int lnsfaid_line_count_errors_device(lnsfaid_ctx* ctx, const uint32_t* d_payload, const uint32_t* d_sent,
+                                                const lnsfaid_line_stats* d_stats, size_t n_codewords, uint64_t errors[4], uint64_t fec[4],
+                                                uint64_t vs_sent[4])
+{
+    int rc = line_link_rules(ctx, n_codewords);
+    if (rc) return rc < 0 ? rc : LNSFAID_OK;
+    if (!d_payload || ((fec || vs_sent) && !d_stats)) return LNSFAID_E_INVAL;
+    if (!dword_aligned(d_payload) || !dword_aligned(d_sent) || !dword_aligned(d_stats)) return LNSFAID_E_INVAL;
+    HIP_TRY(hipSetDevice(ctx->device));
+    rc = ensure_link_acc(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(ctx->d_link_acc, 0, 12 * sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(lf_launch_line_count(d_payload, d_sent, d_stats, n_codewords, (uint32_t)ctx->k_info / 32u, ctx->d_link_acc, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->h_link_acc, ctx->d_link_acc, 12 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    rc = stream_wait(ctx);
+    if (rc) return rc;
+    for (int i = 0; i < 4; ++i) {
+        if (errors) errors[i] += ctx->h_link_acc[i];
+        if (fec) fec[i] += ctx->h_link_acc[4 + i];
+        if (vs_sent) vs_sent[i] += ctx->h_link_acc[8 + i];
+    }
+    return LNSFAID_OK;
 }
 
 extern "C" int lnsfaid_frontend_random_frames(lnsfaid_ctx* ctx, const uint64_t* keys, size_t n_streams)

@@ -404,3 +404,111 @@ int lnsfaid_encode_line_host(const lnsfaid_code* code, const uint8_t* circ, size
     free(sup); free(sup_off); free(s2); free(p);
     return LNSFAID_OK;
 }
+
+/* ---- line-format link, host forms (include/lnsfaid.h "line-format link") ----
+ * The definition of what lnsfaid_line_payload_random_device, lnsfaid_line_bsc_device and lnsfaid_line_count_errors_device return.
+ * Words are read and written byte by byte (little-endian), so host pointers of any alignment do. */
+static uint64_t link_mix64(uint64_t x)
+{
+    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
+    x ^= x >> 27; x *= 0x94D049BB133111EBull;
+    return x ^ (x >> 31);
+}
+static uint64_t link_cwkey(uint64_t key, uint64_t C, uint64_t d) { return link_mix64(link_mix64(key + d) + (C + 1u) * 0xD1B54A32D192ED03ull); }
+static uint64_t link_draw(uint64_t cwkey, uint64_t q) { return link_mix64(cwkey + (q + 1u) * 0x9E3779B97F4A7C15ull); }
+static uint32_t link_ld32(const uint8_t* p) { return (uint32_t)p[0] | (uint32_t)p[1] << 8 | (uint32_t)p[2] << 16 | (uint32_t)p[3] << 24; }
+static void link_st32(uint8_t* p, uint32_t v) { p[0] = (uint8_t)v; p[1] = (uint8_t)(v >> 8); p[2] = (uint8_t)(v >> 16); p[3] = (uint8_t)(v >> 24); }
+static uint32_t link_popcount(uint32_t v) { uint32_t n = 0; for (; v; v &= v - 1u) n += 1u; return n; }
+
+int lnsfaid_line_bsc_threshold(double p, uint32_t* threshold)
+{
+    if (!threshold || !(p >= 0.0 && p < 1.0)) return LNSFAID_E_INVAL; /* NaN fails both comparisons */
+    *threshold = (uint32_t)(p * 4294967296.0); /* exact product (a power of two), below 2^32, truncated: the floor */
+    return LNSFAID_OK;
+}
+
+int lnsfaid_line_payload_random_host(const lnsfaid_code* code, uint64_t key, uint64_t first_codeword, size_t n_codewords, uint32_t* payload)
+{
+    const int rc = line_code_rules(code, LNSFAID_LINE_HARD);
+    if (rc) return rc;
+    if (n_codewords == 0) return LNSFAID_OK;
+    if (!payload) return LNSFAID_E_INVAL;
+    const size_t kw = (size_t)(code->n_var - code->n_check) / 32;
+    uint8_t* out = (uint8_t*)payload;
+    for (size_t i = 0; i < n_codewords; ++i) {
+        const uint64_t ck = link_cwkey(key, first_codeword + (uint64_t)i, 1u);
+        for (size_t w = 0; w < kw; w += 2) {
+            const uint64_t h = link_draw(ck, (uint64_t)(w / 2));
+            link_st32(out + 4 * (i * kw + w), (uint32_t)h);
+            if (w + 1 < kw) link_st32(out + 4 * (i * kw + w + 1), (uint32_t)(h >> 32)); /* an odd K / 32 leaves the last high half unused */
+        }
+    }
+    return LNSFAID_OK;
+}
+
+int lnsfaid_line_bsc_host(const lnsfaid_code* code, const uint32_t* line_in, size_t n_codewords, uint64_t key, uint64_t first_codeword,
+                          uint32_t threshold, uint32_t* line_out, uint32_t* flips, uint64_t* total_flips)
+{
+    const int rc = line_code_rules(code, LNSFAID_LINE_HARD);
+    if (rc) return rc;
+    if (n_codewords == 0) return LNSFAID_OK;
+    if (!line_in || !line_out) return LNSFAID_E_INVAL;
+    const size_t lw = (size_t)(code->n_var - code->puncture_tail) / 32;
+    const uint8_t* in = (const uint8_t*)line_in;
+    uint8_t* out = (uint8_t*)line_out;
+    uint64_t total = 0;
+    for (size_t i = 0; i < n_codewords; ++i) {
+        const uint64_t ck = link_cwkey(key, first_codeword + (uint64_t)i, 2u);
+        uint32_t n = 0;
+        for (size_t w = 0; w < lw; ++w) {
+            uint32_t mask = 0;
+            for (uint32_t j = 0; j < 16u; ++j) { /* position 32 w + 2 j is the low half of draw q = 16 w + j, 32 w + 2 j + 1 the high half */
+                const uint64_t h = link_draw(ck, (uint64_t)(16 * w + j));
+                mask |= (uint32_t)((uint32_t)h < threshold) << (2u * j);
+                mask |= (uint32_t)((uint32_t)(h >> 32) < threshold) << (2u * j + 1u);
+            }
+            link_st32(out + 4 * (i * lw + w), link_ld32(in + 4 * (i * lw + w)) ^ mask);
+            n += link_popcount(mask);
+        }
+        if (flips) link_st32((uint8_t*)flips + 4 * i, n);
+        total += n;
+    }
+    if (total_flips) *total_flips += total;
+    return LNSFAID_OK;
+}
+
+int lnsfaid_line_count_errors_host(const lnsfaid_code* code, const uint32_t* payload, const uint32_t* sent, const lnsfaid_line_stats* stats,
+                                   size_t n_codewords, uint64_t errors[4], uint64_t fec[4], uint64_t vs_sent[4])
+{
+    const int rc = line_code_rules(code, LNSFAID_LINE_HARD);
+    if (rc) return rc;
+    if (n_codewords == 0) return LNSFAID_OK;
+    if (!payload || ((fec || vs_sent) && !stats)) return LNSFAID_E_INVAL;
+    const size_t kw = (size_t)(code->n_var - code->n_check) / 32;
+    const uint8_t* got = (const uint8_t*)payload;
+    const uint8_t* ref = (const uint8_t*)sent;
+    const uint8_t* st = (const uint8_t*)stats;
+    uint64_t e[4] = { 0, 0, 0, 0 }, f[4] = { 0, 0, 0, 0 }, v[4] = { 0, 0, 0, 0 };
+    for (size_t i = 0; i < n_codewords; ++i) {
+        uint64_t wrong = 0;
+        for (size_t w = 0; w < kw; ++w)
+            wrong += link_popcount(link_ld32(got + 4 * (i * kw + w)) ^ (ref ? link_ld32(ref + 4 * (i * kw + w)) : 0u));
+        e[0] += 1; e[1] += wrong > 0; e[2] += wrong; e[3] += wrong == 1 || wrong == 2;
+        if (st) {
+            const int32_t unsatisfied = (int32_t)link_ld32(st + sizeof(lnsfaid_line_stats) * i + 8);
+            const int32_t corrected = (int32_t)link_ld32(st + sizeof(lnsfaid_line_stats) * i + 12);
+            f[0] += 1;
+            if (unsatisfied > 0) f[1] += 1;
+            else if (unsatisfied == 0 && corrected > 0) { f[2] += 1; f[3] += (uint64_t)corrected; }
+            v[0] += 1;
+            if (wrong > 0) { v[1] += 1; v[2] += unsatisfied == 0; }
+            else v[3] += unsatisfied > 0;
+        }
+    }
+    for (int k = 0; k < 4; ++k) {
+        if (errors) errors[k] += e[k];
+        if (fec) fec[k] += f[k];
+        if (vs_sent) vs_sent[k] += v[k];
+    }
+    return LNSFAID_OK;
+}

@@ -99,6 +99,17 @@ SYMBOLS = {
     "lnsfaid_encode_line": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "lnsfaid_encode_line_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "lnsfaid_encode_line_host": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "lnsfaid_line_payload_random_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_size_t, C.c_void_p]),
+    "lnsfaid_line_payload_random_host": (C.c_int, [C.POINTER(Code), C.c_uint64, C.c_uint64, C.c_size_t, C.c_void_p]),
+    "lnsfaid_line_bsc_threshold": (C.c_int, [C.c_double, C.POINTER(C.c_uint32)]),
+    "lnsfaid_line_bsc_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
+                                          C.POINTER(C.c_uint64)]),
+    "lnsfaid_line_bsc_host": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p,
+                                        C.POINTER(C.c_uint64)]),
+    "lnsfaid_line_count_errors_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64),
+                                                   C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "lnsfaid_line_count_errors_host": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64),
+                                                 C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "lnsfaid_frontend_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_size_t, C.c_int32,
                                           C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "lnsfaid_frontend_device_states": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_size_t, C.c_int32,
@@ -363,6 +374,68 @@ def encode_line_host(code, payload, n_codewords, with_bits=False, lib=None, circ
     if rc != 0:
         raise ValueError("lnsfaid_encode_line_host failed: %d" % rc)
     return line, bits
+
+
+def line_bsc_threshold(p, lib=None):
+    """lnsfaid_line_bsc_threshold: floor(p * 2^32) for 0 <= p < 1; ValueError otherwise"""
+    lib = lib or load()
+    t = C.c_uint32()
+    rc = lib.lnsfaid_line_bsc_threshold(float(p), C.byref(t))
+    if rc != 0:
+        raise ValueError("lnsfaid_line_bsc_threshold(%r) failed: %d" % (p, rc))
+    return t.value
+
+
+def line_payload_random_host(code, key, first_codeword, n_codewords, lib=None):
+    """lnsfaid_line_payload_random_host: the payload uint32 [n_codewords, K / 32] of codewords first_codeword .. of stream `key`;
+    code is a Code struct"""
+    import numpy as np
+    lib = lib or load()
+    out = np.empty((n_codewords, (code.n_var - code.n_check) // 32), dtype=np.uint32)
+    rc = lib.lnsfaid_line_payload_random_host(C.byref(code), key, first_codeword, n_codewords, out.ctypes.data)
+    if rc != 0:
+        raise ValueError("lnsfaid_line_payload_random_host failed: %d" % rc)
+    return out
+
+
+def line_bsc_host(code, line, n_codewords, key, first_codeword, threshold, in_place=False, total=0, lib=None):
+    """lnsfaid_line_bsc_host: line uint32 [n_codewords, L / 32] (LINE_HARD) through the binary symmetric channel of stream `key`.
+    Returns (line out, flips uint32 [n_codewords], total + the positions inverted); in_place writes into `line` itself"""
+    import numpy as np
+    lib = lib or load()
+    per = (code.n_var - code.puncture_tail) // 32
+    if not in_place:
+        line = np.ascontiguousarray(line, dtype=np.uint32)
+    if line.dtype != np.uint32 or not line.flags.c_contiguous or line.size != n_codewords * per:
+        raise ValueError("lnsfaid_line_bsc_host: line must be contiguous uint32 with %d words" % (n_codewords * per))
+    out = line if in_place else np.empty_like(line)
+    flips = np.zeros(n_codewords, dtype=np.uint32)
+    t = C.c_uint64(total)
+    rc = lib.lnsfaid_line_bsc_host(C.byref(code), line.ctypes.data, n_codewords, key, first_codeword, threshold, out.ctypes.data,
+                                   flips.ctypes.data, C.byref(t))
+    if rc != 0:
+        raise ValueError("lnsfaid_line_bsc_host failed: %d" % rc)
+    return out, flips, t.value
+
+
+def line_count_errors_host(code, payload, sent, stats, n_codewords, errors=True, fec=None, vs_sent=None, lib=None):
+    """lnsfaid_line_count_errors_host: payload / sent uint32 payload streams (sent None: all-zero), stats a line_stats_dtype() array or
+    None.  errors / fec / vs_sent: True, four numbers the call adds to, or None / False for a NULL pointer.  Returns the three as
+    lists or None"""
+    import numpy as np
+    lib = lib or load()
+    kw = (code.n_var - code.n_check) // 32
+    payload = np.ascontiguousarray(payload, dtype=np.uint32)
+    sent = None if sent is None else np.ascontiguousarray(sent, dtype=np.uint32)
+    stats = None if stats is None else np.ascontiguousarray(stats, dtype=line_stats_dtype())
+    if payload.size != n_codewords * kw or (sent is not None and sent.size != payload.size) or (stats is not None and stats.size != n_codewords):
+        raise ValueError("lnsfaid_line_count_errors_host: buffer sizes do not fit %d codewords" % n_codewords)
+    e, f, v = _fec_counters(errors), _fec_counters(fec), _fec_counters(vs_sent)
+    rc = lib.lnsfaid_line_count_errors_host(C.byref(code), payload.ctypes.data, None if sent is None else sent.ctypes.data,
+                                            None if stats is None else stats.ctypes.data, n_codewords, e, f, v)
+    if rc != 0:
+        raise ValueError("lnsfaid_line_count_errors_host failed: %d" % rc)
+    return tuple(list(x) if x is not None else None for x in (e, f, v))
 
 
 def _demap_host(fn_name, packed, n_var, n_check, interleave, rx, n_groups, mod_type, scale, lib):
@@ -640,6 +713,27 @@ class Decoder:
     def encode_line_device(self, d_payload_ptr, n_codewords, d_line_ptr, d_bits_ptr=None):
         self._check(self.lib.lnsfaid_encode_line_device(self.ctx, d_payload_ptr, n_codewords, d_line_ptr, d_bits_ptr),
                     "lnsfaid_encode_line_device")
+
+    def line_payload_random_device(self, key, first_codeword, n_codewords, d_payload_ptr):
+        """lnsfaid_line_payload_random_device: the payload of codewords first_codeword .. of stream `key` into a device buffer"""
+        self._check(self.lib.lnsfaid_line_payload_random_device(self.ctx, key, first_codeword, n_codewords, d_payload_ptr),
+                    "lnsfaid_line_payload_random_device")
+
+    def line_bsc_device(self, d_line_in_ptr, n_codewords, key, first_codeword, threshold, d_line_out_ptr, d_flips_ptr=None, total=0):
+        """lnsfaid_line_bsc_device: LINE_HARD words through the binary symmetric channel of stream `key` (d_line_out_ptr may equal
+        d_line_in_ptr).  Returns total + the positions inverted"""
+        t = C.c_uint64(total)
+        self._check(self.lib.lnsfaid_line_bsc_device(self.ctx, d_line_in_ptr, n_codewords, key, first_codeword, threshold, d_line_out_ptr,
+                                                     d_flips_ptr, C.byref(t)), "lnsfaid_line_bsc_device")
+        return t.value
+
+    def line_count_errors_device(self, d_payload_ptr, d_sent_ptr, d_stats_ptr, n_codewords, errors=True, fec=None, vs_sent=None):
+        """lnsfaid_line_count_errors_device: device pointers (d_sent_ptr None: all-zero payload; d_stats_ptr the lnsfaid_line_stats of
+        decode_line_device, or None).  errors / fec / vs_sent and the result as line_count_errors_host"""
+        e, f, v = _fec_counters(errors), _fec_counters(fec), _fec_counters(vs_sent)
+        self._check(self.lib.lnsfaid_line_count_errors_device(self.ctx, d_payload_ptr, d_sent_ptr, d_stats_ptr, n_codewords, e, f, v),
+                    "lnsfaid_line_count_errors_device")
+        return tuple(list(x) if x is not None else None for x in (e, f, v))
 
     def count_errors_packed(self, bits, msg, n_groups):
         """lnsfaid_count_errors_packed: bits uint32 (decode_packed), msg uint8 (pack_bits) or None for the all-zero codeword"""
