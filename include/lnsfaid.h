@@ -402,6 +402,41 @@ int lnsfaid_line_count_errors_device(lnsfaid_ctx* ctx, const uint32_t* d_payload
 int lnsfaid_line_count_errors_host(const lnsfaid_code* code, const uint32_t* payload, const uint32_t* sent, const lnsfaid_line_stats* stats,
                                    size_t n_codewords, uint64_t errors[4], uint64_t fec[4], uint64_t vs_sent[4]);
 
+/* ---- line-format soft channel ----------------------------------------------------------------------------
+ * The soft-decision counterpart of the BSC above: a binary-input, 15-level, symmetric memoryless channel that reads LNSFAID_LINE_HARD
+ * (what lnsfaid_encode_line_device writes) and writes LNSFAID_LINE_LLR4 (what lnsfaid_decode_line_device reads), so that
+ * payload -> encode_line -> soft channel -> decode_line (LNSFAID_LINE_LLR4) -> counters runs on the device, and soft input can be
+ * compared with hard decisions on the same codewords.  Integer arithmetic only: every output nibble is a pure function of (key,
+ * codeword number, position, table), and the host form is the definition.
+ *
+ * Generator: the link's, with a third domain - cwkey(key, C, 3) and draw(key, C, 3, q) as written out above, C = first_codeword + i,
+ * wrapping.  Position 2 q of a codeword uses the low 32 bits u of draw q, position 2 q + 1 the high 32 bits, for q < L / 2.
+ * table: fourteen uint32_t thresholds, non-decreasing (a host pointer in both forms).  m = -7 + #{ i : u >= table[i] }, in -7 .. 7.
+ * The output level is m where the line bit is 1 and -m where it is 0 (positive means bit 1, as everywhere): the channel is symmetric by
+ * construction.  The level is stored as the two's-complement nibble of LNSFAID_LINE_LLR4: byte k / 2, the low nibble for even k; -8
+ * never occurs.  Hence P(m = l) = (table[l + 7] - table[l + 6]) / 2^32 exactly, with table[-1] = 0 and table[14] = 2^32.
+ *   flips        optional uint32_t [n_codewords] (the _device form: a device pointer): per codeword, the positions at which the
+ *                channel's own decision level > 0 differs from the line bit - the rule of lnsfaid_line_stats::corrected.  A sent 1 at
+ *                level 0 counts, a sent 0 at level 0 does not.
+ *   total_flips  optional host uint64_t, ADDED to: their sum over the call.  The pre-FEC BER of a run is total_flips / (n * L).
+ * lnsfaid_line_awgn_table (host only): the table of y = +-1 + N(0, sigma^2) behind the reference's 4-bit quantiser
+ * (float2LimitChar_4bit): level = clamp(trunc(y * scale), -7, 7), truncation toward zero.  The boundaries are b_i = j_i / scale for
+ * j = -7 .. -1, 1 .. 7 (level 0 is the double-width bin) and table[i] = min(floor(2^32 * Phi((b_i - 1) / sigma)), 2^32 - 1) with
+ * Phi(x) = erfc(-x / sqrt 2) / 2 in double.  LNSFAID_E_INVAL for a NULL table or a sigma or scale that is not finite and positive; the
+ * table is then not written.  Any other non-decreasing table is as valid an input - a receiver's measured level histogram, summed up.
+ * Rules: the link's.  n_codewords 0 is a no-op.  LNSFAID_E_INVAL: a NULL context or code; L or K not a multiple of 32; more than
+ * 32 * max_groups codewords (device form); a NULL line_in, llr4_out or table; a device pointer, optional ones included, that is not
+ * 4-byte aligned (an output on 16 bytes is written 16 bytes at a time); a table that decreases somewhere; and, because the output is
+ * four times the input and in-place use is impossible, any overlap of the byte ranges of line_in and llr4_out.  A refused call writes
+ * nothing and adds nothing.  The device form queues on the context's stream and returns when total_flips is complete; its accumulator
+ * is the link's.  It does not depend on the decoder configuration.  The host form needs no context and no GPU, takes pointers of any
+ * alignment and has no limit on n_codewords. */
+int lnsfaid_line_awgn_table(double sigma, double scale, uint32_t table[14]);
+int lnsfaid_line_soft_device(lnsfaid_ctx* ctx, const uint32_t* d_line_in, size_t n_codewords, uint64_t key, uint64_t first_codeword,
+                             const uint32_t table[14], uint8_t* d_llr4_out, uint32_t* d_flips, uint64_t* total_flips);
+int lnsfaid_line_soft_host(const lnsfaid_code* code, const uint32_t* line_in, size_t n_codewords, uint64_t key, uint64_t first_codeword,
+                           const uint32_t table[14], uint8_t* llr4_out, uint32_t* flips, uint64_t* total_flips);
+
 /* ---- front-end on the device (optional, the host generator stays the parity source) ---- */
 
 /*

@@ -82,6 +82,8 @@ extern "C" hipError_t lf_launch_line_bsc(const uint32_t* d_in, uint32_t* d_out, 
 extern "C" hipError_t lf_launch_line_payload(uint32_t* d_payload, size_t n_cw, uint32_t kw, uint64_t key, uint64_t first, hipStream_t stream);
 extern "C" hipError_t lf_launch_line_count(const uint32_t* d_payload, const uint32_t* d_sent, const lnsfaid_line_stats* d_stats, size_t n_cw,
                                            uint32_t kw, unsigned long long* d_acc, hipStream_t stream);
+extern "C" hipError_t lf_launch_line_soft(const uint32_t* d_in, uint8_t* d_out, size_t n_cw, uint32_t lw, uint64_t key, uint64_t first,
+                                          const uint32_t table[14], uint32_t* d_flips, unsigned long long* d_total, hipStream_t stream);
 
 #include <atomic>
 #include <chrono>
@@ -2481,6 +2483,33 @@ extern "C" int lnsfaid_line_count_errors_device(lnsfaid_ctx* ctx, const uint32_t
         if (fec) fec[i] += ctx->h_link_acc[4 + i];
         if (vs_sent) vs_sent[i] += ctx->h_link_acc[8 + i];
     }
+    return LNSFAID_OK;
+}
+
+/* ---- line-format soft channel (include/lnsfaid.h "line-format soft channel", DESIGN.md 3.17, lnsfaid_line_soft.hip) ---- */
+extern "C" int lnsfaid_line_soft_device(lnsfaid_ctx* ctx, const uint32_t* d_line_in, size_t n_codewords, uint64_t key, uint64_t first_codeword,
+                                        const uint32_t table[14], uint8_t* d_llr4_out, uint32_t* d_flips, uint64_t* total_flips)
+{
+    int rc = line_link_rules(ctx, n_codewords);
+    if (rc) return rc < 0 ? rc : LNSFAID_OK;
+    if (!d_line_in || !d_llr4_out || !table) return LNSFAID_E_INVAL;
+    if (!dword_aligned(d_line_in) || !dword_aligned(d_llr4_out) || !dword_aligned(d_flips)) return LNSFAID_E_INVAL;
+    for (int i = 1; i < 14; ++i)
+        if (table[i] < table[i - 1]) return LNSFAID_E_INVAL;
+    const size_t l_bits = (size_t)(ctx->n_var - ctx->hcode.puncture_tail);
+    const uintptr_t a = (uintptr_t)d_line_in, b = (uintptr_t)d_llr4_out; /* four times the input: no overlap can be right */
+    if (a < b + n_codewords * (l_bits / 2) && b < a + n_codewords * (l_bits / 8)) return LNSFAID_E_INVAL;
+    HIP_TRY(hipSetDevice(ctx->device));
+    rc = ensure_link_acc(ctx);
+    if (rc) return rc;
+    unsigned long long* d_total = ctx->d_link_acc + 12;
+    HIP_TRY(hipMemsetAsync(d_total, 0, sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(lf_launch_line_soft(d_line_in, d_llr4_out, n_codewords, (uint32_t)l_bits / 32u, key, first_codeword, table, d_flips, d_total,
+                                ctx->stream));
+    if (total_flips) HIP_TRY(hipMemcpyAsync(ctx->h_link_acc + 12, d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    rc = stream_wait(ctx);
+    if (rc) return rc;
+    if (total_flips) *total_flips += ctx->h_link_acc[12];
     return LNSFAID_OK;
 }
 

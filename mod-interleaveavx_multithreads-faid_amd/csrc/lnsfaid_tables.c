@@ -512,3 +512,68 @@ int lnsfaid_line_count_errors_host(const lnsfaid_code* code, const uint32_t* pay
     }
     return LNSFAID_OK;
 }
+
+/* ---- line-format soft channel, host form and table helper (include/lnsfaid.h "line-format soft channel") ----
+ * The definition of what lnsfaid_line_soft_device returns.  Bytes in, bytes out: host pointers of any alignment do. */
+#include <math.h>
+
+int lnsfaid_line_awgn_table(double sigma, double scale, uint32_t table[14])
+{
+    if (!table || !(sigma > 0.0 && sigma < INFINITY) || !(scale > 0.0 && scale < INFINITY)) return LNSFAID_E_INVAL; /* NaN fails the comparisons */
+    for (int i = 0; i < 14; ++i) {
+        const int j = i < 7 ? i - 7 : i - 6; /* -7 .. -1, 1 .. 7: level 0 is the double-width bin of a truncation toward zero */
+        const double b = (double)j / scale;
+        const double phi = 0.5 * erfc(-((b - 1.0) / sigma) / sqrt(2.0));
+        const double t = floor(4294967296.0 * phi);
+        table[i] = t >= 4294967295.0 ? 0xFFFFFFFFu : (uint32_t)t;
+    }
+    return LNSFAID_OK;
+}
+
+/* LNSFAID_OK for fourteen non-decreasing thresholds, which it copies to t */
+static int soft_table_rules(const uint32_t* table, uint32_t t[14])
+{
+    if (!table) return LNSFAID_E_INVAL;
+    memcpy(t, table, 14 * sizeof(uint32_t));
+    for (int i = 1; i < 14; ++i)
+        if (t[i] < t[i - 1]) return LNSFAID_E_INVAL;
+    return LNSFAID_OK;
+}
+
+int lnsfaid_line_soft_host(const lnsfaid_code* code, const uint32_t* line_in, size_t n_codewords, uint64_t key, uint64_t first_codeword,
+                           const uint32_t table[14], uint8_t* llr4_out, uint32_t* flips, uint64_t* total_flips)
+{
+    const int rc = line_code_rules(code, LNSFAID_LINE_HARD);
+    if (rc) return rc;
+    if (n_codewords == 0) return LNSFAID_OK;
+    uint32_t thr[14];
+    if (!line_in || !llr4_out || soft_table_rules(table, thr)) return LNSFAID_E_INVAL;
+    const size_t L = (size_t)(code->n_var - code->puncture_tail);
+    const uint8_t* in = (const uint8_t*)line_in;
+    const uintptr_t a = (uintptr_t)in, b = (uintptr_t)llr4_out; /* the output is four times the input: no overlap can be right */
+    if (a < b + n_codewords * (L / 2) && b < a + n_codewords * (L / 8)) return LNSFAID_E_INVAL;
+    uint64_t total = 0;
+    for (size_t i = 0; i < n_codewords; ++i) {
+        const uint64_t ck = link_cwkey(key, first_codeword + (uint64_t)i, 3u);
+        uint32_t n = 0;
+        for (size_t q = 0; q < L / 2; ++q) { /* position 2 q is the low half of draw q, 2 q + 1 the high half: one output byte */
+            const uint64_t h = link_draw(ck, (uint64_t)q);
+            const unsigned bits = (unsigned)(in[i * (L / 8) + q / 4] >> (2 * (q % 4))) & 3u;
+            unsigned byte = 0;
+            for (unsigned half = 0; half < 2u; ++half) {
+                const uint32_t u = half ? (uint32_t)(h >> 32) : (uint32_t)h;
+                int m = -7;
+                for (int t = 0; t < 14; ++t) m += u >= thr[t];
+                const int bit = (int)(bits >> half) & 1;
+                const int level = bit ? m : -m;
+                n += (uint32_t)((level > 0) != bit);
+                byte |= ((unsigned)level & 15u) << (4u * half);
+            }
+            llr4_out[i * (L / 2) + q] = (uint8_t)byte;
+        }
+        if (flips) link_st32((uint8_t*)flips + 4 * i, n);
+        total += n;
+    }
+    if (total_flips) *total_flips += total;
+    return LNSFAID_OK;
+}

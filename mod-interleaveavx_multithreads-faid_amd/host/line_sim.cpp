@@ -2,6 +2,9 @@
  * link"): per input bit error rate and call
  *   lnsfaid_line_payload_random_device -> lnsfaid_encode_line_device -> lnsfaid_line_bsc_device (in place) ->
  *   lnsfaid_decode_line_device (LNSFAID_LINE_HARD) -> lnsfaid_line_count_errors_device
+ * or, with --ebn0 in place of --ber, the soft-decision sweep (include/lnsfaid.h "line-format soft channel"): per Eb/N0
+ *   ... -> lnsfaid_encode_line_device -> lnsfaid_line_soft_device (table of lnsfaid_line_awgn_table) ->
+ *   lnsfaid_decode_line_device (LNSFAID_LINE_LLR4) -> lnsfaid_line_count_errors_device
  * on the device buffers of one context (lnsfaid_io_buffers, carved up below): no bit crosses to the host, only the counters do.
  * first_codeword continues across calls and points, so a run is one stream of codewords of the key.  A point stops at --min-errors
  * error frames or after --max-calls calls.  One row per point goes to LineResult.txt (in the working directory) and to the console. */
@@ -17,7 +20,7 @@
 #include "lnsfaid.h"
 
 static const char* kUsage =
-    "usage: %s --ber P[,P...] --codewords N --max-calls C --min-errors E [--method 2] [--iterations 10] [--magnitude 4] [--key K] [--device D]\n";
+    "usage: %s --ber P[,P...] [--magnitude 4] | --ebn0 D[,D...] [--scale 9.19238816] --codewords N --max-calls C --min-errors E [--method 2] [--iterations 10] [--key K] [--device D]\n";
 
 static bool parse_u64(const char* s, uint64_t* v)
 {
@@ -42,11 +45,34 @@ static bool parse_ber(const char* s, std::vector<double>* out)
     }
 }
 
+static bool parse_ebn0(const char* s, std::vector<double>* out)
+{
+    const char* p = s;
+    while (true) {
+        char* end = nullptr;
+        const double v = strtod(p, &end);
+        if (end == p || !std::isfinite(v)) return false;
+        out->push_back(v);
+        if (*end == '\0') return true;
+        if (*end != ',') return false;
+        p = end + 1;
+    }
+}
+
+static bool parse_scale(const char* s, double* v)
+{
+    char* end = nullptr;
+    *v = strtod(s, &end);
+    return end != s && *end == '\0' && std::isfinite(*v) && *v > 0.0;
+}
+
 static size_t align256(size_t x) { return (x + 255u) & ~(size_t)255u; }
 
 int main(int argc, char** argv)
 {
-    std::vector<double> ber;
+    std::vector<double> ber, ebn0;
+    double scale = 13.0 / std::sqrt(2.0); /* the QPSK operating scale 13 on a unit-amplitude axis */
+    bool have_magnitude = false, have_scale = false;
     uint64_t codewords = 0, max_calls = 0, min_errors = 0, method = 2, iterations = 10, magnitude = 4, key = 1, device = 0;
     bool have[4] = { false, false, false, false }, ok = true;
     for (int i = 1; i < argc && ok; ++i) {
@@ -54,17 +80,22 @@ int main(int argc, char** argv)
         const char* v = i + 1 < argc ? argv[i + 1] : nullptr;
         if (!v) ok = false;
         else if (!strcmp(a, "--ber")) have[0] = ok = parse_ber(v, &ber);
+        else if (!strcmp(a, "--ebn0")) ok = parse_ebn0(v, &ebn0);
+        else if (!strcmp(a, "--scale")) have_scale = ok = parse_scale(v, &scale);
         else if (!strcmp(a, "--codewords")) have[1] = ok = parse_u64(v, &codewords) && codewords > 0 && codewords <= 0x7fffffffull;
         else if (!strcmp(a, "--max-calls")) have[2] = ok = parse_u64(v, &max_calls) && max_calls > 0;
         else if (!strcmp(a, "--min-errors")) have[3] = ok = parse_u64(v, &min_errors);
         else if (!strcmp(a, "--method")) ok = parse_u64(v, &method) && method <= 5;
         else if (!strcmp(a, "--iterations")) ok = parse_u64(v, &iterations) && iterations > 0 && iterations <= 1000;
-        else if (!strcmp(a, "--magnitude")) ok = parse_u64(v, &magnitude) && magnitude >= 1 && magnitude <= 7;
+        else if (!strcmp(a, "--magnitude")) have_magnitude = ok = parse_u64(v, &magnitude) && magnitude >= 1 && magnitude <= 7;
         else if (!strcmp(a, "--key")) ok = parse_u64(v, &key);
         else if (!strcmp(a, "--device")) ok = parse_u64(v, &device) && device < 1024;
         else ok = false;
         ++i;
     }
+    const bool soft = !ebn0.empty();
+    if (soft) have[0] = ber.empty() && !have_magnitude; /* exactly one of --ber and --ebn0; --magnitude belongs to --ber */
+    else if (have_scale) ok = false;                    /* and --scale to --ebn0 */
     if (!ok || !have[0] || !have[1] || !have[2] || !have[3]) {
         fprintf(stderr, kUsage, argv[0]);
         return 2;
@@ -86,10 +117,12 @@ int main(int argc, char** argv)
         lnsfaid_destroy(ctx);
         return 1;
     }
-    /* each of the two buffers holds 32 * n_var bytes per group; the five streams need (2 K + L) / 8 + 20 bytes per codeword */
+    /* each of the two buffers holds 32 * n_var bytes per group; the five streams need (2 K + L) / 8 + 20 bytes per codeword, the
+     * LLR4 line of the soft sweep L / 2 more, behind the hard line */
     const size_t K = (size_t)(code.n_var - code.n_check), L = (size_t)(code.n_var - code.puncture_tail);
     const size_t room = groups * LNSFAID_GROUP * (size_t)code.n_var;
-    const size_t o_line = align256(n * K / 8), o_flips = o_line + align256(n * L / 8), o_stats = align256(n * K / 8);
+    const size_t o_line = align256(n * K / 8), o_llr4 = o_line + align256(n * L / 8), o_flips = o_llr4 + (soft ? align256(n * L / 2) : 0),
+                 o_stats = align256(n * K / 8);
     if (o_flips + 4 * n > room || o_stats + sizeof(lnsfaid_line_stats) * n > room) {
         fprintf(stderr, "lnsfaid_line_sim: the context's buffers are too small for this code\n");
         lnsfaid_destroy(ctx);
@@ -97,6 +130,7 @@ int main(int argc, char** argv)
     }
     uint32_t* d_payload = (uint32_t*)d_a;
     uint32_t* d_line = (uint32_t*)(d_a + o_line);
+    uint8_t* d_llr4 = (uint8_t*)(d_a + o_llr4);
     uint32_t* d_flips = (uint32_t*)(d_a + o_flips);
     uint32_t* d_decoded = (uint32_t*)d_b;
     lnsfaid_line_stats* d_stats = (lnsfaid_line_stats*)(d_b + o_stats);
@@ -110,32 +144,52 @@ int main(int argc, char** argv)
     const char* head = "# p threshold codewords flipped_bits ber_in TestFrame ErrorFrame ErrorBits LT3ErrBitFrame FER ber_out "
                        "TotalCodewords UncorrectableCodewords CorrectedCodewords CorrectedBits "
                        "vsTestFrame vsErrorFrame UndetectedErrorFrame FalseAlarmFrame seconds\n";
-    fprintf(f, "# lnsfaid_line_sim: DecodeMethod %llu, %llu iterations, magnitude %llu, key %llu, %zu codewords per call\n%s",
-            (unsigned long long)method, (unsigned long long)iterations, (unsigned long long)magnitude, (unsigned long long)key, n, head);
+    const char* soft_head = "# ebn0_db table7 codewords flipped_bits ber_in TestFrame ErrorFrame ErrorBits LT3ErrBitFrame FER ber_out "
+                            "TotalCodewords UncorrectableCodewords CorrectedCodewords CorrectedBits "
+                            "vsTestFrame vsErrorFrame UndetectedErrorFrame FalseAlarmFrame seconds sigma scale\n";
+    if (soft) {
+        head = soft_head;
+        fprintf(f, "# lnsfaid_line_sim: soft, DecodeMethod %llu, %llu iterations, scale %.9g, key %llu, %zu codewords per call\n%s",
+                (unsigned long long)method, (unsigned long long)iterations, scale, (unsigned long long)key, n, head);
+    } else {
+        fprintf(f, "# lnsfaid_line_sim: DecodeMethod %llu, %llu iterations, magnitude %llu, key %llu, %zu codewords per call\n%s",
+                (unsigned long long)method, (unsigned long long)iterations, (unsigned long long)magnitude, (unsigned long long)key, n, head);
+    }
     printf("%s", head);
     uint64_t first = 0;
-    for (const double p : ber) {
-        uint32_t threshold = 0;
-        lnsfaid_line_bsc_threshold(p, &threshold); /* checked with the arguments */
+    for (const double x : soft ? ebn0 : ber) { /* x: Eb/N0 in dB, or the BSC's p */
+        uint32_t threshold = 0, table[14];
+        /* Eb/N0 of the information bit on a unit-amplitude axis: sigma^2 = 1 / (2 R Eb/N0), R = K / L the rate on the line */
+        const double sigma = soft ? 1.0 / std::sqrt(2.0 * ((double)K / (double)L) * std::pow(10.0, x / 10.0)) : 0.0;
+        if (soft) rc = lnsfaid_line_awgn_table(sigma, scale, table);
+        else lnsfaid_line_bsc_threshold(x, &threshold); /* checked with the arguments */
         uint64_t errors[4] = { 0, 0, 0, 0 }, fec[4] = { 0, 0, 0, 0 }, vs[4] = { 0, 0, 0, 0 }, flips = 0;
         const auto t0 = std::chrono::steady_clock::now();
         for (uint64_t call = 0; call < max_calls && !rc && errors[1] < min_errors; ++call, first += n) {
             rc = lnsfaid_line_payload_random_device(ctx, key, first, n, d_payload);
             if (!rc) rc = lnsfaid_encode_line_device(ctx, d_payload, n, d_line, nullptr);
-            if (!rc) rc = lnsfaid_line_bsc_device(ctx, d_line, n, key, first, threshold, d_line, d_flips, &flips);
-            if (!rc) rc = lnsfaid_decode_line_device(ctx, d_line, LNSFAID_LINE_HARD, (int32_t)magnitude, n, d_decoded, nullptr, d_stats);
+            if (soft) {
+                if (!rc) rc = lnsfaid_line_soft_device(ctx, d_line, n, key, first, table, d_llr4, d_flips, &flips);
+                if (!rc) rc = lnsfaid_decode_line_device(ctx, d_llr4, LNSFAID_LINE_LLR4, 0, n, d_decoded, nullptr, d_stats);
+            } else {
+                if (!rc) rc = lnsfaid_line_bsc_device(ctx, d_line, n, key, first, threshold, d_line, d_flips, &flips);
+                if (!rc) rc = lnsfaid_decode_line_device(ctx, d_line, LNSFAID_LINE_HARD, (int32_t)magnitude, n, d_decoded, nullptr, d_stats);
+            }
             if (!rc) rc = lnsfaid_line_count_errors_device(ctx, d_decoded, d_payload, d_stats, n, errors, fec, vs);
         }
         if (rc) break;
         const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
         const double cw = (double)errors[0];
-        char row[640];
-        snprintf(row, sizeof(row), "%.9g %u %llu %llu %.6e %llu %llu %llu %llu %.6e %.6e %llu %llu %llu %llu %llu %llu %llu %llu %.3f\n", p, threshold,
-                 (unsigned long long)errors[0], (unsigned long long)flips, cw > 0 ? (double)flips / (cw * (double)L) : 0.0,
-                 (unsigned long long)errors[0], (unsigned long long)errors[1], (unsigned long long)errors[2], (unsigned long long)errors[3],
-                 cw > 0 ? (double)errors[1] / cw : 0.0, cw > 0 ? (double)errors[2] / (cw * (double)K) : 0.0,
-                 (unsigned long long)fec[0], (unsigned long long)fec[1], (unsigned long long)fec[2], (unsigned long long)fec[3],
-                 (unsigned long long)vs[0], (unsigned long long)vs[1], (unsigned long long)vs[2], (unsigned long long)vs[3], seconds);
+        char row[704];
+        int len = snprintf(row, sizeof(row), "%.9g %u %llu %llu %.6e %llu %llu %llu %llu %.6e %.6e %llu %llu %llu %llu %llu %llu %llu %llu %.3f", x,
+                           soft ? table[7] : threshold, (unsigned long long)errors[0], (unsigned long long)flips,
+                           cw > 0 ? (double)flips / (cw * (double)L) : 0.0,
+                           (unsigned long long)errors[0], (unsigned long long)errors[1], (unsigned long long)errors[2], (unsigned long long)errors[3],
+                           cw > 0 ? (double)errors[1] / cw : 0.0, cw > 0 ? (double)errors[2] / (cw * (double)K) : 0.0,
+                           (unsigned long long)fec[0], (unsigned long long)fec[1], (unsigned long long)fec[2], (unsigned long long)fec[3],
+                           (unsigned long long)vs[0], (unsigned long long)vs[1], (unsigned long long)vs[2], (unsigned long long)vs[3], seconds);
+        if (soft) len += snprintf(row + len, sizeof(row) - (size_t)len, " %.9g %.9g", sigma, scale);
+        snprintf(row + len, sizeof(row) - (size_t)len, "\n");
         fputs(row, f);
         fflush(f);
         fputs(row, stdout);

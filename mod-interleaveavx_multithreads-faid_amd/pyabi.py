@@ -110,6 +110,11 @@ SYMBOLS = {
                                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "lnsfaid_line_count_errors_host": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64),
                                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "lnsfaid_line_awgn_table": (C.c_int, [C.c_double, C.c_double, C.c_void_p]),
+    "lnsfaid_line_soft_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.POINTER(C.c_uint64)]),
+    "lnsfaid_line_soft_host": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                         C.POINTER(C.c_uint64)]),
     "lnsfaid_frontend_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_size_t, C.c_int32,
                                           C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "lnsfaid_frontend_device_states": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_size_t, C.c_int32,
@@ -415,6 +420,47 @@ def line_bsc_host(code, line, n_codewords, key, first_codeword, threshold, in_pl
                                    flips.ctypes.data, C.byref(t))
     if rc != 0:
         raise ValueError("lnsfaid_line_bsc_host failed: %d" % rc)
+    return out, flips, t.value
+
+
+def _soft_table(table):
+    """fourteen thresholds as a contiguous uint32 array (the library checks their order)"""
+    import numpy as np
+    table = np.ascontiguousarray(table, dtype=np.uint32)
+    if table.size != 14:
+        raise ValueError("a soft-channel table has 14 thresholds, not %d" % table.size)
+    return table
+
+
+def line_awgn_table(sigma, scale, lib=None):
+    """lnsfaid_line_awgn_table: the uint32 [14] thresholds of +-1 + N(0, sigma^2) behind the 4-bit quantiser at `scale`; ValueError
+    for a sigma or scale that is not finite and positive"""
+    import numpy as np
+    lib = lib or load()
+    table = np.zeros(14, dtype=np.uint32)
+    rc = lib.lnsfaid_line_awgn_table(float(sigma), float(scale), table.ctypes.data)
+    if rc != 0:
+        raise ValueError("lnsfaid_line_awgn_table(%r, %r) failed: %d" % (sigma, scale, rc))
+    return table
+
+
+def line_soft_host(code, line, n_codewords, key, first_codeword, table, total=0, lib=None):
+    """lnsfaid_line_soft_host: line uint32 [n_codewords, L / 32] (LINE_HARD) through the soft channel of stream `key` and `table`.
+    Returns (llr4 uint8 [n_codewords, L / 2] (LINE_LLR4), flips uint32 [n_codewords], total + the flips of the call)"""
+    import numpy as np
+    lib = lib or load()
+    L = code.n_var - code.puncture_tail
+    line = np.ascontiguousarray(line, dtype=np.uint32)
+    if line.size != n_codewords * (L // 32):
+        raise ValueError("lnsfaid_line_soft_host: line has %d words, not %d" % (line.size, n_codewords * (L // 32)))
+    table = _soft_table(table)
+    out = np.empty((n_codewords, L // 2), dtype=np.uint8)
+    flips = np.zeros(n_codewords, dtype=np.uint32)
+    t = C.c_uint64(total)
+    rc = lib.lnsfaid_line_soft_host(C.byref(code), line.ctypes.data, n_codewords, key, first_codeword, table.ctypes.data, out.ctypes.data,
+                                    flips.ctypes.data, C.byref(t))
+    if rc != 0:
+        raise ValueError("lnsfaid_line_soft_host failed: %d" % rc)
     return out, flips, t.value
 
 
@@ -725,6 +771,15 @@ class Decoder:
         t = C.c_uint64(total)
         self._check(self.lib.lnsfaid_line_bsc_device(self.ctx, d_line_in_ptr, n_codewords, key, first_codeword, threshold, d_line_out_ptr,
                                                      d_flips_ptr, C.byref(t)), "lnsfaid_line_bsc_device")
+        return t.value
+
+    def line_soft_device(self, d_line_in_ptr, n_codewords, key, first_codeword, table, d_llr4_out_ptr, d_flips_ptr=None, total=0):
+        """lnsfaid_line_soft_device: LINE_HARD words through the soft channel of stream `key` and `table` (14 thresholds, host side)
+        into LINE_LLR4 bytes.  Returns total + the flips of the call"""
+        table = _soft_table(table)
+        t = C.c_uint64(total)
+        self._check(self.lib.lnsfaid_line_soft_device(self.ctx, d_line_in_ptr, n_codewords, key, first_codeword, table.ctypes.data,
+                                                      d_llr4_out_ptr, d_flips_ptr, C.byref(t)), "lnsfaid_line_soft_device")
         return t.value
 
     def line_count_errors_device(self, d_payload_ptr, d_sent_ptr, d_stats_ptr, n_codewords, errors=True, fec=None, vs_sent=None):
