@@ -75,7 +75,7 @@ __device__ __forceinline__ void layer4s(const uint32_t (*zsb)[32], SwRegs& R, co
     Tab tab;
     tab.sbv = tabv;
     const SwRow cur = regs_get(R, BR);
-    SwRow st = sw_layer_step<METHOD, Tab::DEG>(lds, tab, p, K, (uint32_t)lane, Tab::DEG, cur, fresh, rowpar, lme);
+    SwRow st = sw_layer_step<METHOD, Tab::DEG, false, 1, 0, 0, SW_PAIRS_ALL>(lds, tab, p, K, (uint32_t)lane, Tab::DEG, cur, fresh, rowpar, lme);
     /* The record is complete HERE.  With a constant layer number regs_put is a renaming, not six moves: nothing else holds the
      * compiler from sinking the packing of the sign words to the record's next use, an iteration later, with the layer's 23 sign
      * masks alive (spilled) until then. */

@@ -169,6 +169,35 @@ SW_FN SwK sw_consts(uint32_t dep = 0u)
 /* 0xff in every byte whose bit 7 is set, else 0x00 (two instructions: shift + v_perm with selectors 8..11) */
 SW_FN uint32_t sw_mask7(uint32_t x, uint32_t sel_sign) { return sw_perm(x, x << 8, sel_sign); }
 #define SW_SEL_SIGN 0x0b090a08u
+/* v_lshlrev_b64 by 8 on the register pair {a (low), b (high)}: the low word is a << 8, the high word (b << 8) | (a >> 24).  Bytes 1 and
+ * 3 of the high word are bytes 0 and 2 of b and only its byte 0 is foreign (a's top byte) - the byte the sign selectors 8 and 9 of
+ * v_perm_b32 never read.  One shift therefore feeds the mask expansion of TWO words.
+ * Device: left to itself the compiler takes a 64-bit shift of two 32-bit halves apart again (v_lshlrev_b64 of {a, 0}, v_lshlrev_b32 of b
+ * and an OR; or, where only the halves of the result are read, v_lshlrev_b32 and v_alignbit_b32), so the pair and the result each pass
+ * through an empty asm statement it cannot look through.  a and b come back as the halves of the pair: a caller that reads them
+ * afterwards must read THESE, or the allocator keeps the old registers alive and copies them into the pair. */
+SW_FN uint64_t sw_shl8x2(uint32_t& a, uint32_t& b)
+{
+    uint64_t p = ((uint64_t)b << 32) | a;
+#if SW_DEV
+    asm("" : "+v"(p));
+    a = (uint32_t)p; b = (uint32_t)(p >> 32);
+    uint64_t r = p << 8;
+    asm("" : "+v"(r));
+    return r;
+#else
+    return p << 8;
+#endif
+}
+/* sw_mask7 of a and of b in three instructions instead of four: the two halves of one sw_shl8x2 under the same selector */
+SW_FN uint32_t sw_mask7_lo(uint32_t a, uint64_t sh, uint32_t sel_sign) { return sw_perm(a, (uint32_t)sh, sel_sign); }
+SW_FN uint32_t sw_mask7_hi(uint32_t b, uint64_t sh, uint32_t sel_sign) { return sw_perm(b, (uint32_t)(sh >> 32), sel_sign); }
+SW_FN void sw_mask7x2(uint32_t a, uint32_t b, uint32_t sel_sign, uint32_t* ma, uint32_t* mb)
+{
+    const uint64_t sh = sw_shl8x2(a, b);
+    *ma = sw_mask7_lo(a, sh, sel_sign);
+    *mb = sw_mask7_hi(b, sh, sel_sign);
+}
 
 /* per-byte population count of the low seven bits (thermometer code -> number) */
 SW_FN uint32_t sw_popcount7(uint32_t x)
@@ -192,6 +221,14 @@ SW_FN uint32_t sw_therm2num(uint32_t x, uint32_t n_lo, uint32_t n_hi)
 }
 /* 0xff in every byte that is zero; bytes must be <= 0x7f */
 SW_FN uint32_t sw_zero_mask(uint32_t x, uint32_t sel_sign) { return ~sw_mask7(x + 0x7f7f7f7fu, sel_sign); }
+/* sw_zero_mask of x and of y on one shift (sw_mask7x2) */
+SW_FN void sw_zero_mask2(uint32_t x, uint32_t y, uint32_t sel_sign, uint32_t* zx, uint32_t* zy)
+{
+    uint32_t mx, my;
+    sw_mask7x2(x + 0x7f7f7f7fu, y + 0x7f7f7f7fu, sel_sign, &mx, &my);
+    *zx = ~mx;
+    *zy = ~my;
+}
 
 /* four bytes read one by one (each value < 256) into one word, byte k = g_k, as two pairs and their merge: three v_lshl_or_b32 where
  * the compiler finds them (written through an asm statement they were forced - and one of the packed kernels then reserved a stack
@@ -579,7 +616,18 @@ struct SwTabStatic {
  * rotating code is correct for shift 0, so a smaller ZG than the layer has is always exact.  Per-degree instances of one wave per
  * codeword only.
  * A static table view (SwTabStatic) names the exact count instead: NZ need not be a multiple of SW_ILP then. */
-template <int METHOD, int DEG, bool ERA = false, int WAVES = 1, int WAVE = 0, int ZG = 0, class Tab, class Xch = SwNoXch>
+/* PAIRS: byte masks that are expanded side by side share one 64-bit shift (sw_mask7x2), a bit per place: SW_PAIRS_PASS1 / _PASS2 the
+ * edges' masks of a pass two by two inside a group of SW_ILP (per-degree instances of one wave per codeword: there both edges of a
+ * pair exist and belong to the wave), SW_PAIRS_ROW the per-row ones, (nm3, nm4) and the two zero masks of the new magnitudes.  A
+ * clear bit: every mask of that place on a shift of its own (sw_mask7).  The layer-static kernel (lnsfaid_kernel4s.hip) sets them all;
+ * the other instances stay on the single form, 0: with the pairs each of them went over one of its own ceilings in tests/ (a 17th
+ * s_waitcnt in the layer loop's degree-23 block, one more instruction around the rotation-free loop's blocks, 36 bytes of scratch in
+ * the packed per-codeword NMS kernel - DESIGN.md 3.1h). */
+#define SW_PAIRS_PASS1 1
+#define SW_PAIRS_PASS2 2
+#define SW_PAIRS_ROW 4
+#define SW_PAIRS_ALL (SW_PAIRS_PASS1 | SW_PAIRS_PASS2 | SW_PAIRS_ROW)
+template <int METHOD, int DEG, bool ERA = false, int WAVES = 1, int WAVE = 0, int ZG = 0, int PAIRS = 0, class Tab, class Xch = SwNoXch>
 SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, const SwK& K, uint32_t lane, int deg, SwRow cur, bool fresh,
                           uint32_t rowpar, bool lme, uint32_t era_edges = 0u, uint32_t era_plane = 0u, const Xch& xch = Xch())
 {
@@ -600,6 +648,8 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
      * edge is conditional and the group's values would have to be kept under a select each */
     constexpr bool QUADS = WAVES == 1 && SW_ILP == 4 && DEG > 0;
     constexpr bool NSTREE = WAVES == 1 && SW_ILP == 4; /* pass 2 packs its sign words four edges at a time (sw_sign_quad) */
+    constexpr bool EPAIRS = WAVES == 1 && DEG > 0 && SW_ILP % 2 == 0; /* edges j0 + 2 i, j0 + 2 i + 1 of a group may share a shift */
+    constexpr bool EPAIRS1 = EPAIRS && (PAIRS & SW_PAIRS_PASS1), EPAIRS2 = EPAIRS && (PAIRS & SW_PAIRS_PASS2), RPAIRS = (PAIRS & SW_PAIRS_ROW) != 0;
     const uint32_t c01 = K.cbit[0], c80 = K.cbit[7], c7f = K.c7f, c78 = K.c78, c0642 = K.c0642, cfc = K.cfc, sel_sign = K.sel_sign;
     const uint32_t tid4 = lane << 2;
     /* the layer's circulants first (scalar loads share the LDS counter: in flight together with LDS reads they force full drains) */
@@ -669,6 +719,35 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
     for (int j0 = 0; j0 < NJ; j0 += SW_ILP) {
         uint32_t r_[SW_ILP], x_[SW_ILP], s_[SW_ILP], k_[SW_ILP], a_[SW_ILP], i_[SW_ILP], u_[SW_ILP];
 #define SW_EDGES(...) _Pragma("unroll") for (int g = 0; g < SW_ILP; ++g) { const int j = j0 + g; if (j < NJ && (DEG > 0 || j < deg) && SW_OWN(j)) { __VA_ARGS__ } }
+        /* A mask stage of a group, DST(g, j) = sw_mask7(SRC(g, j)) on every edge of the group, in two halves: the shifts - with EPAIRS
+         * one per pair of edges, the group's odd last edge keeps a 32-bit one - and the expansions.  A reader of a 64-bit shift's
+         * result within the next two instructions costs a wait state (the compiler fills it with s_nop).  So the shifts take the
+         * stage in front of them along, as PRE: the statement that makes SRC(g, j), run on the two edges of a pair right in front
+         * of the pair's shift.  The first pair's expansions then follow the second pair's statements, and the second pair's the
+         * first pair's expansions; nothing lives longer than on the single form. */
+#define SW_MASK_SHIFTS(EPAIRS, SRC, PRE)                                                                                                 \
+        uint64_t sh_[SW_ILP / 2 + 1];                                                                                                    \
+        if (EPAIRS) {                                                                                                                    \
+            _Pragma("unroll") for (int g0 = 0; g0 < SW_ILP; g0 += 2) {                                                                   \
+                _Pragma("unroll") for (int g = g0; g < g0 + 2; ++g) { const int j = j0 + g; if (j < NJ) { PRE } }                       \
+                if (j0 + g0 + 1 < NJ) sh_[g0 >> 1] = sw_shl8x2(SRC(g0, j0 + g0), SRC(g0 + 1, j0 + g0 + 1));                              \
+                else if (j0 + g0 < NJ) sh_[g0 >> 1] = SRC(g0, j0 + g0) << 8;                                                             \
+            }                                                                                                                            \
+        } else {                                                                                                                         \
+            SW_EDGES(PRE)                                                                                                                \
+        }
+#define SW_MASK_EXPAND(EPAIRS, DST, SRC)                                                                                                 \
+        if (EPAIRS) {                                                                                                                    \
+            _Pragma("unroll") for (int g = 0; g < SW_ILP; ++g) {                                                                         \
+                const int j = j0 + g;                                                                                                    \
+                if (j < NJ) DST(g, j) = (g & 1) ? sw_mask7_hi(SRC(g, j), sh_[g >> 1], sel_sign) : sw_mask7_lo(SRC(g, j), sh_[g >> 1], sel_sign); \
+            }                                                                                                                            \
+        } else {                                                                                                                         \
+            SW_EDGES(DST(g, j) = sw_mask7(SRC(g, j), sel_sign);)                                                                         \
+        }
+#define SW_P1_TS(g, j) ts[j]
+#define SW_P1_MS(g, j) ms[j]
+#define SW_P2_MO(g, j) mo[g]
         /* byte k = En + 120 of row k.  The group's LAST read is consumed first: LDS reads return in order, so the one s_waitcnt in
          * front of it covers the group (in ascending order every edge gets a wait of its own) */
         _Pragma("unroll") for (int g = SW_ILP - 1; g >= 0; --g) { const int j = j0 + g; if (j < NJ && (DEG > 0 || j < deg) && SW_OWN(j)) r_[g] = j < NZ ? ld[j] : sw_alignbyte(ld[j], ld[j], rq[j]); }
@@ -698,8 +777,13 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
         }
         /* FAID: a zero V2C takes the sign of En (CDecoder_FAID.cpp:682); En == Lold there, so it is the stored sign b: bit 7 of
          * t + 128 - b.  k_ still holds the selector 2 k + b of the edge (the erasing variant rebuilds it from its own b) */
-        SW_EDGES(ts[j] = MINSUM ? tb[j] : tb[j] - (ERA ? (x_[g] | c0642) : s_[g]);)
-        SW_EDGES(ms[j] = sw_mask7(ts[j], sel_sign);)
+        { SW_MASK_SHIFTS(EPAIRS1, SW_P1_TS, ts[j] = MINSUM ? tb[j] : tb[j] - (ERA ? (x_[g] | c0642) : s_[g]);)
+        /* (with pairs the XOR of the sign words comes here for the same reason: between the second pair's shift and the expansions) */
+#define SW_SX_STAGE SW_EDGES(                                                                                                            \
+            if (WAVES == 2) sx ^= ts[j]; /* (the neighbour edge belongs to the other wave) */                                            \
+            else if (j & 1) sx = sw_bitop3<SW_TT_XOR3>(sx, ts[j - 1], ts[j]); else if (j == (DEG > 0 ? DEG : deg) - 1) sx ^= ts[j];)
+        if (EPAIRS1) { SW_SX_STAGE }
+        SW_MASK_EXPAND(EPAIRS1, SW_P1_MS, SW_P1_TS) }
         /* |t| -> min(|t|, 7) -> thermometer.  With m = 0xff where the (back-tracked) sign is "not negative":
          *   not negative: ts ^ 0x80 = t - b,  |t| = that + b          negative: ts ^ 0x7f = -t - 1 + b,  |t| = that + 1 - b
          * (b = 0 for the min-sum decoders); 0x78 is added on top so that |t| >= 8 reaches bit 7, which the table look-up
@@ -721,9 +805,7 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
             SW_EDGES(a_[g] = (MINSUM ? a_[g] + i_[g] : a_[g] + i_[g] + c78) & 0x87878787u;)     /* v_add3_u32 */
             SW_EDGES(u_[g] = sw_perm(tt_hi, tt_lo, a_[g]);)
         }
-        SW_EDGES(
-            if (WAVES == 2) sx ^= ts[j]; /* (the neighbour edge belongs to the other wave) */
-            else if (j & 1) sx = sw_bitop3<SW_TT_XOR3>(sx, ts[j - 1], ts[j]); else if (j == (DEG > 0 ? DEG : deg) - 1) sx ^= ts[j];)
+        if (!EPAIRS1) { SW_SX_STAGE }
         if (QUADS) {
             uint32_t v_[4];
             _Pragma("unroll") for (int g = 0; g < 4; ++g) v_[g] = j0 + g < NJ ? u_[g] : 0xffffffffu; /* no such edge: "no minimum" */
@@ -843,8 +925,10 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
         uint32_t d_[SW_ILP], zb[SW_ILP], mo[SW_ILP], lm[SW_ILP];                                                     \
         SW_EDGES(d_[g] = sw_upd2_d(ms[j], u2);)                                                                      \
         SW_EDGES(zb[g] = sw_upd2_zb(tb[j], d_[g], u2);)                                                              \
-        SW_EDGES(mo[g] = sw_upd2_out<MINSUM>(zb[g], d_[g], u2);)                                                     \
-        SW_EDGES(mo[g] = sw_mask7(mo[g], sel_sign);)     /* under or over */                                         \
+        {                                                                                                            \
+            SW_MASK_SHIFTS(EPAIRS2, SW_P2_MO, mo[g] = sw_upd2_out<MINSUM>(zb[g], d_[g], u2);)                        \
+            SW_MASK_EXPAND(EPAIRS2, SW_P2_MO, SW_P2_MO)  /* under or over */                                         \
+        }                                                                                                            \
         SW_EDGES(lm[g] = sw_upd2_limit<MINSUM>(ms[j], d_[g], u2, c80);)                                              \
         SW_EDGES(EN[g] = sw_upd2_en(mo[g], lm[g], zb[g], d_[g], cm27);)                                              \
         SW_EDGES(if (j >= NZ) EN[g] = sw_alignbyte(EN[g], EN[g], 4u - rq[j]);)                                       \
@@ -880,8 +964,15 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
     const uint32_t oh8 = sw_perm(K.oh_hi, K.oh_lo, idx & 0x07070707u);
     /* index bit 4 / bit 3 as byte masks, from the words the index was decoded from (their bit 7: the accumulator differs from the
      * minimum, i.e. the bit is CLEAR): no shifts.  nm3 ignores that bit 3 gives way to bit 4: every use below looks at nm4 first */
-    const uint32_t nm4 = (DEG == 0 && deg <= 16) ? 0xffffffffu : sw_mask7(ne7_4, sel_sign);
-    const uint32_t nm3 = (DEG == 0 && deg <= 8) ? 0xffffffffu : sw_mask7(ne7_3, sel_sign);
+    uint32_t nm3, nm4;
+    if (RPAIRS && (DEG == 0 || DEG > 16)) { /* (a per-degree instance up to degree 16 has one of them at the most) */
+        sw_mask7x2(ne7_3, ne7_4, sel_sign, &nm3, &nm4);
+        if (DEG == 0 && deg <= 16) nm4 = 0xffffffffu;
+        if (DEG == 0 && deg <= 8) nm3 = 0xffffffffu;
+    } else {
+        nm4 = (DEG == 0 && deg <= 16) ? 0xffffffffu : sw_mask7(ne7_4, sel_sign);
+        nm3 = (DEG == 0 && deg <= 8) ? 0xffffffffu : sw_mask7(ne7_3, sel_sign);
+    }
     /* old message on that edge negative: bit (index mod 8) of byte k of sign word (index div 8), as 2 k + b: the v_perm selector */
     const uint32_t selA = sw_argmin_selector(sw_word_pick(nm3, nm4, cur.x[0], cur.x[1], cur.x[2]), oh8, c7f, c01, c0642);
     if (ERA) xb = selA & c01;
@@ -913,6 +1004,12 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
         SW_PASS2_STORE(jg, en)
     }
 #undef SW_EDGES
+#undef SW_MASK_SHIFTS
+#undef SW_SX_STAGE
+#undef SW_MASK_EXPAND
+#undef SW_P1_TS
+#undef SW_P1_MS
+#undef SW_P2_MO
 #undef SW_PASS2_ARITH
 #undef SW_PASS2_STORE
 #undef SW_COL
@@ -943,7 +1040,10 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
     if (!MINSUM) {
         /* A zero message has no sign: stored as "not negative" so that the next iteration's back-track reads
          * "Lmn < 0" straight from the bit.  c2 == 0 zeroes every message of the row but the arg-min's. */
-        const uint32_t z2 = sw_zero_mask(c2n, sel_sign), nz1 = ~sw_zero_mask(c1n, sel_sign);
+        uint32_t z2, z1;
+        if (RPAIRS) sw_zero_mask2(c2n, c1n, sel_sign, &z2, &z1);
+        else { z2 = sw_zero_mask(c2n, sel_sign); z1 = sw_zero_mask(c1n, sel_sign); }
+        const uint32_t nz1 = ~z1;
         const uint32_t keep = oh8 & nz1; /* the arg-min edge's bit survives where its message c1 is not zero */
         uint32_t oh[3];
         sw_word_deal(keep, nm3, nm4, oh);

@@ -25,6 +25,82 @@ __device__ __forceinline__ void body(uint32_t (&a)[8], uint32_t b, uint32_t c)
     }
 }
 
+// The mask expander's shift forms, on four chains (words m[2 i], m[2 i + 1]).  A unit is
+//   1 "paired":      v_lshlrev_b64, 2 v_add_u32, 2 v_perm_b32 reading the shift's halves          (two masks, 5 instructions, 3 half-rate)
+//   2 "two single":  2 v_lshlrev_b32, 2 v_add_u32, 2 v_perm_b32 reading them                       (two masks, 6 instructions, 4 half-rate)
+//   0 / 5 / 3 / 4:   one v_lshlrev_b64 by 8 / v_lshlrev_b32 by 8 / v_pk_lshlrev_b16 by 8 / v_mul_u32_u24 by 256 held in a VGPR
+//                    (the last two: one-for-one stand-ins for v_lshlrev_b32 by 8 in front of the expander's v_perm_b32)
+// (the two adds stand between a shift and its readers, as other edges' instructions do in the layer step.)  MIX: the unit inside the
+// layer step's 7 : 3 mix - full-rate instructions (v_bitop3_b32 / v_add_u32 alternating) behind it.  "paired" and "two single"
+// get the SAME seven (4 half-rate of 13 for the form the kernel had: 31 %), so their difference per unit is what a pair saves
+// in place; a lone shift gets a v_perm_b32 and four fillers (2 half-rate of 6).  Times are reported per UNIT.
+#define UNITS 60
+// A unit is ONE asm statement (between two statements of which the second reads what the first wrote the compiler puts a wait state
+// of its own), and consecutive units work on different chains.  Inline asm cannot name the halves of a 64-bit operand, so the
+// pairs of "paired" are fixed registers, v[100:101] .. v[106:107], named in the clobber list; their values mean nothing.
+#define FILL_X "v_bitop3_b32 %[m0], %[m0], %[b], %[c] bitop3:0x96\n\t"
+#define FILL_A "v_add_u32 %[m1], %[m1], %[b]\n\t"
+#define FILL_0 ""
+#define FILL_4 FILL_X FILL_A FILL_X FILL_A
+#define FILL_7 FILL_X FILL_A FILL_X FILL_A FILL_X FILL_A FILL_X
+#define ADDS "v_add_u32 %[m0], %[m0], %[b]\n\tv_add_u32 %[m1], %[m1], %[b]\n\t"
+#define PAIRED(LO, HI, FILL) asm volatile("v_lshlrev_b64 v[" #LO ":" #HI "], 8, v[" #LO ":" #HI "]\n\t" ADDS "v_perm_b32 %[m0], %[m0], v" #LO ", %[c]\n\tv_perm_b32 %[m1], %[m1], v" #HI ", %[c]\n\t" FILL \
+                                          : [m0] "+v"(m0), [m1] "+v"(m1) : [b] "v"(b), [c] "v"(c) : "v" #LO, "v" #HI)
+#define SINGLES(FILL) asm volatile("v_lshlrev_b32 %[t0], 8, %[m0]\n\tv_lshlrev_b32 %[t1], 8, %[m1]\n\t" ADDS "v_perm_b32 %[m0], %[m0], %[t0], %[c]\n\tv_perm_b32 %[m1], %[m1], %[t1], %[c]\n\t" FILL \
+                                   : [m0] "+v"(m0), [m1] "+v"(m1), [t0] "+v"(t0), [t1] "+v"(t1) : [b] "v"(b), [c] "v"(c))
+#define LONE(SHIFT, TAIL) asm volatile(SHIFT "\n\t" TAIL : [m0] "+v"(m0), [m1] "+v"(m1) : [b] "v"(b), [c] "v"(c), [k] "v"(k256))
+#define LONE_MIX "v_perm_b32 %[m1], %[m1], %[b], %[c]\n\t" FILL_4
+#define LONE_B64(LO, HI, TAIL) asm volatile("v_lshlrev_b64 v[" #LO ":" #HI "], 8, v[" #LO ":" #HI "]\n\t" TAIL : [m0] "+v"(m0), [m1] "+v"(m1) : [b] "v"(b), [c] "v"(c) : "v" #LO, "v" #HI)
+#define SHL_B32 "v_lshlrev_b32 %[m0], 8, %[m0]"
+#define SHL_PK16 "v_pk_lshlrev_b16 %[m0], 8, %[m0] op_sel_hi:[0,1]"
+#define MUL_U24 "v_mul_u32_u24 %[m0], %[m0], %[k]"
+template <int OP, bool MIX> constexpr int unit_len() { return OP == 1 ? (MIX ? 12 : 5) : OP == 2 ? (MIX ? 13 : 6) : MIX ? 6 : 1; }
+template <int I, int OP, bool MIX>
+__device__ __forceinline__ void body_pair(uint32_t (&m)[8], uint32_t b, uint32_t c, uint32_t k256, uint32_t (&t)[8])
+{
+    if constexpr (I < UNITS) {
+        uint32_t& t0 = t[2 * (I % 4)];
+        uint32_t& t1 = t[2 * (I % 4) + 1];
+        uint32_t& m0 = m[2 * (I % 4)];
+        uint32_t& m1 = m[2 * (I % 4) + 1];
+        if constexpr (OP == 0 && I % 4 == 0) { if constexpr (MIX) LONE_B64(100, 101, LONE_MIX); else LONE_B64(100, 101, ""); }
+        else if constexpr (OP == 0 && I % 4 == 1) { if constexpr (MIX) LONE_B64(102, 103, LONE_MIX); else LONE_B64(102, 103, ""); }
+        else if constexpr (OP == 0 && I % 4 == 2) { if constexpr (MIX) LONE_B64(104, 105, LONE_MIX); else LONE_B64(104, 105, ""); }
+        else if constexpr (OP == 0) { if constexpr (MIX) LONE_B64(106, 107, LONE_MIX); else LONE_B64(106, 107, ""); }
+        else if constexpr (OP == 5 && !MIX) LONE(SHL_B32, "");
+        else if constexpr (OP == 5) LONE(SHL_B32, LONE_MIX);
+        else if constexpr (OP == 3 && !MIX) LONE(SHL_PK16, "");
+        else if constexpr (OP == 3) LONE(SHL_PK16, LONE_MIX);
+        else if constexpr (OP == 4 && !MIX) LONE(MUL_U24, "");
+        else if constexpr (OP == 4) LONE(MUL_U24, LONE_MIX);
+        else if constexpr (OP == 2 && !MIX) SINGLES(FILL_0);
+        else if constexpr (OP == 2) SINGLES(FILL_7);
+        else if constexpr (I % 4 == 0) { if constexpr (MIX) PAIRED(100, 101, FILL_7); else PAIRED(100, 101, FILL_0); }
+        else if constexpr (I % 4 == 1) { if constexpr (MIX) PAIRED(102, 103, FILL_7); else PAIRED(102, 103, FILL_0); }
+        else if constexpr (I % 4 == 2) { if constexpr (MIX) PAIRED(104, 105, FILL_7); else PAIRED(104, 105, FILL_0); }
+        else { if constexpr (MIX) PAIRED(106, 107, FILL_7); else PAIRED(106, 107, FILL_0); }
+        body_pair<I + 1, OP, MIX>(m, b, c, k256, t);
+    }
+}
+
+template <int OP, bool MIX>
+__global__ __launch_bounds__(64) void k_pair(uint32_t* out, uint32_t seed)
+{
+    extern __shared__ uint32_t dyn[];
+    uint32_t m[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) m[i] = seed * (2 * i + 5) + threadIdx.x;
+    uint32_t b = seed * 31 + 1, c = seed ^ 0x12345, k256 = 256u;
+    uint32_t t[8] = { 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u }; // (scratch registers of "two single", a pair per chain)
+    asm volatile("" : "+v"(k256));
+    for (int r = 0; r < TRIPS; ++r) body_pair<0, OP, MIX>(m, b, c, k256, t);
+    uint32_t s = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) s ^= m[i];
+    if (dyn[0] == 0x12345678u) s ^= 1;
+    out[blockIdx.x * 64 + threadIdx.x] = s;
+}
+
 // one instruction class per kernel: what each costs at the decode kernel's residency (two waves per SIMD)
 // 0 v_add_u32 (two sources)  1 v_bitop3_b32  2 v_perm_b32  3 v_alignbyte_b32  4 v_add3_u32  5 v_and_or_b32  6 v_add_u32 with an SGPR source
 // 7 v_and_or_b32 with an SGPR source  8 v_lshlrev_b32 (inline constant)  9 v_and_b32 with a 32-bit literal
@@ -131,7 +207,50 @@ template <typename K> void run(K kern, const char* name, uint32_t* d, int waves_
            ms * 1e-3 * ghz * 1e9 / inst_per_simd);
 }
 
-int main()
+// the shift forms: SIMD cycles per UNIT and per issued instruction
+template <typename K> void run_unit(K kern, const char* name, int len, uint32_t* d, int waves_per_simd, double ghz)
+{
+    const size_t lds = waves_per_simd == 1 ? 65536 - 512 : (size_t)(160 * 1024 / (4 * waves_per_simd)) - 512;
+    const int rounds = 4;
+    // (one wave per SIMD: 64 KB of LDS per single-wave workgroup lets a CU hold two, on two of its SIMDs: run_alone's shape)
+    const int blocks = waves_per_simd == 1 ? 256 * 2 * rounds : 256 * 4 * waves_per_simd * rounds;
+    (void)hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, 65536);
+    hipEvent_t e0, e1;
+    (void)hipEventCreate(&e0); (void)hipEventCreate(&e1);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, 0, d, 1u);
+    (void)hipDeviceSynchronize();
+    (void)hipEventRecord(e0);
+    hipLaunchKernelGGL(kern, dim3(blocks), dim3(64), lds, 0, d, 2u);
+    (void)hipEventRecord(e1); (void)hipEventSynchronize(e1);
+    float ms;
+    (void)hipEventElapsedTime(&ms, e0, e1);
+    const double units_per_simd = (waves_per_simd == 1 ? (double)rounds : (double)blocks / 1024.0) * TRIPS * UNITS;
+    const double cyc = ms * 1e-3 * ghz * 1e9 / units_per_simd;
+    printf("%-34s %d waves/SIMD  %8.3f ms  %6.2f SIMD-cycles per unit of %d  = %5.2f per instruction\n", name, waves_per_simd, ms, cyc, len, cyc / len);
+}
+#define RUN_UNIT(OP, MIX, NAME, W) run_unit(k_pair<OP, MIX>, NAME, unit_len<OP, MIX>(), d, W, ghz)
+
+int shift_forms(uint32_t* d, double ghz)
+{
+    printf("shift forms of the mask expander; 'paired' and 'two single' make two masks per unit, the lone shifts are one instruction:\n");
+    for (int w : { 1, 2, 8 }) {
+        RUN_UNIT(5, false, "v_lshlrev_b32 8", w);
+        RUN_UNIT(0, false, "v_lshlrev_b64 8", w);
+        RUN_UNIT(3, false, "v_pk_lshlrev_b16 8", w);
+        RUN_UNIT(4, false, "v_mul_u32_u24 256 (VGPR)", w);
+        RUN_UNIT(1, false, "paired: b64, 2 add, 2 perm", w);
+        RUN_UNIT(2, false, "two single: 2 b32, 2 add, 2 perm", w);
+        RUN_UNIT(5, true, "mix: v_lshlrev_b32, perm, 4 full", w);
+        RUN_UNIT(0, true, "mix: v_lshlrev_b64, perm, 4 full", w);
+        RUN_UNIT(3, true, "mix: v_pk_lshlrev_b16, perm, 4 full", w);
+        RUN_UNIT(4, true, "mix: v_mul_u32_u24, perm, 4 full", w);
+        RUN_UNIT(1, true, "mix: paired + 7 full", w);
+        RUN_UNIT(2, true, "mix: two single + 7 full", w);
+    }
+    return 0;
+}
+
+int main(int argc, char** argv)
 {
     hipDeviceProp_t p;
     (void)hipGetDeviceProperties(&p, 0);
@@ -140,6 +259,7 @@ int main()
            p.multiProcessorCount, ghz, BODY);
     uint32_t* d;
     (void)hipMalloc(&d, (size_t)256 * 4 * 8 * 4 * 64 * 4);
+    if (argc > 1 && argv[1][0] == 's') return shift_forms(d, ghz); // "shifts": only the table of DESIGN.md 3.1h
     run_alone(k<4>, "4 chains", d, ghz);
     run_alone(k<8>, "8 chains", d, ghz);
     for (int w : { 2, 3, 4, 5, 8 }) {
