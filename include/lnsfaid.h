@@ -802,6 +802,11 @@ int lnsfaid_message_store(const lnsfaid_ctx* ctx);
  * applies; LNSFAID_ZERO_SHIFT_LOOP keeps the layer loop of lnsfaid_kernel4z.hip there too (LNSFAID_E_INVAL where the rotation-free
  * kernel does not apply); LNSFAID_ZERO_SHIFT_STATIC asks for the twin, LNSFAID_E_INVAL where it does not apply.  Environment:
  * LNSFAID_ZERO_SHIFT=loop.
+ * Where the twin applies and the configuration cannot open the error-floor window (floor_iter_thresh < 0), the default, _ON and
+ * _STATIC launch the twin's window-free form (lnsfaid_kernel4w.hip): the same decoder without the window's per-layer work and
+ * with a text of its own for the first iteration.  LNSFAID_ZERO_SHIFT_WINDOWED keeps lnsfaid_kernel4s.hip there too
+ * (LNSFAID_E_INVAL where the twin does not apply).  Environment: LNSFAID_ZERO_SHIFT=windowed.  lnsfaid_window_free returns 1 if the
+ * next decode launches the window-free form, 0 if not (lnsfaid_zero_shift_groups reports 2 for either).
  * lnsfaid_zero_shift_groups returns 0 if the next decode launches the rotating kernel, 1 for the rotation-free kernel's layer loop,
  * 2 for its layer-static twin, and writes the number of whole rotation-free groups of four edges for each of the first n layers
  * (zeros when it is not in use; the twin also goes without rotation on the identity edges beyond them).
@@ -812,8 +817,10 @@ int lnsfaid_message_store(const lnsfaid_ctx* ctx);
 #define LNSFAID_ZERO_SHIFT_OFF 2
 #define LNSFAID_ZERO_SHIFT_LOOP 3
 #define LNSFAID_ZERO_SHIFT_STATIC 4
+#define LNSFAID_ZERO_SHIFT_WINDOWED 5
 int lnsfaid_select_zero_shift(lnsfaid_ctx* ctx, int32_t mode);
 int lnsfaid_zero_shift_groups(const lnsfaid_ctx* ctx, int32_t* groups, int32_t n);
+int lnsfaid_window_free(const lnsfaid_ctx* ctx);
 int lnsfaid_code_zero_shift_order(const lnsfaid_code* code, int32_t* groups, int32_t* order);
 
 /* The syndrome walk tables of the bit-flipping stage, without a GPU (for tests).  The stage flips block columns of weight

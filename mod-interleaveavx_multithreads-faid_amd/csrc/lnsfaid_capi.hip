@@ -46,6 +46,8 @@ extern "C" hipError_t lf_launch_decode4z(int method, const LfKernelArgs* args, s
 extern "C" int lf_decode4s_matches(const LfDevCode* code);
 extern "C" const void* lf_decode4s_func(int method);
 extern "C" hipError_t lf_launch_decode4s(int method, const LfKernelArgs* args, size_t lds_bytes, hipStream_t stream);
+extern "C" const void* lf_decode4w_func(int method);
+extern "C" hipError_t lf_launch_decode4w(int method, const LfKernelArgs* args, size_t lds_bytes, hipStream_t stream);
 extern "C" const void* lf_decode5_func(int method);
 extern "C" int lf_decode5_threads(void);
 extern "C" hipError_t lf_launch_decode5(int method, const LfKernelArgs* args, size_t lds_bytes, hipStream_t stream);
@@ -167,7 +169,8 @@ struct lnsfaid_ctx {
     int msg_store = 0;     /* 0: pick per code; 1: registers; 2: streamed through HBM (lnsfaid_select_message_store) */
     int zero_shift = 0;    /* 0: the rotation-free layer step where it applies; 1: the same, asked for; 2: off; 3: its layer loop
                             * (lnsfaid_kernel4z.hip) also where the layer-static kernel applies; 4: the layer-static kernel, asked
-                            * for (lnsfaid_select_zero_shift) */
+                            * for; 5: the same, and lnsfaid_kernel4s.hip also where its window-free twin applies
+                            * (lnsfaid_select_zero_shift) */
     mutable int static_code = -1; /* the code's zero-first edge tables equal the layer-static kernel's constants: -1 not compared yet */
     struct LfCombiner* comb = nullptr; /* call combiner this one-group context is a member of (see below) */
     int comb_slot = -1;
@@ -545,7 +548,8 @@ extern "C" int lnsfaid_create(lnsfaid_ctx** out, const lnsfaid_code* code, const
     if (const char* e = getenv("LNSFAID_MSG_STORE")) /* test / A-B switch, see lnsfaid_select_message_store */
         ctx->msg_store = (e[0] == 'h') ? LNSFAID_MSG_HBM : ((e[0] == 'r') ? LNSFAID_MSG_REGISTERS : 0);
     if (const char* e = getenv("LNSFAID_ZERO_SHIFT")) /* test / A-B switch, see lnsfaid_select_zero_shift: "off" / "on" */
-        ctx->zero_shift = (e[0] == 'o' && e[1] == 'f') ? LNSFAID_ZERO_SHIFT_OFF : (e[0] == 'l' ? LNSFAID_ZERO_SHIFT_LOOP : 0); /* "off" / "loop" */
+        ctx->zero_shift = (e[0] == 'o' && e[1] == 'f') ? LNSFAID_ZERO_SHIFT_OFF /* "off" / "loop" / "windowed" */
+                          : (e[0] == 'l' ? LNSFAID_ZERO_SHIFT_LOOP : (e[0] == 'w' ? LNSFAID_ZERO_SHIFT_WINDOWED : 0));
     g_live_contexts.fetch_add(1, std::memory_order_relaxed); /* (lnsfaid_destroy takes it back) */
     const int rc = create_impl(ctx, code, cfg);
     if (rc) { lnsfaid_destroy(ctx); return rc; }
@@ -671,12 +675,19 @@ static bool use_static_layers(const lnsfaid_ctx* ctx)
 {
     return use_zero_shift(ctx) && ctx->zero_shift != LNSFAID_ZERO_SHIFT_LOOP && static_layers_possible(ctx);
 }
+/* The window-free kernel (lnsfaid_kernel4w.hip) takes the layer-static kernel's place where the configuration cannot open the
+ * error-floor window: nombre_iterations <= floor_iter_thresh never holds for a negative threshold (the shipped DecodeMethod 2). */
+static bool use_window_free(const lnsfaid_ctx* ctx)
+{
+    return use_static_layers(ctx) && ctx->zero_shift != LNSFAID_ZERO_SHIFT_WINDOWED && ctx->hcfg.floor_iter_thresh < 0 &&
+           lf_decode4w_func(ctx->hcfg.method);
+}
 
 extern "C" int lnsfaid_select_zero_shift(lnsfaid_ctx* ctx, int32_t mode)
 {
-    if (!ctx || mode < 0 || mode > LNSFAID_ZERO_SHIFT_STATIC) return LNSFAID_E_INVAL;
+    if (!ctx || mode < 0 || mode > LNSFAID_ZERO_SHIFT_WINDOWED) return LNSFAID_E_INVAL;
     if ((mode == LNSFAID_ZERO_SHIFT_ON || mode == LNSFAID_ZERO_SHIFT_LOOP) && !zero_shift_possible(ctx)) return LNSFAID_E_INVAL;
-    if (mode == LNSFAID_ZERO_SHIFT_STATIC && !static_layers_possible(ctx)) return LNSFAID_E_INVAL;
+    if ((mode == LNSFAID_ZERO_SHIFT_STATIC || mode == LNSFAID_ZERO_SHIFT_WINDOWED) && !static_layers_possible(ctx)) return LNSFAID_E_INVAL;
     ctx->zero_shift = mode;
     return LNSFAID_OK;
 }
@@ -687,6 +698,12 @@ extern "C" int lnsfaid_zero_shift_groups(const lnsfaid_ctx* ctx, int32_t* groups
     const bool on = use_zero_shift(ctx);
     for (int br = 0; br < n; ++br) groups[br] = (on && br < ctx->hcode.nbr) ? layer_zero_groups(ctx, br) : 0;
     return on ? (use_static_layers(ctx) ? 2 : 1) : 0;
+}
+
+extern "C" int lnsfaid_window_free(const lnsfaid_ctx* ctx)
+{
+    if (!ctx) return LNSFAID_E_INVAL;
+    return use_window_free(ctx) ? 1 : 0;
 }
 
 extern "C" int lnsfaid_code_zero_shift_order(const lnsfaid_code* code, int32_t* groups, int32_t* order)
@@ -764,6 +781,7 @@ static const void* selected_kernel(const lnsfaid_ctx* ctx, int* threads, int rul
     }
     if (use_zero_shift(ctx)) {
         *threads = lf_decode4_threads();
+        if (use_window_free(ctx)) return lf_decode4w_func(ctx->hcfg.method);
         return use_static_layers(ctx) ? lf_decode4s_func(ctx->hcfg.method) : lf_decode4z_func(ctx->hcfg.method);
     }
     if (use_kernel4(ctx)) {
@@ -957,6 +975,7 @@ static int decode_device_impl(lnsfaid_ctx* ctx, const int8_t* d_fixInput, size_t
             HIP_TRY(hipEventRecord(ctx->ev_chain[j], ctx->stream));
             if (packed) HIP_TRY(lf_launch_decode4p(ctx->hcfg.method, ctx->hcfg.ef, use_msg_registers(ctx) ? 1 : 0, &a, ctx->lds_bytes, ctx->stream));
             else if (use_kernel5(ctx)) HIP_TRY(lf_launch_decode5(ctx->hcfg.method, &a, ctx->lds_bytes, ctx->stream));
+            else if (use_window_free(ctx)) HIP_TRY(lf_launch_decode4w(ctx->hcfg.method, &a, ctx->lds_bytes, ctx->stream));
             else if (use_static_layers(ctx)) HIP_TRY(lf_launch_decode4s(ctx->hcfg.method, &a, ctx->lds_bytes, ctx->stream));
             else if (use_zero_shift(ctx)) HIP_TRY(lf_launch_decode4z(ctx->hcfg.method, &a, ctx->lds_bytes, ctx->stream));
             else if (use_kernel4(ctx)) HIP_TRY(lf_launch_decode4(ctx->hcfg.method, ctx->hcfg.ef, use_msg_registers(ctx) ? 1 : 0, &a, ctx->lds_bytes, ctx->stream));

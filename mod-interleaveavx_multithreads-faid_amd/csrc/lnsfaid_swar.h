@@ -148,6 +148,8 @@ struct SwK {
     uint32_t n_lo, n_hi; /* thermometer code -> number (sw_therm2num) */
     uint32_t c55, c33, c0f; /* merge masks of pass 2's sign words */
     uint32_t cm27;    /* -0x27272727: the last constant of sw_update2, as an addend of v_add3_u32 */
+    uint32_t tm[4];   /* SW_FORM_NOWIN only, set by its caller once per iteration: thermometer code -> magnitude (sw_therm2msg_tables of
+                       * the row's one table: lut_* for the FAID decoders, oms_*[0] for the min-sum ones) */
 };
 SW_FN SwK sw_consts(uint32_t dep = 0u)
 {
@@ -163,6 +165,7 @@ SW_FN SwK sw_consts(uint32_t dep = 0u)
     k.n_lo = sw_vconst(SW_T2N_LO, dep); k.n_hi = sw_vconst(SW_T2N_HI, dep);
     k.c55 = sw_vconst(0x55555555u, dep); k.c33 = sw_vconst(0x33333333u, dep); k.c0f = sw_vconst(0x0f0f0f0fu, dep);
     k.cm27 = sw_vconst(0u - 0x27272727u, dep);
+    for (int w = 0; w < 4; ++w) k.tm[w] = 0u;
     return k;
 }
 
@@ -217,6 +220,29 @@ SW_FN uint32_t sw_therm2num(uint32_t x, uint32_t n_lo, uint32_t n_hi)
 {
     const uint32_t a = sw_perm(n_hi, n_lo, x & 0x0f0f0f0fu);
     const uint32_t b = sw_perm(n_hi, n_lo, (x >> 4) & 0x07070707u);
+    return a ^ b;
+}
+/* sw_therm2num composed with an 8-entry byte table LUT (entries 0..3 in lut_lo, 4..7 in lut_hi): the row's magnitude LUT[min] straight
+ * from the thermometer code, in the six instructions of sw_therm2num - for a layer step that reads ONE table (SW_FORM_NOWIN).  The low
+ * nibble's look-up A and the look-up B of bits 4..6 each get a table of their own, over the selectors 0 / 1 / 3 / 7 of sw_therm2num
+ * (a full low nibble is selector 15 and still saturates to 0xff).  With C = ~LUT[4]:
+ *   A[code of n] = LUT[n] ^ C (n = 0..3),   B[0] = C,   B[code of n - 4] = ~LUT[n] (n = 5..7)
+ *   n <= 3: A ^ B = LUT[n] ^ C ^ C          n == 4: 0xff ^ C = LUT[4]          n >= 5: 0xff ^ ~LUT[n] = LUT[n]
+ * tm[0], tm[1]: A's entries 0..3 / 4..7; tm[2], tm[3]: B's. */
+SW_HD void sw_therm2msg_tables(uint32_t lut_lo, uint32_t lut_hi, uint32_t tm[4])
+{
+    const uint32_t c = ~lut_hi & 0xffu;                   /* C                                   */
+    const uint32_t a = lut_lo ^ (c * 0x01010101u);        /* LUT[0..3] ^ C, byte n               */
+    const uint32_t nb = ~lut_hi;                          /* ~LUT[4..7], byte n - 4              */
+    tm[0] = (a & 0x0000ffffu) | ((a & 0x00ff0000u) << 8); /* codes 0, 1 -> n = 0, 1; code 3 -> n = 2 */
+    tm[1] = a & 0xff000000u;                              /* code 7 -> n = 3                     */
+    tm[2] = c | (nb & 0x0000ff00u) | ((nb & 0x00ff0000u) << 8); /* codes 0, 1 -> n = 4, 5; code 3 -> n = 6 */
+    tm[3] = nb & 0xff000000u;                             /* code 7 -> n = 7                     */
+}
+SW_FN uint32_t sw_therm2msg(uint32_t x, const uint32_t tm[4])
+{
+    const uint32_t a = sw_perm(tm[1], tm[0], x & 0x0f0f0f0fu);
+    const uint32_t b = sw_perm(tm[3], tm[2], (x >> 4) & 0x07070707u);
     return a ^ b;
 }
 /* 0xff in every byte that is zero; bytes must be <= 0x7f */
@@ -627,10 +653,22 @@ struct SwTabStatic {
 #define SW_PAIRS_PASS2 2
 #define SW_PAIRS_ROW 4
 #define SW_PAIRS_ALL (SW_PAIRS_PASS1 | SW_PAIRS_PASS2 | SW_PAIRS_ROW)
-template <int METHOD, int DEG, bool ERA = false, int WAVES = 1, int WAVE = 0, int ZG = 0, int PAIRS = 0, class Tab, class Xch = SwNoXch>
+/* FORM: what the caller knows about the iteration the step runs in, a bit each (0: nothing - the step as every kernel but the window-free
+ * one, lnsfaid_kernel4w.hip, instantiates it).  One wave per codeword, non-erasing instances only.
+ *   SW_FORM_NOWIN  the error-floor window cannot open (floor_iter_thresh < 0): rowpar, lme, p.window and the window's tables are not
+ *                  looked at, and the row's magnitudes come straight from the thermometer codes through K.tm (sw_therm2msg) instead of
+ *                  sw_therm2num and a look-up in one of two tables.  Not for DecodeMethod 0, whose levels are the magnitudes.
+ *   SW_FORM_FRESH  the first iteration: `cur` is all zero (not looked at) and `fresh` is true, so there is no old patch, the old message
+ *                  on every edge is +0 (the edges' sign bit, selector and table look-up are constants) and so is the arg-min edge's. */
+#define SW_FORM_NOWIN 1
+#define SW_FORM_FRESH 2
+template <int METHOD, int DEG, bool ERA = false, int WAVES = 1, int WAVE = 0, int ZG = 0, int PAIRS = 0, int FORM = 0, class Tab, class Xch = SwNoXch>
 SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, const SwK& K, uint32_t lane, int deg, SwRow cur, bool fresh,
                           uint32_t rowpar, bool lme, uint32_t era_edges = 0u, uint32_t era_plane = 0u, const Xch& xch = Xch())
 {
+    constexpr bool NOWIN = (FORM & SW_FORM_NOWIN) != 0, FRESH = (FORM & SW_FORM_FRESH) != 0;
+    static_assert(FORM == 0 || (WAVES == 1 && !ERA), "iteration forms: one-wave, non-erasing instances");
+    static_assert(!NOWIN || METHOD != 0, "the normalised min-sum rows read no table after the search");
     static_assert(WAVES == 1 || !ERA, "the erasing variant is built for one wave per codeword only");
     /* ERA (EF_ELIMINATION 2, CDecoder_FAID.cpp:673-680; the caller instantiates it only inside the error-floor window of a
      * codeword with few unsatisfied checks): era_edges bit j = edge j is the first edge, in row order, of a block column of
@@ -665,11 +703,13 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
     const uint32_t bias = MINSUM ? 0u : 0x06040200u;
     const uint32_t kt_lo = sw_perm(kn, kp, 0x05010400u) + (MINSUM ? 0u : 0x02020000u), kt_hi = sw_perm(kn, kp, 0x07030602u) + (MINSUM ? 0u : 0x06060404u);
     const uint32_t tt_lo = K.tt_lo, tt_hi = K.tt_hi; /* thermometer code of min(|t|, 7) */
+    /* FRESH: c2o == 0 and no edge's old message is negative, so every edge's selector is its row part and the look-up returns 8 + it */
+    const uint32_t k_fresh = 0x08080808u + bias;
 
     /* ---- the old arg-min edge carries c1, not c2: move its En by the difference so that "every edge carries c2" holds ---- */
     uint32_t padd = 0, psub = 0; /* what the patch below adds to / takes from the old arg-min nodes' LDS bytes */
 #ifndef SW_EXP_NO_OLDPATCH
-    if (!fresh && WAVE == 0) {
+    if (!FRESH && !fresh && WAVE == 0) {
         const uint32_t a0 = cur.pa[0] & 0xffffu, a1 = cur.pa[0] >> 16, a2 = cur.pa[1] & 0xffffu, a3 = cur.pa[1] >> 16;
         SW_SCHED_FENCE(); /* the four reads back to back: one LDS round trip, not one per read */
         const uint32_t g0 = lds.rd8(a0), g1 = lds.rd8(a1), g2 = lds.rd8(a2), g3 = lds.rd8(a3);
@@ -751,9 +791,13 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
         /* byte k = En + 120 of row k.  The group's LAST read is consumed first: LDS reads return in order, so the one s_waitcnt in
          * front of it covers the group (in ascending order every edge gets a wait of its own) */
         _Pragma("unroll") for (int g = SW_ILP - 1; g >= 0; --g) { const int j = j0 + g; if (j < NJ && (DEG > 0 || j < deg) && SW_OWN(j)) r_[g] = j < NZ ? ld[j] : sw_alignbyte(ld[j], ld[j], rq[j]); }
-        SW_EDGES(x_[g] = (j & 7) ? cur.x[j >> 3] >> (j & 7) : cur.x[j >> 3];)
-        SW_EDGES(s_[g] = sw_bitop3<SW_TT_ANDOR>(x_[g], c01, c0642);)
-        SW_EDGES(k_[g] = sw_perm(kt_hi, kt_lo, s_[g]);)
+        if (FRESH) { /* no shift, no selector build, no look-up: constants */
+            SW_EDGES(x_[g] = 0u; s_[g] = c0642; k_[g] = k_fresh;)
+        } else {
+            SW_EDGES(x_[g] = (j & 7) ? cur.x[j >> 3] >> (j & 7) : cur.x[j >> 3];)
+            SW_EDGES(s_[g] = sw_bitop3<SW_TT_ANDOR>(x_[g], c01, c0642);)
+            SW_EDGES(k_[g] = sw_perm(kt_hi, kt_lo, s_[g]);)
+        }
         /* t + 128, VECTOR_SUB_AND_SATURATE comes in pass 2.  (A rotation-free group has no rotate: this is the first use of its reads,
          * so it takes their descending order; a group with a rotating edge in it keeps the rotates' order) */
         if ((j0 + SW_ILP < NJ ? j0 + SW_ILP : NJ) <= NZ) { _Pragma("unroll") for (int g = SW_ILP - 1; g >= 0; --g) if (j0 + g < NJ) tb[j0 + g] = r_[g] + k_[g]; }
@@ -801,7 +845,8 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
             SW_EDGES(u_[g] = sw_perm(p.nms_t[1], p.nms_t[0], a_[g]);)
             SW_EDGES(u_[g] = sw_bitop3<SW_TT_SEL>(h_[g], i_[g], u_[g]);)
         } else {
-            SW_EDGES(i_[g] = MINSUM ? sw_bitop3<SW_TT_NANDOR>(ms[j], c01, c78) : sw_bitop3<SW_TT_XNOR_AND>(x_[g], ms[j], c01);)
+            if (FRESH && !MINSUM) { SW_EDGES(i_[g] = sw_bitop3<0x0a>(ms[j], ms[j], c01);) } /* ~a & c: SW_TT_XNOR_AND with x_ == 0 */
+            else { SW_EDGES(i_[g] = MINSUM ? sw_bitop3<SW_TT_NANDOR>(ms[j], c01, c78) : sw_bitop3<SW_TT_XNOR_AND>(x_[g], ms[j], c01);) }
             SW_EDGES(a_[g] = (MINSUM ? a_[g] + i_[g] : a_[g] + i_[g] + c78) & 0x87878787u;)     /* v_add3_u32 */
             SW_EDGES(u_[g] = sw_perm(tt_hi, tt_lo, a_[g]);)
         }
@@ -838,9 +883,13 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
 
     /* ---- the row's new magnitudes ---- */
     const uint32_t n_lo = WAVES == 2 ? SW_T2N_LO : K.n_lo, n_hi = WAVES == 2 ? SW_T2N_HI : K.n_hi;
-    const uint32_t min1 = sw_therm2num(t1, n_lo, n_hi), min2 = sw_therm2num(t2, n_lo, n_hi);
+    const uint32_t min1 = NOWIN ? 0u : sw_therm2num(t1, n_lo, n_hi), min2 = NOWIN ? 0u : sw_therm2num(t2, n_lo, n_hi);
     uint32_t c1n, c2n;
-    if (METHOD == 0) {
+    if (NOWIN) {
+        /* one table, whatever the row's parity: composed with the thermometer decode (cste_2 from min1, cste_1 from min2) */
+        c2n = sw_therm2msg(t1, K.tm);
+        c1n = sw_therm2msg(t2, K.tm);
+    } else if (METHOD == 0) {
         /* the levels of the search ARE cste() of the minima (CLDPC.cpp:337-352: cste_2 from min1, cste_1 from min2, one factor) */
         c2n = min1;
         c1n = min2;
@@ -974,10 +1023,11 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
         nm3 = (DEG == 0 && deg <= 8) ? 0xffffffffu : sw_mask7(ne7_3, sel_sign);
     }
     /* old message on that edge negative: bit (index mod 8) of byte k of sign word (index div 8), as 2 k + b: the v_perm selector */
-    const uint32_t selA = sw_argmin_selector(sw_word_pick(nm3, nm4, cur.x[0], cur.x[1], cur.x[2]), oh8, c7f, c01, c0642);
+    /* (FRESH: not negative on any edge, the selector is its row part) */
+    const uint32_t selA = FRESH ? c0642 : sw_argmin_selector(sw_word_pick(nm3, nm4, cur.x[0], cur.x[1], cur.x[2]), oh8, c7f, c01, c0642);
     if (ERA) xb = selA & c01;
     const uint32_t gb = sw_gather4(gk0, gk1, gk2, gk3);
-    uint32_t tbA = gb + sw_perm(kt_hi, kt_lo, selA); /* carries `bias` like tb[] */
+    uint32_t tbA = gb + (FRESH ? k_fresh : sw_perm(kt_hi, kt_lo, selA)); /* carries `bias` like tb[] */
     if (ERA) { /* the arg-min edge of a row may be an erased one (a V2C of 0 usually IS the minimum) */
         uint32_t em = 0, match = 0;
 #pragma unroll

@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(HERE, "csrc", "liblnsfaid.so")
 
 GROUP = 32
 MSG_REGISTERS, MSG_HBM = 1, 2  # lnsfaid_select_message_store
-ZERO_SHIFT_ON, ZERO_SHIFT_OFF, ZERO_SHIFT_LOOP, ZERO_SHIFT_STATIC = 1, 2, 3, 4  # lnsfaid_select_zero_shift
+ZERO_SHIFT_ON, ZERO_SHIFT_OFF, ZERO_SHIFT_LOOP, ZERO_SHIFT_STATIC, ZERO_SHIFT_WINDOWED = 1, 2, 3, 4, 5  # lnsfaid_select_zero_shift
 STOP_GROUP, STOP_CODEWORD = 0, 1  # lnsfaid_set_early_stop
 LINE_HARD, LINE_LLR4 = 0, 1  # lnsfaid_decode_line: one bit / one 4-bit LLR per transmitted code bit
 
@@ -168,6 +168,7 @@ SYMBOLS = {
     "lnsfaid_message_store": (C.c_int, [C.c_void_p]),
     "lnsfaid_select_zero_shift": (C.c_int, [C.c_void_p, C.c_int32]),
     "lnsfaid_zero_shift_groups": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
+    "lnsfaid_window_free": (C.c_int, [C.c_void_p]),
     "lnsfaid_code_zero_shift_order": (C.c_int, [C.POINTER(Code), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lnsfaid_code_bf_walk": (C.c_int, [C.POINTER(Code), C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                       C.POINTER(C.c_int32)]),
@@ -918,7 +919,7 @@ class Decoder:
         return self.lib.lnsfaid_message_store(self.ctx)
 
     def select_zero_shift(self, mode):
-        """0 default, ZERO_SHIFT_ON, ZERO_SHIFT_OFF, ZERO_SHIFT_LOOP, ZERO_SHIFT_STATIC (lnsfaid_select_zero_shift)"""
+        """0 default, ZERO_SHIFT_ON, ZERO_SHIFT_OFF, ZERO_SHIFT_LOOP, ZERO_SHIFT_STATIC, ZERO_SHIFT_WINDOWED (lnsfaid_select_zero_shift)"""
         self._check(self.lib.lnsfaid_select_zero_shift(self.ctx, mode), "lnsfaid_select_zero_shift")
 
     def zero_shift_groups(self, n_layers=32):
@@ -933,6 +934,12 @@ class Decoder:
         on = self.lib.lnsfaid_zero_shift_groups(self.ctx, None, 0)
         self._check(min(on, 0), "lnsfaid_zero_shift_groups")
         return on == 2
+
+    def window_free(self):
+        """the next decode launches the layer-static kernel's window-free form (lnsfaid_kernel4w.hip)"""
+        on = self.lib.lnsfaid_window_free(self.ctx)
+        self._check(min(on, 0), "lnsfaid_window_free")
+        return on == 1
 
     def kernel_residency(self):
         """(workgroups per CU of the selected kernel, what its LDS alone allows)"""
