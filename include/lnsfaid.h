@@ -437,6 +437,66 @@ int lnsfaid_line_soft_device(lnsfaid_ctx* ctx, const uint32_t* d_line_in, size_t
 int lnsfaid_line_soft_host(const lnsfaid_code* code, const uint32_t* line_in, size_t n_codewords, uint64_t key, uint64_t first_codeword,
                            const uint32_t table[14], uint8_t* llr4_out, uint32_t* flips, uint64_t* total_flips);
 
+/* ---- burst-format line calls ------------------------------------------------------------------------------
+ * The line-format decode and encode for bursts: lines whose codewords are individually *shortened*.  A burst ends where its
+ * allocation ends, so its last codeword carries fewer than K payload bits: the payload is padded with known zeros up to K, the
+ * parity is computed over the padded word, and the pad is not transmitted.  These calls take such lines as they are, any mix of
+ * shortenings in one call, with no expanded image in memory.  N = n_var, K = n_var - n_check, L = n_var - puncture_tail as in the
+ * line sections; all three must be multiples of 32, LNSFAID_E_INVAL otherwise.
+ *   shortened  const uint32_t [n_codewords]: S_c, the shortening of codeword c in bits.  A *host* pointer in every form, the device
+ *            forms included (as `table` is for lnsfaid_line_soft_device); NULL means all zero.  The rule is S_c % 32 == 0 and
+ *            0 <= S_c <= K - 32; anything else is LNSFAID_E_INVAL, and a refused call writes nothing.  Word granularity is
+ *            deliberate: every format of the line calls is word-based, and with it every codeword of a burst stays 4-byte aligned.
+ *            Bit-granular shortening is out of scope.
+ *   where    uniform over the call: where the known zeros sit in the information part.  LNSFAID_SHORTEN_TAIL: positions
+ *            K - S_c .. K - 1 (the reference's _ShortenBits convention); LNSFAID_SHORTEN_HEAD: positions 0 .. S_c - 1.  With
+ *            k0 = K - S_c or 0 the known range is [k0, k0 + S_c) in both cases.  Any other value is LNSFAID_E_INVAL.
+ *   burst line  codeword c occupies (L - S_c) / 32 words (LNSFAID_LINE_HARD) or (L - S_c) / 2 bytes (LNSFAID_LINE_LLR4), back to back
+ *            with no gaps.  Inside a codeword the order is the mother codeword's positions 0 .. L - 1 with the known range removed;
+ *            bit and nibble order are exactly those of the line formats.
+ *   burst payload  codeword c occupies (K - S_c) / 32 words, back to back: the information bits with the known range removed.  The
+ *            payloads of a burst are still one contiguous bit stream.
+ *   bits     optional, decode and encode, unchanged: the whole mother codeword, N / 32 words per codeword at a fixed stride, known
+ *            positions included.  On encode the known positions are 0; on decode they hold what the decoder decided, so
+ *            lnsfaid_fec_status_packed_* can follow (with the llr4 of lnsfaid_burst_to_llr4).
+ * A known position enters the decoder as level -7: positive means bit 1 everywhere in this library, and -7 is the strongest level a
+ * line can carry.  A decoder may still decide 1 there, so the decode calls also return that count:
+ *   stats    optional, lnsfaid_line_stats [n_codewords]; the struct is unchanged.  `corrected` counts transmitted positions only: the
+ *            mother positions < L outside the known range at which the decision differs from the channel's own.
+ *   short_ones  optional, uint32_t [n_codewords]: the known positions decided as 1.  A receiver treats short_ones > 0 like
+ *            unsatisfied > 0.
+ * One definition, as for the line calls: lnsfaid_burst_to_llr4 lays a burst line out as the llr4 of ceil(n_codewords / 32) whole
+ * groups - known range nibble -7, punctured tail and padding codewords nibble 0, the rest as lnsfaid_line_to_llr4 - and for every
+ * codeword the burst decode returns what lnsfaid_decode_codewords_packed* returns for that llr4: all words as bits, the information
+ * words minus the known ones as payload, and iterations, bf_iterations and unsatisfied.  With shortened == NULL (or all zero) every
+ * output is byte for byte that of lnsfaid_decode_line* / lnsfaid_encode_line*.
+ * lnsfaid_encode_burst_host is the definition of the encode calls: the payload expanded with zeros in the known range,
+ * lnsfaid_encode_line_host, the known words dropped from the line; circ and circ_bytes as there.
+ * lnsfaid_burst_words: host only; validates `shortened` by the rule above and returns the totals of a burst as bit counts (sum of
+ * L - S_c and of K - S_c; either pointer may be NULL), with which the caller sizes line and payload.
+ * Every other rule is that of the corresponding line call: n_codewords 0 (a no-op) .. 32 * max_groups; device pointers 4-byte
+ * aligned, host pointers of any alignment (they go through the context's staging buffers); decoding under the per-codeword rule
+ * (the two-rows kernel and lnsfaid_select_waves(ctx, 2) are refused); encoding independent of the decoder configuration, with
+ * LNSFAID_E_CODE for a singular parity part; the calls return when the outputs are complete.  On the GPU only the built-in code's
+ * circulant size is served, as for the line calls. */
+#define LNSFAID_SHORTEN_TAIL 0
+#define LNSFAID_SHORTEN_HEAD 1
+int lnsfaid_decode_burst(lnsfaid_ctx* ctx, const void* line, int32_t format, int32_t magnitude, const uint32_t* shortened, int32_t where,
+                         size_t n_codewords, uint32_t* payload, uint32_t* bits, lnsfaid_line_stats* stats, uint32_t* short_ones);
+int lnsfaid_decode_burst_device(lnsfaid_ctx* ctx, const void* d_line, int32_t format, int32_t magnitude, const uint32_t* shortened,
+                                int32_t where, size_t n_codewords, uint32_t* d_payload, uint32_t* d_bits, lnsfaid_line_stats* d_stats,
+                                uint32_t* d_short_ones);
+int lnsfaid_encode_burst(lnsfaid_ctx* ctx, const uint32_t* payload, const uint32_t* shortened, int32_t where, size_t n_codewords,
+                         uint32_t* line, uint32_t* bits);
+int lnsfaid_encode_burst_device(lnsfaid_ctx* ctx, const uint32_t* d_payload, const uint32_t* shortened, int32_t where, size_t n_codewords,
+                                uint32_t* d_line, uint32_t* d_bits);
+int lnsfaid_encode_burst_host(const lnsfaid_code* code, const uint8_t* circ, size_t circ_bytes, const uint32_t* payload,
+                              const uint32_t* shortened, int32_t where, size_t n_codewords, uint32_t* line, uint32_t* bits);
+int lnsfaid_burst_to_llr4(const lnsfaid_code* code, const void* line, int32_t format, int32_t magnitude, const uint32_t* shortened,
+                          int32_t where, size_t n_codewords, uint8_t* llr4);
+int lnsfaid_burst_words(const lnsfaid_code* code, const uint32_t* shortened, size_t n_codewords, uint64_t* line_bits,
+                        uint64_t* payload_bits);
+
 /* ---- front-end on the device (optional, the host generator stays the parity source) ---- */
 
 /*

@@ -18,6 +18,7 @@
 
 #include "lnsfaid_device.h"
 #include "lnsfaid_line.h"
+#include "lnsfaid_burst.h"
 #include "lnsfaid_quantise.h"
 #include "lnsfaid_swar.h" /* sw_nms_fits / sw_nms_tables (host side) */
 
@@ -79,6 +80,11 @@ extern "C" hipError_t lf_launch_encode_line(const LfDevCode* d_code, int n_check
                                             const uint32_t* d_payload, size_t n_codewords, uint32_t* d_line, uint32_t* d_bits,
                                             hipStream_t stream);
 
+extern "C" const void* lf_decode4b_func(int method, int ef, int rm);
+extern "C" hipError_t lf_launch_decode4b(int method, int ef, int rm, const LfBurstArgs* args, size_t lds_bytes, hipStream_t stream);
+extern "C" hipError_t lf_launch_encode_burst(const LfDevCode* d_code, int n_check, const uint32_t* d_bsup, const uint32_t* d_bsup_off,
+                                             const uint32_t* d_payload, const LfBurstDesc* d_desc, int where, size_t n_codewords,
+                                             uint32_t* d_line, uint32_t* d_bits, hipStream_t stream);
 extern "C" hipError_t lf_launch_line_bsc(const uint32_t* d_in, uint32_t* d_out, size_t n_cw, uint32_t lw, uint64_t key, uint64_t first,
                                          uint32_t threshold, uint32_t* d_flips, unsigned long long* d_total, hipStream_t stream);
 extern "C" hipError_t lf_launch_line_payload(uint32_t* d_payload, size_t n_cw, uint32_t kw, uint64_t key, uint64_t first, hipStream_t stream);
@@ -163,6 +169,11 @@ struct lnsfaid_ctx {
     uint32_t* d_ln_payload = nullptr;       /* K words per group */
     lnsfaid_line_stats* d_ln_stats = nullptr;
     const void* checked_line_fn = nullptr;  /* line kernel instance whose static LDS has been looked at */
+    /* burst-format line calls, allocated at their first call */
+    LfBurstDesc* d_burst_desc = nullptr;    /* [32 * max_groups] descriptors of the call in flight */
+    LfBurstDesc* h_burst_desc = nullptr;    /* pinned: where the host forms its prefix sums */
+    uint32_t* d_burst_ones = nullptr;       /* short_ones of the host-pointer decode */
+    const void* checked_burst_fn = nullptr; /* burst kernel instance whose static LDS has been looked at */
     int early_stop = LNSFAID_STOP_GROUP; /* rule of lnsfaid_decode / lnsfaid_decode_device (lnsfaid_set_early_stop) */
     int rows_per_lane = 0; /* 0: pick per configuration; 2 / 4: forced (lnsfaid_select_kernel) */
     int waves_per_cw = 0;  /* 0 / 1: one wave per codeword; 2: lnsfaid_kernel5.hip where it applies (lnsfaid_select_waves) */
@@ -454,6 +465,8 @@ extern "C" void lnsfaid_destroy(lnsfaid_ctx* ctx)
     (void)hipFree(ctx->d_io_cw_stats);
     (void)hipFree(ctx->d_pk_in); (void)hipFree(ctx->d_pk_out); (void)hipFree(ctx->d_pk_stats);
     (void)hipFree(ctx->d_ln_payload); (void)hipFree(ctx->d_ln_stats);
+    (void)hipFree(ctx->d_burst_desc); (void)hipFree(ctx->d_burst_ones);
+    if (ctx->h_burst_desc) (void)hipHostFree(ctx->h_burst_desc);
     (void)hipFree(ctx->d_fe_seeds); (void)hipFree(ctx->d_fe_draws); (void)hipFree(ctx->d_fe_codeword);
     (void)hipFree(ctx->d_fe_frames); (void)hipFree(ctx->d_fe_input);
     (void)hipFree(ctx->d_enc_sup); (void)hipFree(ctx->d_enc_off); (void)hipFree(ctx->d_fe_keys);
@@ -2425,6 +2438,174 @@ extern "C" int lnsfaid_encode_line(lnsfaid_ctx* ctx, const uint32_t* payload, si
     HIP_TRY(lf_launch_encode_line(ctx->d_code, ctx->n_check, ctx->d_enc_sup, ctx->d_enc_off, d_payload, n_codewords, d_line,
                                   bits ? ctx->d_pk_out : nullptr, ctx->stream));
     HIP_TRY(hipMemcpyAsync(line, d_line, n_codewords * l_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (bits) HIP_TRY(hipMemcpyAsync(bits, ctx->d_pk_out, n_codewords * n_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    return stream_wait(ctx);
+}
+
+/* ---- burst-format line calls (include/lnsfaid.h "burst-format line calls", DESIGN.md 3.18, lnsfaid_kernel4b.hip,
+ * lnsfaid_encoder_burst.hip; host forms in lnsfaid_tables.c) ----------------------------------------------------------------- */
+/* `shortened` (a host pointer of any alignment, or NULL) by the rule of the header, and the descriptors of the call: prefix sums
+ * into the context's pinned array, one copy on its stream into its device array.  The totals are in words of 32 positions. */
+static int burst_descriptors(lnsfaid_ctx* ctx, const uint32_t* shortened, int32_t where, size_t n_codewords, size_t* line_units,
+                             size_t* payload_words)
+{
+    if (where != LNSFAID_SHORTEN_TAIL && where != LNSFAID_SHORTEN_HEAD) return LNSFAID_E_INVAL;
+    const uint32_t K = (uint32_t)ctx->k_info, L = (uint32_t)(ctx->n_var - ctx->hcode.puncture_tail);
+    if (ctx->n_var % 32 != 0 || L < K) return LNSFAID_E_INVAL;
+    for (size_t c = 0; shortened && c < n_codewords; ++c) {
+        uint32_t s;
+        memcpy(&s, (const uint8_t*)shortened + 4 * c, 4);
+        if (s % 32u != 0u || (uint64_t)s + 32u > K) return LNSFAID_E_INVAL;
+    }
+    HIP_TRY(hipSetDevice(ctx->device));
+    if (!ctx->d_burst_desc) {
+        const size_t bytes = ctx->max_groups * LNSFAID_GROUP * sizeof(LfBurstDesc);
+        HIP_TRY(hipHostMalloc((void**)&ctx->h_burst_desc, bytes, hipHostMallocDefault));
+        HIP_TRY(hipMalloc(&ctx->d_burst_desc, bytes));
+    }
+    uint32_t lo = 0, po = 0; /* at most 65 536 codewords of L / 32 words each: below 2^26 */
+    for (size_t c = 0; c < n_codewords; ++c) {
+        uint32_t s = 0;
+        if (shortened) memcpy(&s, (const uint8_t*)shortened + 4 * c, 4);
+        ctx->h_burst_desc[c] = LfBurstDesc{ lo, po, s / 32u, 0u };
+        lo += (L - s) / 32u;
+        po += (K - s) / 32u;
+    }
+    HIP_TRY(hipMemcpyAsync(ctx->d_burst_desc, ctx->h_burst_desc, n_codewords * sizeof(LfBurstDesc), hipMemcpyHostToDevice, ctx->stream));
+    *line_units = lo;
+    *payload_words = po;
+    return LNSFAID_OK;
+}
+
+/* decode_line_launch with the descriptors: one launch, one wait */
+static int decode_burst_launch(lnsfaid_ctx* ctx, const void* d_line, int32_t format, int32_t magnitude, int32_t where, size_t n_codewords,
+                               uint32_t* d_payload, uint32_t* d_bits, lnsfaid_line_stats* d_stats, uint32_t* d_short_ones)
+{
+    const int rm = use_msg_registers(ctx) ? 1 : 0;
+    const void* fn = lf_decode4b_func(ctx->hcfg.method, ctx->hcfg.ef, rm);
+    if (!fn) return LNSFAID_E_INVAL;
+    if (fn != ctx->checked_burst_fn) { /* as kernel_check: the En image must start at LDS offset 0 */
+        hipFuncAttributes at;
+        HIP_TRY(hipFuncGetAttributes(&at, fn));
+        if (at.sharedSizeBytes != 0) {
+            snprintf(g_hip_err, sizeof(g_hip_err), "burst decode kernel has %zu bytes of static LDS: its En image would not start at LDS offset 0",
+                     (size_t)at.sharedSizeBytes);
+            return LNSFAID_E_INTERNAL;
+        }
+        ctx->checked_burst_fn = fn;
+    }
+    LfBurstArgs a;
+    a.code = ctx->d_code; a.cfg = ctx->d_cfg;
+    a.line = d_line; a.payload = d_payload; a.bits = d_bits;
+    a.st_rows = ctx->d_rows;
+    a.stats = d_stats; a.short_ones = d_short_ones;
+    a.desc = ctx->d_burst_desc;
+    a.format = format; a.magnitude = magnitude; a.where = where; a.n_cw = (int32_t)n_codewords;
+    static const bool trace = getenv("LNSFAID_TRACE") != nullptr;
+    HIP_TRY(hipEventRecord(ctx->ev_chain[0], ctx->stream));
+    HIP_TRY(lf_launch_decode4b(ctx->hcfg.method, ctx->hcfg.ef, rm, &a, ctx->lds_bytes, ctx->stream));
+    HIP_TRY(hipEventRecord(ctx->ev_chain[1], ctx->stream));
+    { const int rcw = stream_wait(ctx); if (rcw) return rcw; }
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_chain[0], ctx->ev_chain[1]));
+    ctx->kernel_ms += ms;
+    ctx->kernel_launches += 1;
+    if (trace) fprintf(stderr, "[lnsfaid] burst launch: %.3f ms, %zu codewords\n", ms, n_codewords);
+    return LNSFAID_OK;
+}
+
+extern "C" int lnsfaid_decode_burst_device(lnsfaid_ctx* ctx, const void* d_line, int32_t format, int32_t magnitude, const uint32_t* shortened,
+                                           int32_t where, size_t n_codewords, uint32_t* d_payload, uint32_t* d_bits,
+                                           lnsfaid_line_stats* d_stats, uint32_t* d_short_ones)
+{
+    int rc = line_rules(ctx, format, magnitude, n_codewords);
+    if (rc < 0) return rc;
+    if (where != LNSFAID_SHORTEN_TAIL && where != LNSFAID_SHORTEN_HEAD) return LNSFAID_E_INVAL;
+    if (rc) return LNSFAID_OK;
+    if (!d_line || !d_payload) return LNSFAID_E_INVAL;
+    if (!dword_aligned(d_line) || !dword_aligned(d_payload) || !dword_aligned(d_bits) || !dword_aligned(d_stats) || !dword_aligned(d_short_ones))
+        return LNSFAID_E_INVAL;
+    size_t lu, pw;
+    rc = burst_descriptors(ctx, shortened, where, n_codewords, &lu, &pw);
+    if (rc) return rc;
+    return decode_burst_launch(ctx, d_line, format, magnitude, where, n_codewords, d_payload, d_bits, d_stats, d_short_ones);
+}
+
+/* host buffers of any alignment: one copy each way through the staging buffers of lnsfaid_decode_line */
+extern "C" int lnsfaid_decode_burst(lnsfaid_ctx* ctx, const void* line, int32_t format, int32_t magnitude, const uint32_t* shortened,
+                                    int32_t where, size_t n_codewords, uint32_t* payload, uint32_t* bits, lnsfaid_line_stats* stats,
+                                    uint32_t* short_ones)
+{
+    int rc = line_rules(ctx, format, magnitude, n_codewords);
+    if (rc < 0) return rc;
+    if (where != LNSFAID_SHORTEN_TAIL && where != LNSFAID_SHORTEN_HEAD) return LNSFAID_E_INVAL;
+    if (rc) return LNSFAID_OK;
+    if (!line || !payload) return LNSFAID_E_INVAL;
+    size_t lu, pw;
+    rc = burst_descriptors(ctx, shortened, where, n_codewords, &lu, &pw);
+    if (rc) return rc;
+    rc = ensure_packed_io(ctx);
+    if (rc) return rc;
+    if (!ctx->d_ln_payload) {
+        HIP_TRY(hipMalloc(&ctx->d_ln_payload, ctx->max_groups * LNSFAID_GROUP * (size_t)ctx->k_info / 8));
+        HIP_TRY(hipMalloc(&ctx->d_ln_stats, ctx->max_groups * LNSFAID_GROUP * sizeof(lnsfaid_line_stats)));
+    }
+    if (!ctx->d_burst_ones) HIP_TRY(hipMalloc(&ctx->d_burst_ones, ctx->max_groups * LNSFAID_GROUP * sizeof(uint32_t)));
+    const size_t n_bytes = (size_t)ctx->n_var / 8;
+    HIP_TRY(hipMemcpyAsync(ctx->d_pk_in, line, lu * (format == LNSFAID_LINE_HARD ? 4u : 16u), hipMemcpyHostToDevice, ctx->stream));
+    rc = decode_burst_launch(ctx, ctx->d_pk_in, format, magnitude, where, n_codewords, ctx->d_ln_payload, bits ? ctx->d_pk_out : nullptr,
+                             stats ? ctx->d_ln_stats : nullptr, short_ones ? ctx->d_burst_ones : nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipMemcpyAsync(payload, ctx->d_ln_payload, pw * 4u, hipMemcpyDeviceToHost, ctx->stream));
+    if (bits) HIP_TRY(hipMemcpyAsync(bits, ctx->d_pk_out, n_codewords * n_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    if (stats)
+        HIP_TRY(hipMemcpyAsync(stats, ctx->d_ln_stats, n_codewords * sizeof(lnsfaid_line_stats), hipMemcpyDeviceToHost, ctx->stream));
+    if (short_ones) HIP_TRY(hipMemcpyAsync(short_ones, ctx->d_burst_ones, n_codewords * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+    return stream_wait(ctx);
+}
+
+extern "C" int lnsfaid_encode_burst_device(lnsfaid_ctx* ctx, const uint32_t* d_payload, const uint32_t* shortened, int32_t where,
+                                           size_t n_codewords, uint32_t* d_line, uint32_t* d_bits)
+{
+    int rc = encode_line_rules(ctx, n_codewords);
+    if (rc < 0) return rc;
+    if (where != LNSFAID_SHORTEN_TAIL && where != LNSFAID_SHORTEN_HEAD) return LNSFAID_E_INVAL;
+    if (rc) return LNSFAID_OK;
+    if (!d_payload || !d_line) return LNSFAID_E_INVAL;
+    if (!dword_aligned(d_payload) || !dword_aligned(d_line) || !dword_aligned(d_bits)) return LNSFAID_E_INVAL;
+    rc = ensure_encoder(ctx);
+    if (rc) return rc;
+    size_t lu, pw;
+    rc = burst_descriptors(ctx, shortened, where, n_codewords, &lu, &pw);
+    if (rc) return rc;
+    HIP_TRY(lf_launch_encode_burst(ctx->d_code, ctx->n_check, ctx->d_enc_sup, ctx->d_enc_off, d_payload, ctx->d_burst_desc, where,
+                                   n_codewords, d_line, d_bits, ctx->stream));
+    return stream_wait(ctx);
+}
+
+/* host buffers of any alignment, through the packed staging buffers as lnsfaid_encode_line: payload, and behind it the line */
+extern "C" int lnsfaid_encode_burst(lnsfaid_ctx* ctx, const uint32_t* payload, const uint32_t* shortened, int32_t where, size_t n_codewords,
+                                    uint32_t* line, uint32_t* bits)
+{
+    int rc = encode_line_rules(ctx, n_codewords);
+    if (rc < 0) return rc;
+    if (where != LNSFAID_SHORTEN_TAIL && where != LNSFAID_SHORTEN_HEAD) return LNSFAID_E_INVAL;
+    if (rc) return LNSFAID_OK;
+    if (!payload || !line) return LNSFAID_E_INVAL;
+    rc = ensure_encoder(ctx);
+    if (rc) return rc;
+    size_t lu, pw;
+    rc = burst_descriptors(ctx, shortened, where, n_codewords, &lu, &pw);
+    if (rc) return rc;
+    rc = ensure_packed_io(ctx);
+    if (rc) return rc;
+    const size_t k_bytes = (size_t)ctx->k_info / 8, n_bytes = (size_t)ctx->n_var / 8;
+    uint32_t* d_payload = (uint32_t*)ctx->d_pk_in;
+    uint32_t* d_line = (uint32_t*)(ctx->d_pk_in + ctx->max_groups * LNSFAID_GROUP * k_bytes);
+    HIP_TRY(hipMemcpyAsync(d_payload, payload, pw * 4u, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(lf_launch_encode_burst(ctx->d_code, ctx->n_check, ctx->d_enc_sup, ctx->d_enc_off, d_payload, ctx->d_burst_desc, where,
+                                   n_codewords, d_line, bits ? ctx->d_pk_out : nullptr, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(line, d_line, lu * 4u, hipMemcpyDeviceToHost, ctx->stream));
     if (bits) HIP_TRY(hipMemcpyAsync(bits, ctx->d_pk_out, n_codewords * n_bytes, hipMemcpyDeviceToHost, ctx->stream));
     return stream_wait(ctx);
 }

@@ -577,3 +577,120 @@ int lnsfaid_line_soft_host(const lnsfaid_code* code, const uint32_t* line_in, si
     if (total_flips) *total_flips += total;
     return LNSFAID_OK;
 }
+
+/* ---- burst-format line calls, host forms (include/lnsfaid.h "burst-format line calls") ----
+ * Codeword c of a burst is shortened by S_c bits: the information positions [k0, k0 + S_c) are known zeros and are not on the line.
+ * Everything is byte by byte (S_c is a multiple of 32, so every codeword starts on a byte in both formats), and `shortened` is read
+ * byte by byte too: host pointers of any alignment do. */
+static uint32_t burst_s(const uint32_t* shortened, size_t c) { return shortened ? link_ld32((const uint8_t*)shortened + 4 * c) : 0u; }
+
+/* the code (N, K and L multiples of 32, K <= L) and every S_c: S_c % 32 == 0 and 0 <= S_c <= K - 32 */
+static int burst_rules(const lnsfaid_code* code, const uint32_t* shortened, size_t n_codewords, uint64_t* line_bits, uint64_t* payload_bits)
+{
+    const int rc = line_code_rules(code, LNSFAID_LINE_HARD);
+    if (rc) return rc;
+    if (code->n_var % 32 != 0 || code->puncture_tail > code->n_check) return LNSFAID_E_INVAL;
+    const uint64_t N = (uint64_t)code->n_var, K = N - (uint64_t)code->n_check, L = N - (uint64_t)code->puncture_tail;
+    uint64_t s_sum = 0;
+    for (size_t c = 0; c < n_codewords; ++c) {
+        const uint32_t s = burst_s(shortened, c);
+        if (s % 32u != 0u || (uint64_t)s + 32u > K) return LNSFAID_E_INVAL;
+        s_sum += s;
+    }
+    if (line_bits) *line_bits = (uint64_t)n_codewords * L - s_sum;
+    if (payload_bits) *payload_bits = (uint64_t)n_codewords * K - s_sum;
+    return LNSFAID_OK;
+}
+
+static int burst_where_rules(int32_t where) { return where == LNSFAID_SHORTEN_TAIL || where == LNSFAID_SHORTEN_HEAD ? LNSFAID_OK : LNSFAID_E_INVAL; }
+
+int lnsfaid_burst_words(const lnsfaid_code* code, const uint32_t* shortened, size_t n_codewords, uint64_t* line_bits, uint64_t* payload_bits)
+{
+    uint64_t lb = 0, pb = 0;
+    const int rc = burst_rules(code, shortened, n_codewords, &lb, &pb);
+    if (rc) return rc;
+    if (line_bits) *line_bits = lb;
+    if (payload_bits) *payload_bits = pb;
+    return LNSFAID_OK;
+}
+
+int lnsfaid_burst_to_llr4(const lnsfaid_code* code, const void* line, int32_t format, int32_t magnitude, const uint32_t* shortened,
+                          int32_t where, size_t n_codewords, uint8_t* llr4)
+{
+    int rc = line_code_rules(code, format);
+    if (rc) return rc;
+    if (format == LNSFAID_LINE_HARD && (magnitude < 1 || magnitude > 7)) return LNSFAID_E_INVAL;
+    if (burst_where_rules(where)) return LNSFAID_E_INVAL;
+    rc = burst_rules(code, shortened, n_codewords, NULL, NULL);
+    if (rc) return rc;
+    if (n_codewords == 0) return LNSFAID_OK;
+    if (!line || !llr4) return LNSFAID_E_INVAL;
+    const size_t N = (size_t)code->n_var, K = N - (size_t)code->n_check, L = N - (size_t)code->puncture_tail;
+    const size_t n_groups = (n_codewords + LNSFAID_GROUP - 1) / LNSFAID_GROUP;
+    const uint8_t* in = (const uint8_t*)line;
+    memset(llr4, 0, n_groups * LNSFAID_GROUP * N / 2); /* the punctured tail and the padding codewords: nibble 0 */
+    size_t first = 0; /* the codeword's first position on the line, counted over the whole burst line */
+    for (size_t cw = 0; cw < n_codewords; ++cw) {
+        const size_t S = burst_s(shortened, cw), k0 = where == LNSFAID_SHORTEN_HEAD ? 0 : K - S;
+        for (size_t p = 0; p < L; ++p) {
+            unsigned nib;
+            if (p >= k0 && p < k0 + S) nib = (unsigned)-7 & 15u; /* a known zero: the strongest level a line can carry */
+            else {
+                const size_t q = first + p - (p >= k0 + S ? S : 0);
+                if (format == LNSFAID_LINE_LLR4) nib = (in[q / 2] >> (q % 2 ? 4 : 0)) & 15u;
+                else nib = (unsigned)(((in[q / 8] >> (q % 8)) & 1) ? magnitude : -magnitude) & 15u;
+            }
+            const size_t e = line_group_element(cw, p, N, K);
+            llr4[e / 2] |= (uint8_t)(nib << (e % 2 ? 4 : 0));
+        }
+        first += L - S;
+    }
+    return LNSFAID_OK;
+}
+
+/* The definition of what lnsfaid_encode_burst* return: the payload expanded with zeros in the known range, lnsfaid_encode_line_host,
+ * the known words dropped from the line.  `bits` is the mother codeword as it is.  Chunks of 64 codewords through two heap buffers. */
+int lnsfaid_encode_burst_host(const lnsfaid_code* code, const uint8_t* circ, size_t circ_bytes, const uint32_t* payload,
+                              const uint32_t* shortened, int32_t where, size_t n_codewords, uint32_t* line, uint32_t* bits)
+{
+    /* everything lnsfaid_encode_line_host refuses is refused here before anything is written */
+    int rc = lnsfaid_encode_line_host(code, circ, circ_bytes, NULL, 0, NULL, NULL);
+    if (rc) return rc;
+    if (burst_where_rules(where)) return LNSFAID_E_INVAL;
+    rc = burst_rules(code, shortened, n_codewords, NULL, NULL);
+    if (rc) return rc;
+    if (n_codewords == 0) return LNSFAID_OK;
+    if (!payload || !line) return LNSFAID_E_INVAL;
+    const size_t N = (size_t)code->n_var, K = N - (size_t)code->n_check, L = N - (size_t)code->puncture_tail;
+    const size_t chunk = n_codewords < 64 ? n_codewords : 64;
+    uint8_t* full_pay = (uint8_t*)malloc(chunk * (K / 8));
+    uint8_t* full_line = (uint8_t*)malloc(chunk * (L / 8));
+    if (!full_pay || !full_line) {
+        free(full_pay); free(full_line);
+        return LNSFAID_E_NOMEM;
+    }
+    const uint8_t* in = (const uint8_t*)payload;
+    uint8_t* out = (uint8_t*)line;
+    for (size_t c0 = 0; c0 < n_codewords && rc == LNSFAID_OK; c0 += chunk) {
+        const size_t nc = n_codewords - c0 < chunk ? n_codewords - c0 : chunk;
+        for (size_t i = 0; i < nc; ++i) { /* expand: zeros in [k0, k0 + S) */
+            const size_t S = burst_s(shortened, c0 + i), k0 = where == LNSFAID_SHORTEN_HEAD ? 0 : K - S;
+            uint8_t* u = full_pay + i * (K / 8);
+            memcpy(u, in, k0 / 8);
+            memset(u + k0 / 8, 0, S / 8);
+            memcpy(u + (k0 + S) / 8, in + k0 / 8, (K - S - k0) / 8);
+            in += (K - S) / 8;
+        }
+        rc = lnsfaid_encode_line_host(code, circ, circ_bytes, (const uint32_t*)full_pay, nc, (uint32_t*)full_line,
+                                      bits ? (uint32_t*)((uint8_t*)bits + c0 * (N / 8)) : NULL);
+        for (size_t i = 0; i < nc && rc == LNSFAID_OK; ++i) { /* drop the known words */
+            const size_t S = burst_s(shortened, c0 + i), k0 = where == LNSFAID_SHORTEN_HEAD ? 0 : K - S;
+            const uint8_t* l = full_line + i * (L / 8);
+            memcpy(out, l, k0 / 8);
+            memcpy(out + k0 / 8, l + (k0 + S) / 8, (L - S - k0) / 8);
+            out += (L - S) / 8;
+        }
+    }
+    free(full_pay); free(full_line);
+    return rc;
+}

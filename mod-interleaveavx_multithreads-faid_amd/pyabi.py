@@ -15,6 +15,7 @@ GROUP = 32
 MSG_REGISTERS, MSG_HBM = 1, 2  # lnsfaid_select_message_store
 ZERO_SHIFT_ON, ZERO_SHIFT_OFF, ZERO_SHIFT_LOOP, ZERO_SHIFT_STATIC, ZERO_SHIFT_WINDOWED = 1, 2, 3, 4, 5  # lnsfaid_select_zero_shift
 STOP_GROUP, STOP_CODEWORD = 0, 1  # lnsfaid_set_early_stop
+SHORTEN_TAIL, SHORTEN_HEAD = 0, 1  # lnsfaid_decode_burst / lnsfaid_encode_burst: where the known zeros of a shortened codeword sit
 LINE_HARD, LINE_LLR4 = 0, 1  # lnsfaid_decode_line: one bit / one 4-bit LLR per transmitted code bit
 
 
@@ -99,6 +100,16 @@ SYMBOLS = {
     "lnsfaid_encode_line": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "lnsfaid_encode_line_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "lnsfaid_encode_line_host": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "lnsfaid_decode_burst": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p]),
+    "lnsfaid_decode_burst_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p,
+                                              C.c_void_p, C.c_void_p, C.c_void_p]),
+    "lnsfaid_encode_burst": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "lnsfaid_encode_burst_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p, C.c_void_p]),
+    "lnsfaid_encode_burst_host": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p,
+                                            C.c_void_p]),
+    "lnsfaid_burst_to_llr4": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p]),
+    "lnsfaid_burst_words": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_size_t, C.c_void_p, C.c_void_p]),
     "lnsfaid_line_payload_random_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_size_t, C.c_void_p]),
     "lnsfaid_line_payload_random_host": (C.c_int, [C.POINTER(Code), C.c_uint64, C.c_uint64, C.c_size_t, C.c_void_p]),
     "lnsfaid_line_bsc_threshold": (C.c_int, [C.c_double, C.POINTER(C.c_uint32)]),
@@ -379,6 +390,71 @@ def encode_line_host(code, payload, n_codewords, with_bits=False, lib=None, circ
                                       bits.ctypes.data if with_bits else None)
     if rc != 0:
         raise ValueError("lnsfaid_encode_line_host failed: %d" % rc)
+    return line, bits
+
+
+def _shortened(shortened, n_codewords):
+    """None, or S_c in bits per codeword as a contiguous uint32 array (a host array in every form)"""
+    import numpy as np
+    if shortened is None:
+        return None
+    shortened = np.ascontiguousarray(shortened, dtype=np.uint32)
+    if shortened.size != n_codewords:
+        raise ValueError("shortened has %d entries, not %d" % (shortened.size, n_codewords))
+    return shortened
+
+
+def burst_words(code, shortened, n_codewords, lib=None):
+    """lnsfaid_burst_words: (bits of the burst line, bits of the burst payload) of n_codewords codewords shortened by `shortened`
+    (uint32 [n_codewords] in bits, or None for all zero); ValueError for an entry the rule refuses"""
+    lib = lib or load()
+    shortened = _shortened(shortened, n_codewords)
+    lb, pb = C.c_uint64(0), C.c_uint64(0)
+    rc = lib.lnsfaid_burst_words(C.byref(code), None if shortened is None else shortened.ctypes.data, n_codewords,
+                                 C.cast(C.byref(lb), C.c_void_p), C.cast(C.byref(pb), C.c_void_p))
+    if rc != 0:
+        raise ValueError("lnsfaid_burst_words failed: %d" % rc)
+    return lb.value, pb.value
+
+
+def burst_to_llr4(code, line, fmt, magnitude, shortened, where, n_codewords, lib=None):
+    """lnsfaid_burst_to_llr4: burst line (uint32 words for LINE_HARD, uint8 for LINE_LLR4) -> uint8 llr4 of ceil(n_codewords / 32)
+    groups: what lnsfaid_decode_burst* decodes"""
+    import numpy as np
+    lib = lib or load()
+    shortened = _shortened(shortened, n_codewords)
+    line_bits, _ = burst_words(code, shortened, n_codewords, lib)
+    line = np.ascontiguousarray(line, dtype=np.uint32 if fmt == LINE_HARD else np.uint8)
+    if line.size != (line_bits // 32 if fmt == LINE_HARD else line_bits // 2):
+        raise ValueError("lnsfaid_burst_to_llr4: line has %d elements for %d positions" % (line.size, line_bits))
+    groups = (n_codewords + GROUP - 1) // GROUP
+    out = np.empty(groups * GROUP * code.n_var // 2, dtype=np.uint8)
+    rc = lib.lnsfaid_burst_to_llr4(C.byref(code), line.ctypes.data, fmt, magnitude, None if shortened is None else shortened.ctypes.data,
+                                   where, n_codewords, out.ctypes.data)
+    if rc != 0:
+        raise ValueError("lnsfaid_burst_to_llr4 failed: %d" % rc)
+    return out
+
+
+def encode_burst_host(code, payload, shortened, where, n_codewords, with_bits=False, lib=None, circ=None):
+    """lnsfaid_encode_burst_host: burst payload (flat uint32) -> (burst line, flat uint32 in the LINE_HARD format, the whole mother
+    codewords uint32 [n_codewords, n_var / 32] or None).  circ as encode_line_host"""
+    import numpy as np
+    lib = lib or load()
+    if circ is None:
+        circ = code_parity_inverse(code, lib)
+    shortened = _shortened(shortened, n_codewords)
+    line_bits, payload_bits = burst_words(code, shortened, n_codewords, lib)
+    payload = np.ascontiguousarray(payload, dtype=np.uint32)
+    if payload.size != payload_bits // 32:
+        raise ValueError("lnsfaid_encode_burst_host: payload has %d words, not %d" % (payload.size, payload_bits // 32))
+    line = np.empty(line_bits // 32, dtype=np.uint32)
+    bits = np.empty((n_codewords, code.n_var // 32), dtype=np.uint32) if with_bits else None
+    rc = lib.lnsfaid_encode_burst_host(C.byref(code), circ.ctypes.data, circ.size, payload.ctypes.data,
+                                       None if shortened is None else shortened.ctypes.data, where, n_codewords, line.ctypes.data,
+                                       bits.ctypes.data if with_bits else None)
+    if rc != 0:
+        raise ValueError("lnsfaid_encode_burst_host failed: %d" % rc)
     return line, bits
 
 
@@ -760,6 +836,57 @@ class Decoder:
     def encode_line_device(self, d_payload_ptr, n_codewords, d_line_ptr, d_bits_ptr=None):
         self._check(self.lib.lnsfaid_encode_line_device(self.ctx, d_payload_ptr, n_codewords, d_line_ptr, d_bits_ptr),
                     "lnsfaid_encode_line_device")
+
+    def decode_burst(self, line, fmt, shortened, where, n_codewords, magnitude=4, with_bits=False, with_stats=True, with_ones=True):
+        """lnsfaid_decode_burst: burst line, flat uint32 words (LINE_HARD) or uint8 (LINE_LLR4); shortened uint32 [n_codewords] in
+        bits or None.  Returns (burst payload, flat uint32; packed decisions uint32 [n_codewords, n_var / 32] or None;
+        lnsfaid_line_stats array or None; short_ones uint32 [n_codewords] or None)"""
+        import numpy as np
+        code = self.code50.code
+        shortened = _shortened(shortened, n_codewords)
+        line_bits, payload_bits = burst_words(code, shortened, n_codewords, self.lib)
+        assert line.dtype == (np.uint32 if fmt == LINE_HARD else np.uint8) and line.flags.c_contiguous
+        assert line.size == (line_bits // 32 if fmt == LINE_HARD else line_bits // 2)
+        payload = np.empty(payload_bits // 32, dtype=np.uint32)
+        bits = np.empty((n_codewords, code.n_var // 32), dtype=np.uint32) if with_bits else None
+        stats = np.zeros(n_codewords, dtype=line_stats_dtype()) if with_stats else None
+        ones = np.zeros(n_codewords, dtype=np.uint32) if with_ones else None
+        self._check(self.lib.lnsfaid_decode_burst(self.ctx, line.ctypes.data, fmt, magnitude,
+                                                  None if shortened is None else shortened.ctypes.data, where, n_codewords,
+                                                  payload.ctypes.data, bits.ctypes.data if with_bits else None,
+                                                  stats.ctypes.data if with_stats else None, ones.ctypes.data if with_ones else None),
+                    "lnsfaid_decode_burst")
+        return payload, bits, stats, ones
+
+    def decode_burst_device(self, d_line_ptr, fmt, shortened, where, n_codewords, d_payload_ptr, d_bits_ptr=None, d_stats_ptr=None,
+                            d_short_ones_ptr=None, magnitude=4):
+        """lnsfaid_decode_burst_device: device pointers, but `shortened` is a host array (uint32 [n_codewords], bits) or None"""
+        shortened = _shortened(shortened, n_codewords)
+        self._check(self.lib.lnsfaid_decode_burst_device(self.ctx, d_line_ptr, fmt, magnitude,
+                                                         None if shortened is None else shortened.ctypes.data, where, n_codewords,
+                                                         d_payload_ptr, d_bits_ptr, d_stats_ptr, d_short_ones_ptr),
+                    "lnsfaid_decode_burst_device")
+
+    def encode_burst(self, payload, shortened, where, n_codewords, with_bits=False):
+        """lnsfaid_encode_burst: burst payload (flat uint32, the payload of decode_burst).  Returns (burst line, flat uint32 in the
+        LINE_HARD format, the whole mother codewords uint32 [n_codewords, n_var / 32] or None)"""
+        import numpy as np
+        code = self.code50.code
+        shortened = _shortened(shortened, n_codewords)
+        line_bits, payload_bits = burst_words(code, shortened, n_codewords, self.lib)
+        assert payload.dtype == np.uint32 and payload.size == payload_bits // 32 and payload.flags.c_contiguous
+        line = np.empty(line_bits // 32, dtype=np.uint32)
+        bits = np.empty((n_codewords, code.n_var // 32), dtype=np.uint32) if with_bits else None
+        self._check(self.lib.lnsfaid_encode_burst(self.ctx, payload.ctypes.data, None if shortened is None else shortened.ctypes.data,
+                                                  where, n_codewords, line.ctypes.data, bits.ctypes.data if with_bits else None),
+                    "lnsfaid_encode_burst")
+        return line, bits
+
+    def encode_burst_device(self, d_payload_ptr, shortened, where, n_codewords, d_line_ptr, d_bits_ptr=None):
+        """lnsfaid_encode_burst_device: device pointers, `shortened` a host array or None"""
+        shortened = _shortened(shortened, n_codewords)
+        self._check(self.lib.lnsfaid_encode_burst_device(self.ctx, d_payload_ptr, None if shortened is None else shortened.ctypes.data,
+                                                         where, n_codewords, d_line_ptr, d_bits_ptr), "lnsfaid_encode_burst_device")
 
     def line_payload_random_device(self, key, first_codeword, n_codewords, d_payload_ptr):
         """lnsfaid_line_payload_random_device: the payload of codewords first_codeword .. of stream `key` into a device buffer"""
