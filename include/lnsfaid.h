@@ -497,6 +497,62 @@ int lnsfaid_burst_to_llr4(const lnsfaid_code* code, const void* line, int32_t fo
 int lnsfaid_burst_words(const lnsfaid_code* code, const uint32_t* shortened, size_t n_codewords, uint64_t* line_bits,
                         uint64_t* payload_bits);
 
+/* ---- line-format failure capture ---------------------------------------------------------------------------
+ * The codewords of a line call that fail, as ordered, compact records: what the decoder did with them.  (key, global codeword number)
+ * reproduces payload, codeword and every channel draw on the host (the link's generators are counter-based); the records hold what
+ * cannot be reproduced cheaply - the decisions, the error pattern and the set of unsatisfied checks.  N = n_var, K = n_var - n_check,
+ * L = n_var - puncture_tail, all multiples of 32 as for the line calls.
+ *   line, format  exactly the input of lnsfaid_decode_line*.  line may be NULL: the line section of every record is then zero and
+ *            channel_errors is 0.
+ *   bits     the optional `bits` output of lnsfaid_decode_line*, N / 32 words per codeword; REQUIRED here.  The decisions may come
+ *            from anywhere, as for the FEC status calls.
+ *   sent     the optional `bits` output of lnsfaid_encode_line*: the mother codeword, N / 32 words per codeword.  NULL means "no sent
+ *            word is known" - a receiver's situation - and NOT the all-zero codeword of the counter calls: select must then not
+ *            contain LNSFAID_LINE_CAPTURE_WRONG (LNSFAID_E_INVAL), and the error section and the three sent-derived counts are zero.
+ *            A simulator that sends zeros passes a zeroed buffer.
+ *   select   1 .. 3 (else LNSFAID_E_INVAL): codeword i is a failure when select & flags != 0.  UNCORRECTABLE: the syndrome of bits,
+ *            recomputed here over all N bits (punctured tail included), is non-zero - the number lnsfaid_line_stats::unsatisfied
+ *            gives for decisions of the line decode.  WRONG: wrong_payload > 0.
+ *   order    failures are numbered 0, 1, ... in ascending index.  A call stores failures skip .. skip + capacity - 1; *found is the
+ *            number of failures in the whole call, *stored = min(capacity, max(found - skip, 0)).  capacity 0 counts only.  Every
+ *            output is a pure function of the inputs, and paging with skip concatenates to the one-shot result.
+ *   payload  payload + i * W holds record i, W = lnsfaid_line_capture_words: 32-bit words, four sections back to back -
+ *              line      L / 32 words (HARD) or L / 8 words (LLR4): the codeword's line image, verbatim
+ *              bits      N / 32 words: the decisions
+ *              error     N / 32 words: bits XOR sent
+ *              syndrome  n_check / 32 words: bit b of word w is set when row 32 w + b of pos_vn (the code table's own row order)
+ *                        is unsatisfied
+ *            50G-PON: W = 1 740 (HARD) or 3 360 (LLR4).
+ * Rules: the line link's.  n_codewords 0 is a no-op that sets *found and *stored to 0.  LNSFAID_E_INVAL: a NULL context or code; a
+ * format other than the two; N, K or L not a multiple of 32; more than 32 * max_groups codewords (device form); a NULL bits, found
+ * or stored; NULL records or payload with capacity > 0; a device pointer (line, bits, sent) that is not 4-byte aligned (more
+ * alignment only widens the loads).  A refused call touches no output.  Exactly *stored records and *stored * W payload words are
+ * written.  records, payload, found and stored are host pointers in both forms.
+ * The device form is a pure read of its inputs; it queues on the context's stream, stages through context buffers of
+ * min(capacity, n_codewords) slots (allocated at first use, grown on demand, freed by lnsfaid_destroy) and copies back only what
+ * it stored.  It does not depend on the decoder configuration.  On the GPU only the built-in code's circulant size is served.
+ * The host form needs no context and no GPU, reads pos_vn, deg and deg_rows row by row - so it serves any code the struct
+ * describes - takes pointers of any alignment and has no limit on n_codewords: it is the definition. */
+#define LNSFAID_LINE_CAPTURE_UNCORRECTABLE 1 /* the decisions leave at least one row of H unsatisfied              */
+#define LNSFAID_LINE_CAPTURE_WRONG         2 /* an information bit differs from the sent word (needs sent)         */
+typedef struct lnsfaid_line_failure {
+    uint64_t codeword;       /* first_codeword + index (wraps): with the key of the run it reproduces payload and channel draws */
+    uint32_t index;          /* index in the call                                                                   */
+    uint32_t flags;          /* LNSFAID_LINE_CAPTURE_* bits that hold for this codeword (both are evaluated whatever select is;
+                                WRONG only when sent is given)                                                      */
+    uint32_t unsatisfied;    /* rows of H the decisions leave unsatisfied = popcount of the syndrome section        */
+    uint32_t wrong_payload;  /* positions k < K where bits differ from sent (0 without sent)                        */
+    uint32_t wrong_parity;   /* positions K <= k < N, punctured tail included (0 without sent)                      */
+    uint32_t channel_errors; /* positions k < L where the channel's own decision (line bit; nibble > 0) differs from sent (0 without sent) */
+} lnsfaid_line_failure;      /* 32 bytes */
+int lnsfaid_line_capture_words(const lnsfaid_code* code, int32_t format, uint32_t* words_per_record);
+int lnsfaid_line_capture_device(lnsfaid_ctx* ctx, const void* d_line, int32_t format, const uint32_t* d_bits, const uint32_t* d_sent,
+                                size_t n_codewords, uint64_t first_codeword, int32_t select, size_t skip, size_t capacity,
+                                lnsfaid_line_failure* records, uint32_t* payload, uint64_t* found, uint64_t* stored);
+int lnsfaid_line_capture_host(const lnsfaid_code* code, const void* line, int32_t format, const uint32_t* bits, const uint32_t* sent,
+                              size_t n_codewords, uint64_t first_codeword, int32_t select, size_t skip, size_t capacity,
+                              lnsfaid_line_failure* records, uint32_t* payload, uint64_t* found, uint64_t* stored);
+
 /* ---- front-end on the device (optional, the host generator stays the parity source) ---- */
 
 /*

@@ -92,6 +92,10 @@ extern "C" hipError_t lf_launch_line_count(const uint32_t* d_payload, const uint
                                            uint32_t kw, unsigned long long* d_acc, hipStream_t stream);
 extern "C" hipError_t lf_launch_line_soft(const uint32_t* d_in, uint8_t* d_out, size_t n_cw, uint32_t lw, uint64_t key, uint64_t first,
                                           const uint32_t table[14], uint32_t* d_flips, unsigned long long* d_total, hipStream_t stream);
+extern "C" hipError_t lf_launch_line_capture(const LfDevCode* d_code, int n_var, int puncture_tail, const void* d_line, int format,
+                                             const uint32_t* d_bits, const uint32_t* d_sent, size_t n_cw, uint64_t first, int select,
+                                             uint32_t skip, uint32_t cap, uint4* d_cnt, uint32_t* d_slots, lnsfaid_line_failure* d_records,
+                                             uint32_t* d_payload, unsigned long long* d_meta, hipStream_t stream);
 
 #include <atomic>
 #include <chrono>
@@ -218,6 +222,14 @@ struct lnsfaid_ctx {
     /* line-format link (lnsfaid_line_link.hip), allocated at the first lnsfaid_line_bsc_device / lnsfaid_line_count_errors_device call */
     unsigned long long* d_link_acc = nullptr; /* errors[4], fec[4], vs_sent[4] of the call in flight, then the channel's flipped bits */
     unsigned long long* h_link_acc = nullptr; /* pinned */
+    /* line-format failure capture (lnsfaid_line_capture.hip), allocated at the first lnsfaid_line_capture_device call */
+    uint4* d_lcap_cnt = nullptr;                /* [max_groups * 32] flags, unsatisfied, wrong payload / parity bits per codeword */
+    unsigned long long* d_lcap_meta = nullptr;  /* found, stored */
+    unsigned long long* h_lcap_meta = nullptr;  /* pinned */
+    size_t lcap_slots = 0, lcap_words = 0;      /* what the three buffers below hold: slots, payload words; grown on demand */
+    uint32_t* d_lcap_slots = nullptr;           /* index of every slot's codeword */
+    lnsfaid_line_failure* d_lcap_records = nullptr;
+    uint32_t* d_lcap_payload = nullptr;
     /* encoder (lnsfaid_encoder.hip): support of B^-1's first rows, derived at the first encode / random-frames call */
     int enc_state = 0;                      /* 0: not derived yet, 1: on the device, LNSFAID_E_CODE: parity part singular */
     uint32_t* d_enc_sup = nullptr;          /* entries b * z + c, block row after block row */
@@ -478,6 +490,9 @@ extern "C" void lnsfaid_destroy(lnsfaid_ctx* ctx)
     if (ctx->h_fec_acc) (void)hipHostFree(ctx->h_fec_acc);
     (void)hipFree(ctx->d_link_acc);
     if (ctx->h_link_acc) (void)hipHostFree(ctx->h_link_acc);
+    (void)hipFree(ctx->d_lcap_cnt); (void)hipFree(ctx->d_lcap_meta);
+    if (ctx->h_lcap_meta) (void)hipHostFree(ctx->h_lcap_meta);
+    (void)hipFree(ctx->d_lcap_slots); (void)hipFree(ctx->d_lcap_records); (void)hipFree(ctx->d_lcap_payload);
     if (ctx->h_remaining) (void)hipHostFree(ctx->h_remaining);
     if (ctx->h_counters) (void)hipHostFree(ctx->h_counters);
     if (ctx->ev0) (void)hipEventDestroy(ctx->ev0);
@@ -2710,6 +2725,69 @@ extern "C" int lnsfaid_line_soft_device(lnsfaid_ctx* ctx, const uint32_t* d_line
     rc = stream_wait(ctx);
     if (rc) return rc;
     if (total_flips) *total_flips += ctx->h_link_acc[12];
+    return LNSFAID_OK;
+}
+
+/* ---- line-format failure capture (include/lnsfaid.h "line-format failure capture", DESIGN.md 3.19, lnsfaid_line_capture.hip; the
+ * host form is in lnsfaid_tables.c) ---- */
+/* staging for `slots` records of `words` payload words each; what a smaller call left is kept */
+static int line_capture_buffers(lnsfaid_ctx* ctx, size_t slots, size_t words)
+{
+    /* each on its own: a call after a failed allocation asks again for what is still missing */
+    if (!ctx->d_lcap_cnt) HIP_TRY(hipMalloc(&ctx->d_lcap_cnt, ctx->max_groups * LNSFAID_GROUP * sizeof(uint4)));
+    if (!ctx->d_lcap_meta) HIP_TRY(hipMalloc(&ctx->d_lcap_meta, 2 * sizeof(unsigned long long)));
+    if (!ctx->h_lcap_meta) HIP_TRY(hipHostMalloc((void**)&ctx->h_lcap_meta, 2 * sizeof(unsigned long long), hipHostMallocDefault));
+    if (slots > ctx->lcap_slots || slots * words > ctx->lcap_words) {
+        { const int rcw = stream_wait(ctx); if (rcw) return rcw; } /* nothing queued may still use the old buffers */
+        (void)hipFree(ctx->d_lcap_slots); (void)hipFree(ctx->d_lcap_records); (void)hipFree(ctx->d_lcap_payload);
+        ctx->d_lcap_slots = nullptr; ctx->d_lcap_records = nullptr; ctx->d_lcap_payload = nullptr;
+        ctx->lcap_slots = 0; ctx->lcap_words = 0;
+        HIP_TRY(hipMalloc(&ctx->d_lcap_slots, slots * sizeof(uint32_t))); /* slots > 0 here: capacity 0 counts only and needs none */
+        HIP_TRY(hipMalloc(&ctx->d_lcap_records, slots * sizeof(lnsfaid_line_failure)));
+        HIP_TRY(hipMalloc(&ctx->d_lcap_payload, slots * words * sizeof(uint32_t)));
+        ctx->lcap_slots = slots; ctx->lcap_words = slots * words;
+    }
+    return LNSFAID_OK;
+}
+
+extern "C" int lnsfaid_line_capture_device(lnsfaid_ctx* ctx, const void* d_line, int32_t format, const uint32_t* d_bits, const uint32_t* d_sent,
+                                           size_t n_codewords, uint64_t first_codeword, int32_t select, size_t skip, size_t capacity,
+                                           lnsfaid_line_failure* records, uint32_t* payload, uint64_t* found, uint64_t* stored)
+{
+    int rc = line_link_rules(ctx, n_codewords);
+    if (rc < 0) return rc;
+    if (ctx->n_var % 32 != 0 || (format != LNSFAID_LINE_HARD && format != LNSFAID_LINE_LLR4)) return LNSFAID_E_INVAL;
+    if (select < 1 || select > 3 || (!d_sent && (select & LNSFAID_LINE_CAPTURE_WRONG))) return LNSFAID_E_INVAL;
+    if (rc) { /* n_codewords == 0 */
+        if (found) *found = 0;
+        if (stored) *stored = 0;
+        return LNSFAID_OK;
+    }
+    if (!d_bits || !found || !stored || (capacity > 0 && (!records || !payload))) return LNSFAID_E_INVAL;
+    if (!dword_aligned(d_line) || !dword_aligned(d_bits) || !dword_aligned(d_sent)) return LNSFAID_E_INVAL;
+    const size_t l_bits = (size_t)(ctx->n_var - ctx->hcode.puncture_tail);
+    const size_t words = (format == LNSFAID_LINE_LLR4 ? l_bits / 8 : l_bits / 32) + 2 * (size_t)(ctx->n_var / 32) + (size_t)(ctx->n_check / 32);
+    const size_t slots = capacity < n_codewords ? capacity : n_codewords;
+    HIP_TRY(hipSetDevice(ctx->device));
+    rc = line_capture_buffers(ctx, slots, words);
+    if (rc) return rc;
+    /* no failure has a rank of n_codewords or more: a larger skip stores as little */
+    HIP_TRY(lf_launch_line_capture(ctx->d_code, ctx->n_var, ctx->hcode.puncture_tail, d_line, format, d_bits, d_sent, n_codewords, first_codeword,
+                                   select, (uint32_t)(skip < n_codewords ? skip : n_codewords), (uint32_t)slots, ctx->d_lcap_cnt,
+                                   ctx->d_lcap_slots, ctx->d_lcap_records, ctx->d_lcap_payload, ctx->d_lcap_meta, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->h_lcap_meta, ctx->d_lcap_meta, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    rc = stream_wait(ctx); /* the one wait that tells the host how much to copy */
+    if (rc) return rc;
+    const size_t n_found = (size_t)ctx->h_lcap_meta[0], n_stored = (size_t)ctx->h_lcap_meta[1];
+    if (n_stored > slots) return LNSFAID_E_INTERNAL;
+    if (n_stored) {
+        HIP_TRY(hipMemcpyAsync(records, ctx->d_lcap_records, n_stored * sizeof(lnsfaid_line_failure), hipMemcpyDeviceToHost, ctx->stream));
+        HIP_TRY(hipMemcpyAsync(payload, ctx->d_lcap_payload, n_stored * words * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+        rc = stream_wait(ctx);
+        if (rc) return rc;
+    }
+    *found = n_found;
+    *stored = n_stored;
     return LNSFAID_OK;
 }
 

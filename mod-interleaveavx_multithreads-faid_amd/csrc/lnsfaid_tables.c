@@ -694,3 +694,103 @@ int lnsfaid_encode_burst_host(const lnsfaid_code* code, const uint8_t* circ, siz
     free(full_pay); free(full_line);
     return rc;
 }
+
+/* ---- line-format failure capture, host form (include/lnsfaid.h "line-format failure capture") ----
+ * The definition of what lnsfaid_line_capture_device returns: the syndrome row by row from pos_vn, no quasi-cyclic shortcut.  Bytes
+ * in, bytes out (little-endian words), so host pointers of any alignment do. */
+static int capture_code_rules(const lnsfaid_code* code, int32_t format)
+{
+    const int rc = line_code_rules(code, format);
+    if (rc) return rc;
+    return code->n_var % 32 != 0 ? LNSFAID_E_INVAL : LNSFAID_OK;
+}
+
+static size_t capture_line_words(const lnsfaid_code* code, int32_t format)
+{
+    const size_t L = (size_t)(code->n_var - code->puncture_tail);
+    return format == LNSFAID_LINE_LLR4 ? L / 8 : L / 32;
+}
+
+int lnsfaid_line_capture_words(const lnsfaid_code* code, int32_t format, uint32_t* words_per_record)
+{
+    const int rc = capture_code_rules(code, format);
+    if (rc) return rc;
+    if (!words_per_record) return LNSFAID_E_INVAL;
+    *words_per_record = (uint32_t)(capture_line_words(code, format) + 2 * (size_t)(code->n_var / 32) + (size_t)(code->n_check / 32));
+    return LNSFAID_OK;
+}
+
+int lnsfaid_line_capture_host(const lnsfaid_code* code, const void* line, int32_t format, const uint32_t* bits, const uint32_t* sent,
+                              size_t n_codewords, uint64_t first_codeword, int32_t select, size_t skip, size_t capacity,
+                              lnsfaid_line_failure* records, uint32_t* payload, uint64_t* found, uint64_t* stored)
+{
+    int rc = capture_code_rules(code, format);
+    if (rc) return rc;
+    if (select < 1 || select > 3 || (!sent && (select & LNSFAID_LINE_CAPTURE_WRONG))) return LNSFAID_E_INVAL;
+    if (n_codewords == 0) {
+        if (found) *found = 0;
+        if (stored) *stored = 0;
+        return LNSFAID_OK;
+    }
+    if (!bits || !found || !stored || (capacity > 0 && (!records || !payload))) return LNSFAID_E_INVAL;
+    rc = fec_code_rules(code, 1);
+    if (rc) return rc;
+    const size_t N = (size_t)code->n_var, M = (size_t)code->n_check, K = N - M, L = N - (size_t)code->puncture_tail;
+    const size_t nw = N / 32, mw = M / 32, lw = capture_line_words(code, format), W = lw + 2 * nw + mw;
+    const uint8_t* in = (const uint8_t*)line;
+    const uint8_t* dec = (const uint8_t*)bits;
+    const uint8_t* ref = (const uint8_t*)sent;
+    uint8_t* out = (uint8_t*)payload;
+    uint8_t* bit = (uint8_t*)malloc(N);
+    uint32_t* syn = (uint32_t*)malloc(4 * (mw ? mw : 1));
+    if (!bit || !syn) { free(bit); free(syn); return LNSFAID_E_NOMEM; }
+    uint64_t n_found = 0, n_stored = 0;
+    for (size_t i = 0; i < n_codewords; ++i) {
+        const uint8_t* d = dec + i * (N / 8);
+        const uint8_t* s = ref ? ref + i * (N / 8) : NULL;
+        lnsfaid_line_failure r;
+        memset(&r, 0, sizeof(r));
+        r.codeword = first_codeword + (uint64_t)i;
+        r.index = (uint32_t)i;
+        for (size_t k = 0; k < N; ++k) {
+            bit[k] = (uint8_t)((d[k / 8] >> (k % 8)) & 1);
+            if (s && bit[k] != ((s[k / 8] >> (k % 8)) & 1)) {
+                if (k < K) r.wrong_payload += 1u;
+                else r.wrong_parity += 1u;
+            }
+        }
+        memset(syn, 0, 4 * mw);
+        size_t e = 0, row = 0;
+        for (int dg = 0; dg < code->nb_degres; ++dg)
+            for (int q = 0; q < code->deg_rows[dg]; ++q, ++row) {
+                unsigned parity = 0;
+                for (int j = 0; j < code->deg[dg]; ++j) parity ^= bit[code->pos_vn[e++]];
+                if (parity) { syn[row / 32] |= 1u << (row % 32); r.unsatisfied += 1u; }
+            }
+        r.flags = (r.unsatisfied > 0 ? (uint32_t)LNSFAID_LINE_CAPTURE_UNCORRECTABLE : 0u) |
+                  (r.wrong_payload > 0 ? (uint32_t)LNSFAID_LINE_CAPTURE_WRONG : 0u);
+        if (!(r.flags & (uint32_t)select)) continue;
+        const uint64_t rank = n_found++;
+        if (rank < (uint64_t)skip || rank - (uint64_t)skip >= (uint64_t)capacity) continue;
+        const uint8_t* l = in ? in + i * lw * 4 : NULL;
+        if (l && s)
+            for (size_t k = 0; k < L; ++k) {
+                unsigned ch;
+                if (format == LNSFAID_LINE_LLR4) { const unsigned nib = (l[k / 2] >> (k % 2 ? 4 : 0)) & 15u; ch = nib >= 1u && nib <= 7u; }
+                else ch = (l[k / 8] >> (k % 8)) & 1u;
+                r.channel_errors += ch != ((unsigned)(s[k / 8] >> (k % 8)) & 1u);
+            }
+        uint8_t* p = out + (size_t)n_stored * W * 4;
+        if (l) memcpy(p, l, lw * 4);
+        else memset(p, 0, lw * 4);
+        memcpy(p + lw * 4, d, nw * 4);
+        for (size_t b = 0; b < nw * 4; ++b) p[(lw + nw) * 4 + b] = s ? (uint8_t)(d[b] ^ s[b]) : (uint8_t)0;
+        for (size_t w = 0; w < mw; ++w) link_st32(p + (lw + 2 * nw + w) * 4, syn[w]);
+        memcpy((uint8_t*)records + (size_t)n_stored * sizeof(r), &r, sizeof(r));
+        n_stored += 1;
+    }
+    free(bit); free(syn);
+    *found = n_found;
+    *stored = n_stored;
+    return LNSFAID_OK;
+}

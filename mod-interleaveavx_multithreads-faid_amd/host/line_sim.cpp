@@ -7,7 +7,10 @@
  *   lnsfaid_decode_line_device (LNSFAID_LINE_LLR4) -> lnsfaid_line_count_errors_device
  * on the device buffers of one context (lnsfaid_io_buffers, carved up below): no bit crosses to the host, only the counters do.
  * first_codeword continues across calls and points, so a run is one stream of codewords of the key.  A point stops at --min-errors
- * error frames or after --max-calls calls.  One row per point goes to LineResult.txt (in the working directory) and to the console. */
+ * error frames or after --max-calls calls.  One row per point goes to LineResult.txt (in the working directory) and to the console.
+ * With --capture-failures CAPACITY (include/lnsfaid.h "line-format failure capture") the encode and decode calls also
+ * write their `bits`, and after the counters of every call lnsfaid_line_capture_device pages through the codewords that are
+ * uncorrectable or wrong, CAPACITY records at a time; one text row per failure is appended to --capture-file (LineFailures.txt). */
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -20,7 +23,7 @@
 #include "lnsfaid.h"
 
 static const char* kUsage =
-    "usage: %s --ber P[,P...] [--magnitude 4] | --ebn0 D[,D...] [--scale 9.19238816] --codewords N --max-calls C --min-errors E [--method 2] [--iterations 10] [--key K] [--device D]\n";
+    "usage: %s --ber P[,P...] [--magnitude 4] | --ebn0 D[,D...] [--scale 9.19238816] --codewords N --max-calls C --min-errors E [--method 2] [--iterations 10] [--key K] [--device D] [--capture-failures CAPACITY [--capture-file LineFailures.txt]]\n";
 
 static bool parse_u64(const char* s, uint64_t* v)
 {
@@ -68,12 +71,22 @@ static bool parse_scale(const char* s, double* v)
 
 static size_t align256(size_t x) { return (x + 255u) & ~(size_t)255u; }
 
+/* " ; " and the ascending indices of the set bits of a record section */
+static void print_set_bits(FILE* f, const uint32_t* words, size_t n_words)
+{
+    fputs(" ;", f);
+    for (size_t w = 0; w < n_words; ++w)
+        for (uint32_t v = words[w]; v; v &= v - 1u) fprintf(f, " %zu", 32 * w + (size_t)__builtin_ctz(v));
+}
+
 int main(int argc, char** argv)
 {
     std::vector<double> ber, ebn0;
     double scale = 13.0 / std::sqrt(2.0); /* the QPSK operating scale 13 on a unit-amplitude axis */
     bool have_magnitude = false, have_scale = false;
     uint64_t codewords = 0, max_calls = 0, min_errors = 0, method = 2, iterations = 10, magnitude = 4, key = 1, device = 0;
+    uint64_t capture = 0; /* --capture-failures: records per page, 0 = off */
+    const char* capture_file = nullptr;
     bool have[4] = { false, false, false, false }, ok = true;
     for (int i = 1; i < argc && ok; ++i) {
         const char* a = argv[i];
@@ -90,12 +103,16 @@ int main(int argc, char** argv)
         else if (!strcmp(a, "--magnitude")) have_magnitude = ok = parse_u64(v, &magnitude) && magnitude >= 1 && magnitude <= 7;
         else if (!strcmp(a, "--key")) ok = parse_u64(v, &key);
         else if (!strcmp(a, "--device")) ok = parse_u64(v, &device) && device < 1024;
+        else if (!strcmp(a, "--capture-failures")) ok = parse_u64(v, &capture) && capture > 0 && capture <= 0x7fffffffull;
+        else if (!strcmp(a, "--capture-file")) ok = *(capture_file = v) != '\0';
         else ok = false;
         ++i;
     }
     const bool soft = !ebn0.empty();
     if (soft) have[0] = ber.empty() && !have_magnitude; /* exactly one of --ber and --ebn0; --magnitude belongs to --ber */
     else if (have_scale) ok = false;                    /* and --scale to --ebn0 */
+    if (capture_file && !capture) ok = false;           /* and --capture-file to --capture-failures */
+    if (capture && !capture_file) capture_file = "LineFailures.txt";
     if (!ok || !have[0] || !have[1] || !have[2] || !have[3]) {
         fprintf(stderr, kUsage, argv[0]);
         return 2;
@@ -118,12 +135,15 @@ int main(int argc, char** argv)
         return 1;
     }
     /* each of the two buffers holds 32 * n_var bytes per group; the five streams need (2 K + L) / 8 + 20 bytes per codeword, the
-     * LLR4 line of the soft sweep L / 2 more, behind the hard line */
-    const size_t K = (size_t)(code.n_var - code.n_check), L = (size_t)(code.n_var - code.puncture_tail);
-    const size_t room = groups * LNSFAID_GROUP * (size_t)code.n_var;
+     * LLR4 line of the soft sweep L / 2 more, behind the hard line; with --capture-failures the sent words and the decisions, N / 8
+     * each, come last in either buffer */
+    const size_t K = (size_t)(code.n_var - code.n_check), L = (size_t)(code.n_var - code.puncture_tail), N = (size_t)code.n_var;
+    const size_t room = groups * LNSFAID_GROUP * N;
     const size_t o_line = align256(n * K / 8), o_llr4 = o_line + align256(n * L / 8), o_flips = o_llr4 + (soft ? align256(n * L / 2) : 0),
                  o_stats = align256(n * K / 8);
-    if (o_flips + 4 * n > room || o_stats + sizeof(lnsfaid_line_stats) * n > room) {
+    const size_t o_sent = o_flips + align256(4 * n), o_bits = o_stats + align256(sizeof(lnsfaid_line_stats) * n);
+    if (o_flips + 4 * n > room || o_stats + sizeof(lnsfaid_line_stats) * n > room ||
+        (capture && (o_sent + n * N / 8 > room || o_bits + n * N / 8 > room))) {
         fprintf(stderr, "lnsfaid_line_sim: the context's buffers are too small for this code\n");
         lnsfaid_destroy(ctx);
         return 1;
@@ -134,10 +154,34 @@ int main(int argc, char** argv)
     uint32_t* d_flips = (uint32_t*)(d_a + o_flips);
     uint32_t* d_decoded = (uint32_t*)d_b;
     lnsfaid_line_stats* d_stats = (lnsfaid_line_stats*)(d_b + o_stats);
+    uint32_t* d_sent = capture ? (uint32_t*)(d_a + o_sent) : nullptr;  /* the encode call's bits */
+    uint32_t* d_bits = capture ? (uint32_t*)(d_b + o_bits) : nullptr;  /* the decode call's bits */
+    const int32_t format = soft ? LNSFAID_LINE_LLR4 : LNSFAID_LINE_HARD;
+    const size_t page = capture < n ? (size_t)capture : n;
+    uint32_t W = 0;
+    std::vector<lnsfaid_line_failure> records;
+    std::vector<uint32_t> sections;
+    FILE* ff = nullptr;
+    if (capture) {
+        rc = lnsfaid_line_capture_words(&code, format, &W);
+        if (!rc) {
+            records.resize(page);
+            sections.resize(page * (size_t)W);
+            ff = fopen(capture_file, "w");
+        }
+        if (!ff) {
+            fprintf(stderr, "lnsfaid_line_sim: cannot write %s\n", capture_file);
+            lnsfaid_destroy(ctx);
+            return 1;
+        }
+        fprintf(ff, "# %s codeword index flags unsatisfied wrong_payload wrong_parity channel_errors ; wrong positions ; unsatisfied rows\n",
+                soft ? "ebn0_db" : "p");
+    }
 
     FILE* f = fopen("LineResult.txt", "w");
     if (!f) {
         fprintf(stderr, "lnsfaid_line_sim: cannot write LineResult.txt\n");
+        if (ff) fclose(ff);
         lnsfaid_destroy(ctx);
         return 1;
     }
@@ -167,15 +211,31 @@ int main(int argc, char** argv)
         const auto t0 = std::chrono::steady_clock::now();
         for (uint64_t call = 0; call < max_calls && !rc && errors[1] < min_errors; ++call, first += n) {
             rc = lnsfaid_line_payload_random_device(ctx, key, first, n, d_payload);
-            if (!rc) rc = lnsfaid_encode_line_device(ctx, d_payload, n, d_line, nullptr);
+            if (!rc) rc = lnsfaid_encode_line_device(ctx, d_payload, n, d_line, d_sent);
             if (soft) {
                 if (!rc) rc = lnsfaid_line_soft_device(ctx, d_line, n, key, first, table, d_llr4, d_flips, &flips);
-                if (!rc) rc = lnsfaid_decode_line_device(ctx, d_llr4, LNSFAID_LINE_LLR4, 0, n, d_decoded, nullptr, d_stats);
+                if (!rc) rc = lnsfaid_decode_line_device(ctx, d_llr4, LNSFAID_LINE_LLR4, 0, n, d_decoded, d_bits, d_stats);
             } else {
                 if (!rc) rc = lnsfaid_line_bsc_device(ctx, d_line, n, key, first, threshold, d_line, d_flips, &flips);
-                if (!rc) rc = lnsfaid_decode_line_device(ctx, d_line, LNSFAID_LINE_HARD, (int32_t)magnitude, n, d_decoded, nullptr, d_stats);
+                if (!rc) rc = lnsfaid_decode_line_device(ctx, d_line, LNSFAID_LINE_HARD, (int32_t)magnitude, n, d_decoded, d_bits, d_stats);
             }
             if (!rc) rc = lnsfaid_line_count_errors_device(ctx, d_decoded, d_payload, d_stats, n, errors, fec, vs);
+            uint64_t found = 0, stored = 0;
+            for (size_t skip = 0; capture && !rc && (skip == 0 || skip < found); skip += page) {
+                rc = lnsfaid_line_capture_device(ctx, soft ? (const void*)d_llr4 : (const void*)d_line, format, d_bits, d_sent, n, first,
+                                                 LNSFAID_LINE_CAPTURE_UNCORRECTABLE | LNSFAID_LINE_CAPTURE_WRONG, skip, page, records.data(),
+                                                 sections.data(), &found, &stored);
+                for (size_t s = 0; !rc && s < stored; ++s) {
+                    const lnsfaid_line_failure& r = records[s];
+                    const uint32_t* error = sections.data() + s * (size_t)W + (W - 2 * N / 32 - (N - K) / 32) + N / 32;
+                    fprintf(ff, "%.9g %llu %u %u %u %u %u %u", x, (unsigned long long)r.codeword, r.index, r.flags, r.unsatisfied, r.wrong_payload,
+                            r.wrong_parity, r.channel_errors);
+                    print_set_bits(ff, error, N / 32);
+                    print_set_bits(ff, error + N / 32, (N - K) / 32);
+                    fputc('\n', ff);
+                }
+            }
+            if (ff) fflush(ff);
         }
         if (rc) break;
         const double seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
@@ -196,6 +256,7 @@ int main(int argc, char** argv)
         fflush(stdout);
     }
     fclose(f);
+    if (ff) fclose(ff);
     if (rc) fprintf(stderr, "lnsfaid_line_sim: a call failed: %s (%s)\n", lnsfaid_strerror(rc), lnsfaid_last_hip_error());
     lnsfaid_destroy(ctx);
     return rc ? 1 : 0;

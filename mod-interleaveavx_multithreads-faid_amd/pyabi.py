@@ -17,6 +17,7 @@ ZERO_SHIFT_ON, ZERO_SHIFT_OFF, ZERO_SHIFT_LOOP, ZERO_SHIFT_STATIC, ZERO_SHIFT_WI
 STOP_GROUP, STOP_CODEWORD = 0, 1  # lnsfaid_set_early_stop
 SHORTEN_TAIL, SHORTEN_HEAD = 0, 1  # lnsfaid_decode_burst / lnsfaid_encode_burst: where the known zeros of a shortened codeword sit
 LINE_HARD, LINE_LLR4 = 0, 1  # lnsfaid_decode_line: one bit / one 4-bit LLR per transmitted code bit
+LINE_CAPTURE_UNCORRECTABLE, LINE_CAPTURE_WRONG = 1, 2  # lnsfaid_line_capture_*: bits of select and of a record's flags
 
 
 class Code(C.Structure):
@@ -126,6 +127,11 @@ SYMBOLS = {
                                            C.POINTER(C.c_uint64)]),
     "lnsfaid_line_soft_host": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(C.c_uint64)]),
+    "lnsfaid_line_capture_words": (C.c_int, [C.POINTER(Code), C.c_int32, C.POINTER(C.c_uint32)]),
+    "lnsfaid_line_capture_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_int32,
+                                              C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "lnsfaid_line_capture_host": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_int32,
+                                            C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "lnsfaid_frontend_device": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_size_t, C.c_int32,
                                           C.c_float, C.c_float, C.c_void_p, C.c_void_p]),
     "lnsfaid_frontend_device_states": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint64), C.c_size_t, C.c_int32,
@@ -561,6 +567,73 @@ def line_count_errors_host(code, payload, sent, stats, n_codewords, errors=True,
     return tuple(list(x) if x is not None else None for x in (e, f, v))
 
 
+def line_failure_dtype():
+    """numpy view of lnsfaid_line_failure"""
+    import numpy as np
+    return np.dtype([("codeword", np.uint64), ("index", np.uint32), ("flags", np.uint32), ("unsatisfied", np.uint32),
+                     ("wrong_payload", np.uint32), ("wrong_parity", np.uint32), ("channel_errors", np.uint32)])
+
+
+def line_capture_words(code, fmt, lib=None):
+    """lnsfaid_line_capture_words: 32-bit words of one record's payload for a Code struct and a line format"""
+    lib = lib or load()
+    w = C.c_uint32()
+    rc = lib.lnsfaid_line_capture_words(C.byref(code), fmt, C.byref(w))
+    if rc != 0:
+        raise ValueError("lnsfaid_line_capture_words failed: %d" % rc)
+    return w.value
+
+
+def line_capture_split(code, fmt, payload):
+    """payload uint32 [stored, W] -> its four sections {"line", "bits", "error", "syndrome"}, each uint32 [stored, words]"""
+    L, N, M = code.n_var - code.puncture_tail, code.n_var, code.n_check
+    lw = L // 8 if fmt == LINE_LLR4 else L // 32
+    cuts = [0, lw, lw + N // 32, lw + 2 * (N // 32), lw + 2 * (N // 32) + M // 32]
+    return {name: payload[:, cuts[i]:cuts[i + 1]] for i, name in enumerate(("line", "bits", "error", "syndrome"))}
+
+
+def line_capture_positions(words):
+    """one record's `error` or `syndrome` section (uint32 words) -> the ascending list of its set bits: wrong positions / unsatisfied
+    rows of pos_vn"""
+    import numpy as np
+    bits = np.unpackbits(np.ascontiguousarray(words, dtype="<u4").view(np.uint8), bitorder="little")
+    return np.flatnonzero(bits).tolist()
+
+
+def _line_capture(fn, what, code, fmt, n_codewords, capacity, lib):
+    """runs fn(records pointer, payload pointer, found, stored) on buffers of min(capacity, n_codewords) slots"""
+    import numpy as np
+    W = line_capture_words(code, fmt, lib)
+    slots = min(capacity, n_codewords)
+    records = np.zeros(slots, dtype=line_failure_dtype())
+    payload = np.zeros((slots, W), dtype=np.uint32)
+    found, stored = C.c_uint64(), C.c_uint64()
+    rc = fn(records.ctypes.data if slots else None, payload.ctypes.data if slots else None, C.byref(found), C.byref(stored))
+    if rc != 0:
+        raise ValueError("%s failed: %d" % (what, rc))
+    return found.value, records[:stored.value], line_capture_split(code, fmt, payload[:stored.value])
+
+
+def line_capture_host(code, line, fmt, bits, sent, n_codewords, first_codeword=0, select=1, skip=0, capacity=256, lib=None):
+    """lnsfaid_line_capture_host: line as decode_line takes it or None, bits / sent uint32 [n_codewords, N / 32] (sent None: no sent word
+    is known).  Returns (found, records as a structured numpy array, {"line", "bits", "error", "syndrome"} uint32 [stored, words])"""
+    import numpy as np
+    lib = lib or load()
+    per, dtype, _ = line_sizes(code, fmt)
+    arrs = []
+    for name, a, dt, size in (("line", line, dtype, n_codewords * per), ("bits", bits, np.uint32, n_codewords * (code.n_var // 32)),
+                              ("sent", sent, np.uint32, n_codewords * (code.n_var // 32))):
+        if a is not None:
+            a = np.ascontiguousarray(a, dtype=dt)
+            if a.size != size:
+                raise ValueError("lnsfaid_line_capture_host: %s has %d elements, not %d" % (name, a.size, size))
+        arrs.append(a)
+    ptr = [a.ctypes.data if a is not None else None for a in arrs]
+    return _line_capture(lambda r, p, f, s: lib.lnsfaid_line_capture_host(C.byref(code), ptr[0], fmt, ptr[1], ptr[2], n_codewords, first_codeword,
+                                                                          select, skip, capacity, r, p, f, s),
+                         "lnsfaid_line_capture_host", code, fmt, n_codewords, capacity, lib)
+
+
 def _demap_host(fn_name, packed, n_var, n_check, interleave, rx, n_groups, mod_type, scale, lib):
     import numpy as np
     lib = lib or load()
@@ -964,6 +1037,16 @@ class Decoder:
             return _capture(lambda r, p, f, s, o: self.lib.lnsfaid_capture_errors_device(self.ctx, d_fix_ptr, d_dec_ptr, d_sent_ptr, n_groups,
                                                                                          skip, capacity, r, p, f, s, o),
                             "lnsfaid_capture_errors_device", self.code50.N, n_groups, capacity, counters)
+        except ValueError as e:
+            raise RuntimeError("%s (hip: %s)" % (e, self.lib.lnsfaid_last_hip_error().decode()))
+
+    def line_capture_device(self, d_line_ptr, fmt, d_bits_ptr, d_sent_ptr, n_codewords, first_codeword=0, select=1, skip=0, capacity=256):
+        """lnsfaid_line_capture_device: device pointers (d_line_ptr / d_sent_ptr may be None).  The result as line_capture_host"""
+        try:
+            return _line_capture(lambda r, p, f, s: self.lib.lnsfaid_line_capture_device(self.ctx, d_line_ptr, fmt, d_bits_ptr, d_sent_ptr,
+                                                                                         n_codewords, first_codeword, select, skip, capacity,
+                                                                                         r, p, f, s),
+                                 "lnsfaid_line_capture_device", self.code50.code, fmt, n_codewords, capacity, self.lib)
         except ValueError as e:
             raise RuntimeError("%s (hip: %s)" % (e, self.lib.lnsfaid_last_hip_error().decode()))
 
