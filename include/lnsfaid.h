@@ -553,6 +553,53 @@ int lnsfaid_line_capture_host(const lnsfaid_code* code, const void* line, int32_
                               size_t n_codewords, uint64_t first_codeword, int32_t select, size_t skip, size_t capacity,
                               lnsfaid_line_failure* records, uint32_t* payload, uint64_t* found, uint64_t* stored);
 
+/* ---- line-format error-propagation channel ------------------------------------------------------------------
+ * A hard channel with memory in the line's own format, LNSFAID_LINE_HARD in and out: a wrong decision raises the error probability of
+ * the next one, as behind a decision-feedback equaliser, so the same average BER arrives in runs.  Everything downstream takes its
+ * output unchanged: lnsfaid_decode_line*, lnsfaid_line_count_errors* and lnsfaid_line_capture*, whose channel_errors already counts
+ * line against sent.  L, K, mix64, cwkey and draw are those of the link section above; the host form is the definition.
+ *
+ * Draws: the BSC's domain, d = 2, on purpose.  Position 2 q of codeword C uses u = the low 32 bits of draw(key, C, 2, q), position
+ * 2 q + 1 the high 32 bits, for q < L / 2; one more draw, which the BSC never makes, gives the start: s = the low 32 bits of
+ * draw(key, C, 2, L / 2).
+ * t: three thresholds { t_idle, t_after, t_start }, a host pointer in both forms (as `table` is for lnsfaid_line_soft_device).  The rule
+ * is t_idle <= t_after (positive correlation only).
+ * Chain, one per codeword - nothing carries from a codeword to the next:
+ *   e[-1] = (s < t_start),   e[k] = (u[k] < (e[k - 1] ? t_after : t_idle)) for k = 0 .. L - 1,   position k is inverted iff e[k] = 1.
+ * With g[k] = (u[k] < t_idle) and p[k] = (u[k] < t_after) this is e[k] = g[k] | (p[k] & e[k - 1]), and because g implies p it is the
+ * carry chain of an adder: generate, propagate, kill.
+ *   line_out == line_in is allowed (in place); any other overlap of the two is undefined.
+ *   flips        optional uint32_t [n_codewords] (the _device form: a device pointer): the positions inverted per codeword.
+ *   total_flips  optional host uint64_t, ADDED to: the positions inverted in the call.
+ *   runs         optional uint32_t [n_codewords] (the _device form: a device pointer): per codeword, the maximal runs of consecutive
+ *                inverted positions inside the codeword.  A run that starts at position 0 because e[-1] = 1 is one run.
+ *   total_runs   optional host uint64_t, ADDED to: the runs of the call.  total_flips / total_runs is the measured mean run length.
+ * Consequences, all exact:
+ *   1. With t_idle == t_after the output, flips and total_flips are byte for byte those of lnsfaid_line_bsc_* with that threshold,
+ *      whatever t_start is: a sweep with and without memory on one key uses common random numbers.
+ *   2. With { 0, 0xFFFFFFFF, t_start } a codeword is either returned untouched (s >= t_start) or inverted from position 0 on
+ *      (s < t_start), entirely unless some u[k] equals 0xFFFFFFFF.
+ *   3. { 0, 0, anything } copies the line.
+ * lnsfaid_line_markov_thresholds (host only): the thresholds of a stationary chain with marginal error probability p = ber and
+ * a = propagation = P(e[k] = 1 | e[k - 1] = 1), hence a mean run length of 1 / (1 - a):  t_after = floor(a * 2^32),
+ * t_start = floor(p * 2^32), t_idle = floor(2^32 * p * (1 - a) / (1 - p)), evaluated in double in that order (and never above t_after);
+ * when a == p all three are floor(p * 2^32), the BSC of consequence 1.  With q = p (1 - a) / (1 - p) the stationary probability
+ * q / (1 - a + q) is p, so P(e[k] = 1) = p at every position and ber stays the x-axis of a sweep.  It requires 0 <= p <= a < 1, which
+ * is exactly t_idle <= t_after; anything else, NaN, or a NULL t is LNSFAID_E_INVAL with t not written.
+ * Rules: the BSC's.  n_codewords 0 is a no-op (every buffer may be NULL).  LNSFAID_E_INVAL: a NULL context or code; L or K not a
+ * multiple of 32; more than 32 * max_groups codewords (device form); a NULL line_in, line_out or t; t_idle > t_after; a device pointer,
+ * optional ones included, that is not 4-byte aligned.  A refused call writes nothing and adds nothing.  The device form queues on the
+ * context's stream and returns when the totals are complete; its two accumulators live with the link's, allocated at first use and
+ * freed by lnsfaid_destroy.  It does not depend on the decoder configuration.  The host form needs no context and no GPU, takes
+ * pointers of any alignment and has no limit on n_codewords. */
+int lnsfaid_line_markov_thresholds(double ber, double propagation, uint32_t t[3]);
+int lnsfaid_line_markov_device(lnsfaid_ctx* ctx, const uint32_t* d_line_in, size_t n_codewords, uint64_t key, uint64_t first_codeword,
+                               const uint32_t t[3], uint32_t* d_line_out, uint32_t* d_flips, uint32_t* d_runs,
+                               uint64_t* total_flips, uint64_t* total_runs);
+int lnsfaid_line_markov_host(const lnsfaid_code* code, const uint32_t* line_in, size_t n_codewords, uint64_t key, uint64_t first_codeword,
+                             const uint32_t t[3], uint32_t* line_out, uint32_t* flips, uint32_t* runs,
+                             uint64_t* total_flips, uint64_t* total_runs);
+
 /* ---- front-end on the device (optional, the host generator stays the parity source) ---- */
 
 /*

@@ -92,6 +92,9 @@ extern "C" hipError_t lf_launch_line_count(const uint32_t* d_payload, const uint
                                            uint32_t kw, unsigned long long* d_acc, hipStream_t stream);
 extern "C" hipError_t lf_launch_line_soft(const uint32_t* d_in, uint8_t* d_out, size_t n_cw, uint32_t lw, uint64_t key, uint64_t first,
                                           const uint32_t table[14], uint32_t* d_flips, unsigned long long* d_total, hipStream_t stream);
+extern "C" hipError_t lf_launch_line_markov(const uint32_t* d_in, uint32_t* d_out, size_t n_cw, uint32_t lw, uint64_t key, uint64_t first,
+                                            const uint32_t t[3], uint32_t* d_flips, uint32_t* d_runs, unsigned long long* d_totals,
+                                            hipStream_t stream);
 extern "C" hipError_t lf_launch_line_capture(const LfDevCode* d_code, int n_var, int puncture_tail, const void* d_line, int format,
                                              const uint32_t* d_bits, const uint32_t* d_sent, size_t n_cw, uint64_t first, int select,
                                              uint32_t skip, uint32_t cap, uint4* d_cnt, uint32_t* d_slots, lnsfaid_line_failure* d_records,
@@ -220,7 +223,7 @@ struct lnsfaid_ctx {
     unsigned long long* d_fec_acc = nullptr; /* out[4] then vs_sent[4] of the call in flight */
     unsigned long long* h_fec_acc = nullptr; /* pinned */
     /* line-format link (lnsfaid_line_link.hip), allocated at the first lnsfaid_line_bsc_device / lnsfaid_line_count_errors_device call */
-    unsigned long long* d_link_acc = nullptr; /* errors[4], fec[4], vs_sent[4] of the call in flight, then the channel's flipped bits */
+    unsigned long long* d_link_acc = nullptr; /* errors[4], fec[4], vs_sent[4] of the call in flight, then the channel's flipped bits and runs */
     unsigned long long* h_link_acc = nullptr; /* pinned */
     /* line-format failure capture (lnsfaid_line_capture.hip), allocated at the first lnsfaid_line_capture_device call */
     uint4* d_lcap_cnt = nullptr;                /* [max_groups * 32] flags, unsatisfied, wrong payload / parity bits per codeword */
@@ -2626,7 +2629,7 @@ extern "C" int lnsfaid_encode_burst(lnsfaid_ctx* ctx, const uint32_t* payload, c
 }
 
 /* ---- line-format link (include/lnsfaid.h "line-format link", DESIGN.md 3.16, lnsfaid_line_link.hip; host forms in lnsfaid_tables.c) -- */
-#define LF_LINK_ACC 13 /* twelve counters and the flipped bits */
+#define LF_LINK_ACC 14 /* twelve counters, the flipped bits and the runs of the error-propagation channel */
 /* everything that can be refused without looking at the buffers; 1: nothing to do.  Nothing of the decoder configuration. */
 static int line_link_rules(const lnsfaid_ctx* ctx, size_t n_codewords)
 {
@@ -2725,6 +2728,32 @@ extern "C" int lnsfaid_line_soft_device(lnsfaid_ctx* ctx, const uint32_t* d_line
     rc = stream_wait(ctx);
     if (rc) return rc;
     if (total_flips) *total_flips += ctx->h_link_acc[12];
+    return LNSFAID_OK;
+}
+
+/* ---- line-format error-propagation channel (include/lnsfaid.h "line-format error-propagation channel", DESIGN.md 3.20,
+ * lnsfaid_line_markov.hip; the host form is in lnsfaid_tables.c) ---- */
+extern "C" int lnsfaid_line_markov_device(lnsfaid_ctx* ctx, const uint32_t* d_line_in, size_t n_codewords, uint64_t key, uint64_t first_codeword,
+                                          const uint32_t t[3], uint32_t* d_line_out, uint32_t* d_flips, uint32_t* d_runs,
+                                          uint64_t* total_flips, uint64_t* total_runs)
+{
+    int rc = line_link_rules(ctx, n_codewords);
+    if (rc) return rc < 0 ? rc : LNSFAID_OK;
+    if (!d_line_in || !d_line_out || !t || t[0] > t[1]) return LNSFAID_E_INVAL;
+    if (!dword_aligned(d_line_in) || !dword_aligned(d_line_out) || !dword_aligned(d_flips) || !dword_aligned(d_runs)) return LNSFAID_E_INVAL;
+    HIP_TRY(hipSetDevice(ctx->device));
+    rc = ensure_link_acc(ctx);
+    if (rc) return rc;
+    unsigned long long* d_totals = ctx->d_link_acc + 12; /* [0] flips, [1] runs */
+    HIP_TRY(hipMemsetAsync(d_totals, 0, 2 * sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(lf_launch_line_markov(d_line_in, d_line_out, n_codewords, (uint32_t)(ctx->n_var - ctx->hcode.puncture_tail) / 32u, key, first_codeword,
+                                  t, d_flips, d_runs, d_totals, ctx->stream));
+    if (total_flips || total_runs)
+        HIP_TRY(hipMemcpyAsync(ctx->h_link_acc + 12, d_totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    rc = stream_wait(ctx);
+    if (rc) return rc;
+    if (total_flips) *total_flips += ctx->h_link_acc[12];
+    if (total_runs) *total_runs += ctx->h_link_acc[13];
     return LNSFAID_OK;
 }
 

@@ -578,6 +578,65 @@ int lnsfaid_line_soft_host(const lnsfaid_code* code, const uint32_t* line_in, si
     return LNSFAID_OK;
 }
 
+/* ---- line-format error-propagation channel, host form and threshold helper (include/lnsfaid.h "line-format error-propagation
+ * channel") ----
+ * The definition of what lnsfaid_line_markov_device returns: the BSC's draws, walked position by position with the previous decision
+ * choosing the threshold.  Words and thresholds are read and written byte by byte: host pointers of any alignment do. */
+int lnsfaid_line_markov_thresholds(double ber, double propagation, uint32_t t[3])
+{
+    const double p = ber, a = propagation;
+    if (!t || !(p >= 0.0 && p <= a && a < 1.0)) return LNSFAID_E_INVAL; /* NaN fails the comparisons */
+    const uint32_t t_after = (uint32_t)(a * 4294967296.0), t_start = (uint32_t)(p * 4294967296.0); /* exact products, truncated: the floor */
+    uint32_t t_idle = t_start; /* a == p: the BSC */
+    if (a != p) {
+        t_idle = (uint32_t)floor(4294967296.0 * p * (1.0 - a) / (1.0 - p)); /* below a * 2^32 < 2^32 up to rounding */
+        if (t_idle > t_after) t_idle = t_after; /* a rounding of the quotient must not break the rule of the channel */
+    }
+    link_st32((uint8_t*)t, t_idle); link_st32((uint8_t*)t + 4, t_after); link_st32((uint8_t*)t + 8, t_start);
+    return LNSFAID_OK;
+}
+
+int lnsfaid_line_markov_host(const lnsfaid_code* code, const uint32_t* line_in, size_t n_codewords, uint64_t key, uint64_t first_codeword,
+                             const uint32_t t[3], uint32_t* line_out, uint32_t* flips, uint32_t* runs, uint64_t* total_flips,
+                             uint64_t* total_runs)
+{
+    const int rc = line_code_rules(code, LNSFAID_LINE_HARD);
+    if (rc) return rc;
+    if (n_codewords == 0) return LNSFAID_OK;
+    if (!line_in || !line_out || !t) return LNSFAID_E_INVAL;
+    const uint32_t t_idle = link_ld32((const uint8_t*)t), t_after = link_ld32((const uint8_t*)t + 4), t_start = link_ld32((const uint8_t*)t + 8);
+    if (t_idle > t_after) return LNSFAID_E_INVAL;
+    const size_t lw = (size_t)(code->n_var - code->puncture_tail) / 32;
+    const uint8_t* in = (const uint8_t*)line_in;
+    uint8_t* out = (uint8_t*)line_out;
+    uint64_t total = 0, total_r = 0;
+    for (size_t i = 0; i < n_codewords; ++i) {
+        const uint64_t ck = link_cwkey(key, first_codeword + (uint64_t)i, 2u);
+        uint32_t e = (uint32_t)link_draw(ck, (uint64_t)(16 * lw)) < t_start; /* the draw after the BSC's last: e of position -1 */
+        uint32_t before = 0, n = 0, r = 0;                                    /* before: e of the position before, 0 in front of the codeword */
+        for (size_t w = 0; w < lw; ++w) {
+            uint32_t mask = 0;
+            for (uint32_t k = 0; k < 32u; ++k) { /* position 32 w + k: the low half of draw q = 16 w + k / 2 for even k, the high half for odd k */
+                const uint64_t h = link_draw(ck, (uint64_t)(16 * w + k / 2u));
+                const uint32_t u = (k & 1u) ? (uint32_t)(h >> 32) : (uint32_t)h;
+                e = u < (e ? t_after : t_idle);
+                mask |= e << k;
+                n += e;
+                r += e & ~before;
+                before = e;
+            }
+            link_st32(out + 4 * (i * lw + w), link_ld32(in + 4 * (i * lw + w)) ^ mask);
+        }
+        if (flips) link_st32((uint8_t*)flips + 4 * i, n);
+        if (runs) link_st32((uint8_t*)runs + 4 * i, r);
+        total += n;
+        total_r += r;
+    }
+    if (total_flips) *total_flips += total;
+    if (total_runs) *total_runs += total_r;
+    return LNSFAID_OK;
+}
+
 /* ---- burst-format line calls, host forms (include/lnsfaid.h "burst-format line calls") ----
  * Codeword c of a burst is shortened by S_c bits: the information positions [k0, k0 + S_c) are known zeros and are not on the line.
  * Everything is byte by byte (S_c is a multiple of 32, so every codeword starts on a byte in both formats), and `shortened` is read

@@ -5,6 +5,8 @@
  * or, with --ebn0 in place of --ber, the soft-decision sweep (include/lnsfaid.h "line-format soft channel"): per Eb/N0
  *   ... -> lnsfaid_encode_line_device -> lnsfaid_line_soft_device (table of lnsfaid_line_awgn_table) ->
  *   lnsfaid_decode_line_device (LNSFAID_LINE_LLR4) -> lnsfaid_line_count_errors_device
+ * or, with --ber and --propagation A, the hard sweep through the channel with memory (include/lnsfaid.h "line-format error-propagation
+ * channel"): lnsfaid_line_markov_device with lnsfaid_line_markov_thresholds(p, max(A, p)) in place of the BSC call,
  * on the device buffers of one context (lnsfaid_io_buffers, carved up below): no bit crosses to the host, only the counters do.
  * first_codeword continues across calls and points, so a run is one stream of codewords of the key.  A point stops at --min-errors
  * error frames or after --max-calls calls.  One row per point goes to LineResult.txt (in the working directory) and to the console.
@@ -23,7 +25,7 @@
 #include "lnsfaid.h"
 
 static const char* kUsage =
-    "usage: %s --ber P[,P...] [--magnitude 4] | --ebn0 D[,D...] [--scale 9.19238816] --codewords N --max-calls C --min-errors E [--method 2] [--iterations 10] [--key K] [--device D] [--capture-failures CAPACITY [--capture-file LineFailures.txt]]\n";
+    "usage: %s --ber P[,P...] [--magnitude 4] [--propagation A] | --ebn0 D[,D...] [--scale 9.19238816] --codewords N --max-calls C --min-errors E [--method 2] [--iterations 10] [--key K] [--device D] [--capture-failures CAPACITY [--capture-file LineFailures.txt]]\n";
 
 static bool parse_u64(const char* s, uint64_t* v)
 {
@@ -69,6 +71,13 @@ static bool parse_scale(const char* s, double* v)
     return end != s && *end == '\0' && std::isfinite(*v) && *v > 0.0;
 }
 
+static bool parse_propagation(const char* s, double* v)
+{
+    char* end = nullptr;
+    *v = strtod(s, &end);
+    return end != s && *end == '\0' && *v >= 0.0 && *v < 1.0; /* NaN fails the comparisons */
+}
+
 static size_t align256(size_t x) { return (x + 255u) & ~(size_t)255u; }
 
 /* " ; " and the ascending indices of the set bits of a record section */
@@ -83,7 +92,8 @@ int main(int argc, char** argv)
 {
     std::vector<double> ber, ebn0;
     double scale = 13.0 / std::sqrt(2.0); /* the QPSK operating scale 13 on a unit-amplitude axis */
-    bool have_magnitude = false, have_scale = false;
+    double propagation = 0.0;
+    bool have_magnitude = false, have_scale = false, markov = false;
     uint64_t codewords = 0, max_calls = 0, min_errors = 0, method = 2, iterations = 10, magnitude = 4, key = 1, device = 0;
     uint64_t capture = 0; /* --capture-failures: records per page, 0 = off */
     const char* capture_file = nullptr;
@@ -95,6 +105,7 @@ int main(int argc, char** argv)
         else if (!strcmp(a, "--ber")) have[0] = ok = parse_ber(v, &ber);
         else if (!strcmp(a, "--ebn0")) ok = parse_ebn0(v, &ebn0);
         else if (!strcmp(a, "--scale")) have_scale = ok = parse_scale(v, &scale);
+        else if (!strcmp(a, "--propagation")) markov = ok = parse_propagation(v, &propagation);
         else if (!strcmp(a, "--codewords")) have[1] = ok = parse_u64(v, &codewords) && codewords > 0 && codewords <= 0x7fffffffull;
         else if (!strcmp(a, "--max-calls")) have[2] = ok = parse_u64(v, &max_calls) && max_calls > 0;
         else if (!strcmp(a, "--min-errors")) have[3] = ok = parse_u64(v, &min_errors);
@@ -109,7 +120,7 @@ int main(int argc, char** argv)
         ++i;
     }
     const bool soft = !ebn0.empty();
-    if (soft) have[0] = ber.empty() && !have_magnitude; /* exactly one of --ber and --ebn0; --magnitude belongs to --ber */
+    if (soft) have[0] = ber.empty() && !have_magnitude && !markov; /* exactly one of --ber and --ebn0; --magnitude and --propagation belong to --ber */
     else if (have_scale) ok = false;                    /* and --scale to --ebn0 */
     if (capture_file && !capture) ok = false;           /* and --capture-file to --capture-failures */
     if (capture && !capture_file) capture_file = "LineFailures.txt";
@@ -136,13 +147,14 @@ int main(int argc, char** argv)
     }
     /* each of the two buffers holds 32 * n_var bytes per group; the five streams need (2 K + L) / 8 + 20 bytes per codeword, the
      * LLR4 line of the soft sweep L / 2 more, behind the hard line; with --capture-failures the sent words and the decisions, N / 8
-     * each, come last in either buffer */
+     * each, come last in either buffer; with --propagation the runs per codeword lie behind the flips */
     const size_t K = (size_t)(code.n_var - code.n_check), L = (size_t)(code.n_var - code.puncture_tail), N = (size_t)code.n_var;
     const size_t room = groups * LNSFAID_GROUP * N;
     const size_t o_line = align256(n * K / 8), o_llr4 = o_line + align256(n * L / 8), o_flips = o_llr4 + (soft ? align256(n * L / 2) : 0),
                  o_stats = align256(n * K / 8);
-    const size_t o_sent = o_flips + align256(4 * n), o_bits = o_stats + align256(sizeof(lnsfaid_line_stats) * n);
-    if (o_flips + 4 * n > room || o_stats + sizeof(lnsfaid_line_stats) * n > room ||
+    const size_t o_runs = o_flips + align256(4 * n);
+    const size_t o_sent = o_runs + (markov ? align256(4 * n) : 0), o_bits = o_stats + align256(sizeof(lnsfaid_line_stats) * n);
+    if (o_flips + 4 * n > room || (markov && o_runs + 4 * n > room) || o_stats + sizeof(lnsfaid_line_stats) * n > room ||
         (capture && (o_sent + n * N / 8 > room || o_bits + n * N / 8 > room))) {
         fprintf(stderr, "lnsfaid_line_sim: the context's buffers are too small for this code\n");
         lnsfaid_destroy(ctx);
@@ -152,6 +164,7 @@ int main(int argc, char** argv)
     uint32_t* d_line = (uint32_t*)(d_a + o_line);
     uint8_t* d_llr4 = (uint8_t*)(d_a + o_llr4);
     uint32_t* d_flips = (uint32_t*)(d_a + o_flips);
+    uint32_t* d_runs = markov ? (uint32_t*)(d_a + o_runs) : nullptr;
     uint32_t* d_decoded = (uint32_t*)d_b;
     lnsfaid_line_stats* d_stats = (lnsfaid_line_stats*)(d_b + o_stats);
     uint32_t* d_sent = capture ? (uint32_t*)(d_a + o_sent) : nullptr;  /* the encode call's bits */
@@ -191,6 +204,10 @@ int main(int argc, char** argv)
     const char* soft_head = "# ebn0_db table7 codewords flipped_bits ber_in TestFrame ErrorFrame ErrorBits LT3ErrBitFrame FER ber_out "
                             "TotalCodewords UncorrectableCodewords CorrectedCodewords CorrectedBits "
                             "vsTestFrame vsErrorFrame UndetectedErrorFrame FalseAlarmFrame seconds sigma scale\n";
+    const char* markov_head = "# p threshold codewords flipped_bits ber_in TestFrame ErrorFrame ErrorBits LT3ErrBitFrame FER ber_out "
+                              "TotalCodewords UncorrectableCodewords CorrectedCodewords CorrectedBits "
+                              "vsTestFrame vsErrorFrame UndetectedErrorFrame FalseAlarmFrame seconds propagation t_idle t_after runs mean_run\n";
+    if (markov) head = markov_head;
     if (soft) {
         head = soft_head;
         fprintf(f, "# lnsfaid_line_sim: soft, DecodeMethod %llu, %llu iterations, scale %.9g, key %llu, %zu codewords per call\n%s",
@@ -202,12 +219,14 @@ int main(int argc, char** argv)
     printf("%s", head);
     uint64_t first = 0;
     for (const double x : soft ? ebn0 : ber) { /* x: Eb/N0 in dB, or the BSC's p */
-        uint32_t threshold = 0, table[14];
+        uint32_t threshold = 0, table[14], mt[3] = { 0, 0, 0 };
         /* Eb/N0 of the information bit on a unit-amplitude axis: sigma^2 = 1 / (2 R Eb/N0), R = K / L the rate on the line */
         const double sigma = soft ? 1.0 / std::sqrt(2.0 * ((double)K / (double)L) * std::pow(10.0, x / 10.0)) : 0.0;
         if (soft) rc = lnsfaid_line_awgn_table(sigma, scale, table);
         else lnsfaid_line_bsc_threshold(x, &threshold); /* checked with the arguments */
-        uint64_t errors[4] = { 0, 0, 0, 0 }, fec[4] = { 0, 0, 0, 0 }, vs[4] = { 0, 0, 0, 0 }, flips = 0;
+        const double a = propagation > x ? propagation : x; /* positive correlation only: below p the channel is the BSC */
+        if (markov) rc = lnsfaid_line_markov_thresholds(x, a, mt); /* mt[2], the threshold of the marginal BER, is `threshold` */
+        uint64_t errors[4] = { 0, 0, 0, 0 }, fec[4] = { 0, 0, 0, 0 }, vs[4] = { 0, 0, 0, 0 }, flips = 0, runs = 0;
         const auto t0 = std::chrono::steady_clock::now();
         for (uint64_t call = 0; call < max_calls && !rc && errors[1] < min_errors; ++call, first += n) {
             rc = lnsfaid_line_payload_random_device(ctx, key, first, n, d_payload);
@@ -216,7 +235,8 @@ int main(int argc, char** argv)
                 if (!rc) rc = lnsfaid_line_soft_device(ctx, d_line, n, key, first, table, d_llr4, d_flips, &flips);
                 if (!rc) rc = lnsfaid_decode_line_device(ctx, d_llr4, LNSFAID_LINE_LLR4, 0, n, d_decoded, d_bits, d_stats);
             } else {
-                if (!rc) rc = lnsfaid_line_bsc_device(ctx, d_line, n, key, first, threshold, d_line, d_flips, &flips);
+                if (!rc && markov) rc = lnsfaid_line_markov_device(ctx, d_line, n, key, first, mt, d_line, d_flips, d_runs, &flips, &runs);
+                else if (!rc) rc = lnsfaid_line_bsc_device(ctx, d_line, n, key, first, threshold, d_line, d_flips, &flips);
                 if (!rc) rc = lnsfaid_decode_line_device(ctx, d_line, LNSFAID_LINE_HARD, (int32_t)magnitude, n, d_decoded, d_bits, d_stats);
             }
             if (!rc) rc = lnsfaid_line_count_errors_device(ctx, d_decoded, d_payload, d_stats, n, errors, fec, vs);
@@ -249,6 +269,9 @@ int main(int argc, char** argv)
                            (unsigned long long)fec[0], (unsigned long long)fec[1], (unsigned long long)fec[2], (unsigned long long)fec[3],
                            (unsigned long long)vs[0], (unsigned long long)vs[1], (unsigned long long)vs[2], (unsigned long long)vs[3], seconds);
         if (soft) len += snprintf(row + len, sizeof(row) - (size_t)len, " %.9g %.9g", sigma, scale);
+        if (markov)
+            len += snprintf(row + len, sizeof(row) - (size_t)len, " %.9g %u %u %llu %.6f", a, mt[0], mt[1], (unsigned long long)runs,
+                            runs ? (double)flips / (double)runs : 0.0);
         snprintf(row + len, sizeof(row) - (size_t)len, "\n");
         fputs(row, f);
         fflush(f);

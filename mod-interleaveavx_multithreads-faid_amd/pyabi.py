@@ -127,6 +127,11 @@ SYMBOLS = {
                                            C.POINTER(C.c_uint64)]),
     "lnsfaid_line_soft_host": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(C.c_uint64)]),
+    "lnsfaid_line_markov_thresholds": (C.c_int, [C.c_double, C.c_double, C.c_void_p]),
+    "lnsfaid_line_markov_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "lnsfaid_line_markov_host": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                           C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "lnsfaid_line_capture_words": (C.c_int, [C.POINTER(Code), C.c_int32, C.POINTER(C.c_uint32)]),
     "lnsfaid_line_capture_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_int32,
                                               C.c_size_t, C.c_size_t, C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
@@ -545,6 +550,49 @@ def line_soft_host(code, line, n_codewords, key, first_codeword, table, total=0,
     if rc != 0:
         raise ValueError("lnsfaid_line_soft_host failed: %d" % rc)
     return out, flips, t.value
+
+
+def _markov_t(t):
+    """{ t_idle, t_after, t_start } as a contiguous uint32 array (the library checks their order)"""
+    import numpy as np
+    t = np.ascontiguousarray(t, dtype=np.uint32)
+    if t.size != 3:
+        raise ValueError("an error-propagation channel has 3 thresholds, not %d" % t.size)
+    return t
+
+
+def line_markov_thresholds(ber, propagation, lib=None):
+    """lnsfaid_line_markov_thresholds: uint32 [3] { t_idle, t_after, t_start } of the stationary chain with marginal error
+    probability `ber` and P(error | error before) = `propagation`; ValueError unless 0 <= ber <= propagation < 1"""
+    import numpy as np
+    lib = lib or load()
+    t = np.zeros(3, dtype=np.uint32)
+    rc = lib.lnsfaid_line_markov_thresholds(float(ber), float(propagation), t.ctypes.data)
+    if rc != 0:
+        raise ValueError("lnsfaid_line_markov_thresholds(%r, %r) failed: %d" % (ber, propagation, rc))
+    return t
+
+
+def line_markov_host(code, line, n_codewords, key, first_codeword, t, total=0, total_runs=0, lib=None):
+    """lnsfaid_line_markov_host: line uint32 [n_codewords, L / 32] (LINE_HARD) through the error-propagation channel of stream `key`
+    and thresholds `t`.  Returns (line out, flips uint32 [n_codewords], runs uint32 [n_codewords], total + the positions inverted,
+    total_runs + the runs of the call)"""
+    import numpy as np
+    lib = lib or load()
+    per = (code.n_var - code.puncture_tail) // 32
+    line = np.ascontiguousarray(line, dtype=np.uint32)
+    if line.size != n_codewords * per:
+        raise ValueError("lnsfaid_line_markov_host: line has %d words, not %d" % (line.size, n_codewords * per))
+    t = _markov_t(t)
+    out = np.empty_like(line)
+    flips = np.zeros(n_codewords, dtype=np.uint32)
+    runs = np.zeros(n_codewords, dtype=np.uint32)
+    tf, tr = C.c_uint64(total), C.c_uint64(total_runs)
+    rc = lib.lnsfaid_line_markov_host(C.byref(code), line.ctypes.data, n_codewords, key, first_codeword, t.ctypes.data, out.ctypes.data,
+                                      flips.ctypes.data, runs.ctypes.data, C.byref(tf), C.byref(tr))
+    if rc != 0:
+        raise ValueError("lnsfaid_line_markov_host failed: %d" % rc)
+    return out, flips, runs, tf.value, tr.value
 
 
 def line_count_errors_host(code, payload, sent, stats, n_codewords, errors=True, fec=None, vs_sent=None, lib=None):
@@ -982,6 +1030,18 @@ class Decoder:
         self._check(self.lib.lnsfaid_line_soft_device(self.ctx, d_line_in_ptr, n_codewords, key, first_codeword, table.ctypes.data,
                                                       d_llr4_out_ptr, d_flips_ptr, C.byref(t)), "lnsfaid_line_soft_device")
         return t.value
+
+    def line_markov_device(self, d_line_in_ptr, n_codewords, key, first_codeword, t, d_line_out_ptr, d_flips_ptr=None, d_runs_ptr=None,
+                           total=0, total_runs=0):
+        """lnsfaid_line_markov_device: LINE_HARD words through the error-propagation channel of stream `key` and thresholds `t`
+        ({ t_idle, t_after, t_start }, host side; d_line_out_ptr may equal d_line_in_ptr).  Returns (total + the positions inverted,
+        total_runs + the runs of the call)"""
+        t = _markov_t(t)
+        tf, tr = C.c_uint64(total), C.c_uint64(total_runs)
+        self._check(self.lib.lnsfaid_line_markov_device(self.ctx, d_line_in_ptr, n_codewords, key, first_codeword, t.ctypes.data,
+                                                        d_line_out_ptr, d_flips_ptr, d_runs_ptr, C.byref(tf), C.byref(tr)),
+                    "lnsfaid_line_markov_device")
+        return tf.value, tr.value
 
     def line_count_errors_device(self, d_payload_ptr, d_sent_ptr, d_stats_ptr, n_codewords, errors=True, fec=None, vs_sent=None):
         """lnsfaid_line_count_errors_device: device pointers (d_sent_ptr None: all-zero payload; d_stats_ptr the lnsfaid_line_stats of
