@@ -50,6 +50,19 @@ __device__ __forceinline__ bool dirty4w(int lane)
 #else
 #define LF4W_FRESH SW_FORM_FRESH
 #endif
+/* How both forms are written: constants of full-rate instructions in registers instead of SGPRs (SW_FORM_VK), the single
+ * left shifts as multiplies by a register (SW_FORM_MUL).  -DLF4W_KEEP_SGPR / -DLF4W_KEEP_SHIFTS take one part out each, as above. */
+#ifdef LF4W_KEEP_SGPR
+#define LF4W_VK 0
+#else
+#define LF4W_VK SW_FORM_VK
+#endif
+#ifdef LF4W_KEEP_SHIFTS
+#define LF4W_MUL 0
+#else
+#define LF4W_MUL SW_FORM_MUL
+#endif
+#define LF4W_CLASS (LF4W_VK | LF4W_MUL)
 
 /* layer BR of the iteration: layer4s of lnsfaid_kernel4s.hip without the rows' syndrome bits, on the step of the iteration's FORM */
 template <int METHOD, int FORM, int BR>
@@ -61,11 +74,14 @@ __device__ __forceinline__ void layer4w(const uint32_t (*zsb)[32], SwRegs& R, co
      * address and rotate amounts) is computed in each of them, not kept alive - spilled - from one to the other */
     asm volatile("; lf4w layer %1" : "+v"(lane) : "n"(BR));
     uint32_t tabn = 0u;
-    if (BR + 1 < SW50_LAYERS) tabn = zsb[BR + 1][lane & 31]; /* next layer's edge table, a layer ahead of its use */
+    /* next layer's edge table, a layer ahead of its use (SW_FORM_MUL: `lane` is 4 * lane, the table's byte offset in its bits 2 .. 6) */
+    if (BR + 1 < SW50_LAYERS) tabn = (FORM & SW_FORM_MUL) ? *(const uint32_t*)((const char*)zsb[BR + 1] + (lane & 0x7c)) : zsb[BR + 1][lane & 31];
     Tab tab;
     tab.sbv = tabv;
     const SwRow zero = { { 0u, 0u, 0u }, 0u, { 0u, 0u } };
-    const SwRow cur = (FORM & SW_FORM_FRESH) ? zero : regs_get(R, BR); /* (iteration 1 starts from regs_clear: the same values) */
+    SwRow cur = (FORM & SW_FORM_FRESH) ? zero : regs_get(R, BR); /* (iteration 1 starts from regs_clear: the same values) */
+    /* the record's unpacking belongs to THIS layer: without a fixed point the compiler starts it inside the layer before */
+    if (!(FORM & SW_FORM_FRESH)) asm volatile("" : "+v"(cur.cw));
     SwRow st = sw_layer_step<METHOD, Tab::DEG, false, 1, 0, 0, SW_PAIRS_ALL, FORM>(lds, tab, p, K, (uint32_t)lane, Tab::DEG, cur,
                                                                                   (FORM & SW_FORM_FRESH) ? true : fresh, 0u, false);
     /* The record is complete HERE (layer4s: without a fixed point the packing of the sign words sinks to the record's next use) */
@@ -114,6 +130,8 @@ __device__ __forceinline__ void main_step4w(CCode c, CCfg f, const LfDevCode* gc
 #pragma unroll
         for (int w = 0; w < 4; ++w) K.tm[w] = sw_vconst(tm[w], (uint32_t)it);
     }
+    if (LF4W_MUL) K.c100 = sw_vconst(0x100u, (uint32_t)it); /* the factor of sw_shl8_mul */
+    const int lane_arg = LF4W_MUL ? lane << 2 : lane; /* SW_FORM_MUL takes 4 * lane: shifted here once, not in every layer */
     const SwLds lds = SwLds();
     /* the arg-min tables of all layers behind ONE base register, the layer in the loads' offset field (main_step4s) */
     uint32_t z = 0u;
@@ -123,11 +141,11 @@ __device__ __forceinline__ void main_step4w(CCode c, CCfg f, const LfDevCode* gc
     __builtin_amdgcn_sched_barrier(0);
     if (first) { /* (regs_clear, or a codeword parked in front of iteration 1: every message is still 0) */
         asm volatile("; lf4w first begin");
-        layers4w<METHOD, LF4W_BASE | LF4W_FRESH>(zsb, R, lds, p, K, lane, true, tabv);
+        layers4w<METHOD, LF4W_BASE | LF4W_FRESH | LF4W_CLASS>(zsb, R, lds, p, K, lane_arg, true, tabv);
         asm volatile("; lf4w first end");
     } else {
         asm volatile("; lf4w middle begin");
-        layers4w<METHOD, LF4W_BASE>(zsb, R, lds, p, K, lane, false, tabv);
+        layers4w<METHOD, LF4W_BASE | LF4W_CLASS>(zsb, R, lds, p, K, lane_arg, false, tabv);
         asm volatile("; lf4w middle end");
     }
 }

@@ -150,6 +150,7 @@ struct SwK {
     uint32_t cm27;    /* -0x27272727: the last constant of sw_update2, as an addend of v_add3_u32 */
     uint32_t tm[4];   /* SW_FORM_NOWIN only, set by its caller once per iteration: thermometer code -> magnitude (sw_therm2msg_tables of
                        * the row's one table: lut_* for the FAID decoders, oms_*[0] for the min-sum ones) */
+    uint32_t c100;    /* SW_FORM_MUL only: the factor of the left shifts by 8 (sw_shl8_mul) */
 };
 SW_FN SwK sw_consts(uint32_t dep = 0u)
 {
@@ -166,6 +167,7 @@ SW_FN SwK sw_consts(uint32_t dep = 0u)
     k.c55 = sw_vconst(0x55555555u, dep); k.c33 = sw_vconst(0x33333333u, dep); k.c0f = sw_vconst(0x0f0f0f0fu, dep);
     k.cm27 = sw_vconst(0u - 0x27272727u, dep);
     for (int w = 0; w < 4; ++w) k.tm[w] = 0u;
+    k.c100 = 0x100u; /* (a plain value: the one caller that reads it on the device moves it to a register itself, like tm[]) */
     return k;
 }
 
@@ -201,6 +203,21 @@ SW_FN void sw_mask7x2(uint32_t a, uint32_t b, uint32_t sel_sign, uint32_t* ma, u
     *ma = sw_mask7_lo(a, sh, sel_sign);
     *mb = sw_mask7_hi(b, sh, sel_sign);
 }
+
+/* ---- left shifts by a constant outside the slow issue class (SW_FORM_MUL) ----
+ * v_mul_u32_u24: the low 32 bits of s0[23:0] * s1[23:0].  With the factor 1 << n (n <= 23) in a register that is (x & 0xffffff) << n:
+ * x << n wherever bits 24 .. 31 of x are dead - always for n >= 8, where the shift drops them anyway, and only such shifts are
+ * written this way.  The factor must sit in a VGPR the compiler cannot look into (sw_vconst), or it makes the shift of it
+ * again; inside the layer step's instruction mix the multiply by a register issues like a full-rate instruction, which neither
+ * v_lshlrev_b32 nor the multiply by a literal does (profiles/r23_class_moves/ubench_issue_classes.txt). */
+SW_FN uint32_t sw_mul_u24(uint32_t x, uint32_t k) { return (x & 0xffffffu) * (k & 0xffffffu); } /* the compiler's own v_mul_u32_u24 */
+/* x << 8, every x; c100: 0x100 in a register */
+SW_FN uint32_t sw_shl8_mul(uint32_t x, uint32_t c100) { return sw_mul_u24(x, c100); }
+/* sw_mask7 on that shift */
+SW_FN uint32_t sw_mask7_mul(uint32_t x, uint32_t sel_sign, uint32_t c100) { return sw_perm(x, sw_shl8_mul(x, c100), sel_sign); }
+/* sw_mask7(x << 1) for bytes x <= 0x7f - bit 6 of every byte as a byte mask - without the shift by one: adding 0x40 carries bit 6
+ * into bit 7 and nothing out of the byte (0x7f + 0x40 = 0xbf), and the expander looks at bit 7 only */
+SW_FN uint32_t sw_mask6_mul(uint32_t x, uint32_t sel_sign, uint32_t c100) { return sw_mask7_mul(x + 0x40404040u, sel_sign, c100); }
 
 /* per-byte population count of the low seven bits (thermometer code -> number) */
 SW_FN uint32_t sw_popcount7(uint32_t x)
@@ -245,6 +262,14 @@ SW_FN uint32_t sw_therm2msg(uint32_t x, const uint32_t tm[4])
     const uint32_t b = sw_perm(tm[3], tm[2], (x >> 4) & 0x07070707u);
     return a ^ b;
 }
+/* the same with the low-nibble mask from a register (SW_FORM_VK): the compiler merges that AND into the last AND of the minimum search,
+ * a v_bitop3_b32, which takes no literal - the mask would become an SGPR operand */
+SW_FN uint32_t sw_therm2msg_vk(uint32_t x, const uint32_t tm[4], uint32_t c0f)
+{
+    const uint32_t a = sw_perm(tm[1], tm[0], x & c0f);
+    const uint32_t b = sw_perm(tm[3], tm[2], (x >> 4) & 0x07070707u);
+    return a ^ b;
+}
 /* 0xff in every byte that is zero; bytes must be <= 0x7f */
 SW_FN uint32_t sw_zero_mask(uint32_t x, uint32_t sel_sign) { return ~sw_mask7(x + 0x7f7f7f7fu, sel_sign); }
 /* sw_zero_mask of x and of y on one shift (sw_mask7x2) */
@@ -271,6 +296,13 @@ SW_FN uint32_t sw_opaque(uint32_t x)
     asm("" : "+v"(x));
 #endif
     return x;
+}
+/* sw_gather4 as three v_perm_b32 (SW_FORM_MUL): knowing every byte's range the compiler takes the three v_lshl_or_b32 apart, shifts g2
+ * and g3 into place one by one and merges with a v_or3_b32 - four instructions of the slow class; the packer is three, with no shift */
+SW_FN uint32_t sw_gather4_perm(uint32_t g0, uint32_t g1, uint32_t g2, uint32_t g3)
+{
+    const uint32_t lo = sw_perm(g1, g0, 0x0c0c0400u), hi = sw_perm(g3, g2, 0x0c0c0400u); /* byte 0 of either source, zeros above */
+    return sw_perm(hi, lo, 0x05040100u);
 }
 /* LDS byte address of the variable node that row k of a lane meets through a circulant, from
  * x = 4 (lane + shift) + (k << 8) in the low half (below 0x10000, a multiple of 4) and the block column << 24:
@@ -541,6 +573,16 @@ SW_FN uint32_t sw_update2(uint32_t tb, uint32_t ms, const SwUpd2& u, uint32_t se
     return sw_upd2_en(mout, sw_upd2_limit<MINSUM>(ms, d, u, c80), zb, d, cm27);
 }
 
+/* sw_update2 with its mask on sw_mask7_mul (SW_FORM_MUL) */
+template <bool MINSUM>
+SW_FN uint32_t sw_update2_mul(uint32_t tb, uint32_t ms, const SwUpd2& u, uint32_t sel_sign, uint32_t c80, uint32_t cm27, uint32_t c100)
+{
+    const uint32_t d = sw_upd2_d(ms, u);
+    const uint32_t zb = sw_upd2_zb(tb, d, u);
+    const uint32_t mout = sw_mask7_mul(sw_upd2_out<MINSUM>(zb, d, u), sel_sign, c100);
+    return sw_upd2_en(mout, sw_upd2_limit<MINSUM>(ms, d, u, c80), zb, d, cm27);
+}
+
 /* ---- minimum search over thermometer codes: running minimum t1, second minimum t2 (with multiplicity) and the five index
  * accumulators ta[] (see "binary index" in sw_layer_step) ---- */
 /* one edge (index j) at a time */
@@ -659,14 +701,26 @@ struct SwTabStatic {
  *                  looked at, and the row's magnitudes come straight from the thermometer codes through K.tm (sw_therm2msg) instead of
  *                  sw_therm2num and a look-up in one of two tables.  Not for DecodeMethod 0, whose levels are the magnitudes.
  *   SW_FORM_FRESH  the first iteration: `cur` is all zero (not looked at) and `fresh` is true, so there is no old patch, the old message
- *                  on every edge is +0 (the edges' sign bit, selector and table look-up are constants) and so is the arg-min edge's. */
+ *                  on every edge is +0 (the edges' sign bit, selector and table look-up are constants) and so is the arg-min edge's.
+ * Two more bits say how the step is WRITTEN, not what it knows: its results are those of the form without them.  They move
+ * instructions from the slow issue class to the full rate:
+ *   SW_FORM_VK     constants that the compiler would put into SGPRs as operands of full-rate instructions (an SGPR source makes such an
+ *                  instruction a slow one) come from SwK's registers: the low-nibble mask of sw_therm2msg, the record's valid mask, and the
+ *                  index decode in a form that reads 0x80 alone; the addends 0x78 and -0x27 of v_add3_u32, slow wherever they sit, give
+ *                  their registers up.  Per-degree FAID / min-sum instances of degree > 16.
+ *   SW_FORM_MUL    the single left shifts by 8 of the mask expander go through sw_shl8_mul (K.c100 must be a register), the shift by one
+ *                  in front of the old patch's mask becomes an addition (sw_mask6_mul), the byte gathers pack with v_perm_b32
+ *                  (sw_gather4_perm), and `lane` is passed as 4 * lane: the caller shifts once per iteration, not the step per layer. */
 #define SW_FORM_NOWIN 1
 #define SW_FORM_FRESH 2
+#define SW_FORM_VK 4
+#define SW_FORM_MUL 8
 template <int METHOD, int DEG, bool ERA = false, int WAVES = 1, int WAVE = 0, int ZG = 0, int PAIRS = 0, int FORM = 0, class Tab, class Xch = SwNoXch>
 SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, const SwK& K, uint32_t lane, int deg, SwRow cur, bool fresh,
                           uint32_t rowpar, bool lme, uint32_t era_edges = 0u, uint32_t era_plane = 0u, const Xch& xch = Xch())
 {
     constexpr bool NOWIN = (FORM & SW_FORM_NOWIN) != 0, FRESH = (FORM & SW_FORM_FRESH) != 0;
+    constexpr bool VK = (FORM & SW_FORM_VK) != 0, MULF = (FORM & SW_FORM_MUL) != 0;
     static_assert(FORM == 0 || (WAVES == 1 && !ERA), "iteration forms: one-wave, non-erasing instances");
     static_assert(!NOWIN || METHOD != 0, "the normalised min-sum rows read no table after the search");
     static_assert(WAVES == 1 || !ERA, "the erasing variant is built for one wave per codeword only");
@@ -688,8 +742,15 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
     constexpr bool NSTREE = WAVES == 1 && SW_ILP == 4; /* pass 2 packs its sign words four edges at a time (sw_sign_quad) */
     constexpr bool EPAIRS = WAVES == 1 && DEG > 0 && SW_ILP % 2 == 0; /* edges j0 + 2 i, j0 + 2 i + 1 of a group may share a shift */
     constexpr bool EPAIRS1 = EPAIRS && (PAIRS & SW_PAIRS_PASS1), EPAIRS2 = EPAIRS && (PAIRS & SW_PAIRS_PASS2), RPAIRS = (PAIRS & SW_PAIRS_ROW) != 0;
-    const uint32_t c01 = K.cbit[0], c80 = K.cbit[7], c7f = K.c7f, c78 = K.c78, c0642 = K.c0642, cfc = K.cfc, sel_sign = K.sel_sign;
-    const uint32_t tid4 = lane << 2;
+    static_assert(!VK || DEG > 16, "the index decode of SW_FORM_VK: per-degree instances with edges in 16 .. 23");
+    /* SW_FORM_VK: 0x78 and -0x27 are addends of v_add3_u32 only (FAID rows), which is of the slow class wherever its operands sit:
+     * literals, i.e. SGPRs, and their two registers go to the constants that full-rate instructions read */
+    const uint32_t c78 = (VK && !MINSUM) ? 0x78787878u : K.c78;
+    const uint32_t c01 = K.cbit[0], c80 = K.cbit[7], c7f = K.c7f, c0642 = K.c0642, cfc = K.cfc, sel_sign = K.sel_sign;
+    const uint32_t tid4 = MULF ? lane : lane << 2; /* (SW_FORM_MUL: the caller's 4 * lane) */
+    /* a single mask, and a single left shift by 8, in the form of the step */
+#define SW_MASK7(x) (MULF ? sw_mask7_mul((x), sel_sign, K.c100) : sw_mask7((x), sel_sign))
+#define SW_SHL8(x) (MULF ? sw_shl8_mul((x), K.c100) : (x) << 8)
     /* the layer's circulants first (scalar loads share the LDS counter: in flight together with LDS reads they force full drains) */
     uint32_t s4j[NJ], cbj[NJ];
 #pragma unroll
@@ -713,11 +774,11 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
         const uint32_t a0 = cur.pa[0] & 0xffffu, a1 = cur.pa[0] >> 16, a2 = cur.pa[1] & 0xffffu, a3 = cur.pa[1] >> 16;
         SW_SCHED_FENCE(); /* the four reads back to back: one LDS round trip, not one per read */
         const uint32_t g0 = lds.rd8(a0), g1 = lds.rd8(a1), g2 = lds.rd8(a2), g3 = lds.rd8(a3);
-        const uint32_t mneg = sw_mask7(cur.cw << 1, sel_sign); /* bit 6: the arg-min message is negative */
+        const uint32_t mneg = MULF ? sw_mask6_mul(cur.cw, sel_sign, K.c100) : sw_mask7(cur.cw << 1, sel_sign); /* bit 6: the arg-min message is negative */
         /* En - L(c1) = (En - sigma (c1 - c2)) - sigma c2 */
         padd = sw_bitop3<SW_TT_SEL>(mneg, c1o, c2o); psub = sw_bitop3<SW_TT_SEL>(mneg, c2o, c1o);
         SW_SCHED_FENCE();
-        const uint32_t r = sw_gather4(g0, g1, g2, g3) + padd - psub;
+        const uint32_t r = (MULF ? sw_gather4_perm(g0, g1, g2, g3) : sw_gather4(g0, g1, g2, g3)) + padd - psub;
         const uint32_t rh = sw_opaque(r >> 8); /* one shift serves both odd bytes */
         lds.wr8(a0, r); lds.wr8(a1, rh); lds.wr8(a2, r >> 16); lds.wr8(a3, rh >> 16);
     }
@@ -771,7 +832,7 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
             _Pragma("unroll") for (int g0 = 0; g0 < SW_ILP; g0 += 2) {                                                                   \
                 _Pragma("unroll") for (int g = g0; g < g0 + 2; ++g) { const int j = j0 + g; if (j < NJ) { PRE } }                       \
                 if (j0 + g0 + 1 < NJ) sh_[g0 >> 1] = sw_shl8x2(SRC(g0, j0 + g0), SRC(g0 + 1, j0 + g0 + 1));                              \
-                else if (j0 + g0 < NJ) sh_[g0 >> 1] = SRC(g0, j0 + g0) << 8;                                                             \
+                else if (j0 + g0 < NJ) sh_[g0 >> 1] = SW_SHL8(SRC(g0, j0 + g0));                                                           \
             }                                                                                                                            \
         } else {                                                                                                                         \
             SW_EDGES(PRE)                                                                                                                \
@@ -887,8 +948,8 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
     uint32_t c1n, c2n;
     if (NOWIN) {
         /* one table, whatever the row's parity: composed with the thermometer decode (cste_2 from min1, cste_1 from min2) */
-        c2n = sw_therm2msg(t1, K.tm);
-        c1n = sw_therm2msg(t2, K.tm);
+        c2n = VK ? sw_therm2msg_vk(t1, K.tm, K.c0f) : sw_therm2msg(t1, K.tm);
+        c1n = VK ? sw_therm2msg_vk(t2, K.tm, K.c0f) : sw_therm2msg(t2, K.tm);
     } else if (METHOD == 0) {
         /* the levels of the search ARE cste() of the minima (CLDPC.cpp:337-352: cste_2 from min1, cste_1 from min2, one factor) */
         c2n = min1;
@@ -922,7 +983,7 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
     /* new message on edge j is negative iff s_j ^ XOR_all(s) ^ (deg odd) (the 0xC0 / 0x40 constants of
      * CDecoder_FAID.cpp:902-917); with nn_j = bit 7 of ts_j = "V2C not negative" that is: not negative iff nn_j ^ F,
      * F = bit 7 of the XOR of all ts */
-    const uint32_t fm = (WAVES == 2 && WAVE == 1) ? fm_x : sw_mask7(sx, sel_sign);
+    const uint32_t fm = (WAVES == 2 && WAVE == 1) ? fm_x : SW_MASK7(sx);
     if (WAVES == 2 && WAVE == 1) { c2n = c2n_x; c1n = 0u; } /* (everything per row below is wave 0's: dead code here) */
 
     /* ---- binary index of an edge that attains the minimum.  Bits 0..2: ta[b] runs over the edges whose index has bit b clear,
@@ -931,8 +992,28 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
      * minimum that is its index; a tie leaves 16 / 8 / 0 + the AND of the tied indices' low bits, not above one of the tied
      * edges in that range, so still an edge of the row - and in a tie c1 == c2 ---- */
     uint32_t idx = 0, ne7_3 = 0, ne7_4 = 0; /* the decode words of bits 3 and 4, kept for their byte masks below */
+    uint32_t idx8 = 0; /* SW_FORM_VK: idx << 3 */
+    if (VK) {
+        /* The same five bits collected at bit 7 and shifted DOWN into place: bit b enters at bit 7 and is moved right 4 - b times, so
+         * the word ends as idx << 3 - no bit ever below bit 3 of its byte, nothing crosses into the byte below - and one more shift
+         * gives idx.  Every step reads the one constant 0x80 in a register where the form above reads a one-hot constant per bit (no
+         * literal in v_bitop3_b32: an SGPR each), in as many instructions; and 4 * idx, the arg-min table's index, is a RIGHT shift of it. */
+        uint32_t n7[5];
 #pragma unroll
-    for (int b = 4; b >= 0; --b) {
+        for (int b = 0; b < 5; ++b) n7[b] = sw_bitop3<SW_TT_XORAND>(ta[b], t1, c7f) + c7f; /* bit 7 of every byte: ta[b] != t1 */
+        ne7_4 = n7[4]; ne7_3 = n7[3];
+        const uint32_t b4 = sw_bitop3<0x0a>(n7[4], n7[4], c80); /* ~a & c */
+        const uint32_t b3 = sw_bitop3<0x02>(n7[3], b4, c80);    /* ~a & ~b & c: bit 3 gives way to bit 4 */
+        uint32_t acc = n7[0] & c80;
+        acc = sw_bitop3<SW_TT_ANDOR>(n7[1], c80, acc >> 1);
+        acc = sw_bitop3<SW_TT_ANDOR>(n7[2], c80, acc >> 1);
+        acc = (acc >> 1) | b3;
+        acc = (acc >> 1) | b4;
+        idx8 = acc;
+        idx = acc >> 3;
+    }
+#pragma unroll
+    for (int b = 4; b >= 0 && !VK; --b) {
         const uint32_t dd = sw_bitop3<SW_TT_XORAND>(ta[b], t1, c7f);
         const uint32_t ne7 = dd + c7f;      /* bit 7 of every byte: ta[b] != t1 */
         const uint32_t ne = ne7 >> (7 - b); /* the same at bit b */
@@ -950,18 +1031,18 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
      * the table look-up and its use, and the rest of it between the issue of the En reads and theirs.  LDS operations of a
      * wave execute in order: the En reads are ISSUED before the first write of pass 2, so they return the old values. ---- */
     uint32_t pa[4], sbk[4], gk0 = 0, gk1 = 0, gk2 = 0, gk3 = 0, xb = 0;
-    const uint32_t idx4 = idx << 2;
+    const uint32_t idx4 = VK ? idx8 >> 1 : idx << 2;
 #pragma unroll
 #ifdef SW_EXP_NO_ARGMIN /* timing experiment only: results are wrong */
     for (int k = 0; k < 4; ++k) sbk[k] = (cbj[k] << 16) | s4j[k];
 #else
-    for (int k = 0; k < 4; ++k) sbk[k] = WAVE == 0 ? tab.sb_dyn4((idx4 >> (8 * k)) & 0x7cu) : 0u;
+    for (int k = 0; k < 4; ++k) sbk[k] = WAVE == 0 ? tab.sb_dyn4((VK ? idx8 >> (8 * k + 1) : idx4 >> (8 * k)) & 0x7cu) : 0u;
 #endif
     SW_SCHED_FENCE();
 
     /* ---- pass 2 (CDecoder_FAID.cpp:909-929, CDecoder_OMS.cpp:452-471): every edge as if it carried c2 ---- */
     const SwUpd2 u2 = sw_update2_consts<MINSUM>(c2n, fm, bias);
-    const uint32_t cm27 = WAVES == 2 ? 0u - 0x27272727u : K.cm27; /* (two waves per codeword: 128 registers, none to spare for constants) */
+    const uint32_t cm27 = (WAVES == 2 || VK) ? 0u - 0x27272727u : K.cm27; /* (two waves per codeword: 128 registers, none to spare for constants) */
     uint32_t ns[3] = { 0u, 0u, 0u };
     uint32_t cbit[8];
 #pragma unroll
@@ -1026,7 +1107,7 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
     /* (FRESH: not negative on any edge, the selector is its row part) */
     const uint32_t selA = FRESH ? c0642 : sw_argmin_selector(sw_word_pick(nm3, nm4, cur.x[0], cur.x[1], cur.x[2]), oh8, c7f, c01, c0642);
     if (ERA) xb = selA & c01;
-    const uint32_t gb = sw_gather4(gk0, gk1, gk2, gk3);
+    const uint32_t gb = MULF ? sw_gather4_perm(gk0, gk1, gk2, gk3) : sw_gather4(gk0, gk1, gk2, gk3);
     uint32_t tbA = gb + (FRESH ? k_fresh : sw_perm(kt_hi, kt_lo, selA)); /* carries `bias` like tb[] */
     if (ERA) { /* the arg-min edge of a row may be an erased one (a V2C of 0 usually IS the minimum) */
         uint32_t em = 0, match = 0;
@@ -1042,10 +1123,10 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
         xb = sw_bitop3<SW_TT_SEL>(em, ~((en_true + 0x08080808u) >> 7) & c01, xb);
     }
     const uint32_t tsA = MINSUM ? tbA : tbA - (ERA ? (xb | c0642) : selA);
-    const uint32_t msA = sw_mask7(tsA, sel_sign);
+    const uint32_t msA = SW_MASK7(tsA);
     const uint32_t negA = ~(msA ^ fm); /* byte mask: the new message on the arg-min edge is negative */
     const SwUpd2 u1 = sw_update2_consts<MINSUM>(c1n, fm, bias);
-    const uint32_t enA = sw_update2<MINSUM>(tbA, msA, u1, sel_sign, c80, cm27);
+    const uint32_t enA = MULF ? sw_update2_mul<MINSUM>(tbA, msA, u1, sel_sign, c80, cm27, K.c100) : sw_update2<MINSUM>(tbA, msA, u1, sel_sign, c80, cm27);
 
 #pragma unroll
     for (int jg = 2 * SW_ILP; jg < NJ; jg += SW_ILP) { /* the remaining groups of pass 2 */
@@ -1063,6 +1144,8 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
 #undef SW_PASS2_ARITH
 #undef SW_PASS2_STORE
 #undef SW_COL
+#undef SW_MASK7
+#undef SW_SHL8
     if (WAVES == 2) {
         if (WAVE == 1) { xch.put(0, ns[0]); xch.put(1, ns[1]); xch.put(2, ns[2]); }
         xch.barrier(); /* D: wave 1's En is in LDS */
@@ -1085,7 +1168,7 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
     for (int g = 0; g < 3; ++g) {
         const int cnt = n - 8 * g < 0 ? 0 : (n - 8 * g > 8 ? 8 : n - 8 * g);
         const uint32_t valid = 0x01010101u * ((1u << cnt) - 1u);
-        out.x[g] = ~(ns[g] ^ fm) & valid; /* negative iff not (nn ^ F) */
+        out.x[g] = ~(ns[g] ^ fm) & ((VK && cnt == 7) ? c7f : valid); /* negative iff not (nn ^ F) */
     }
     if (!MINSUM) {
         /* A zero message has no sign: stored as "not negative" so that the next iteration's back-track reads

@@ -29,6 +29,7 @@ __device__ __forceinline__ void body(uint32_t (&a)[8], uint32_t b, uint32_t c)
 //   1 "paired":      v_lshlrev_b64, 2 v_add_u32, 2 v_perm_b32 reading the shift's halves          (two masks, 5 instructions, 3 half-rate)
 //   2 "two single":  2 v_lshlrev_b32, 2 v_add_u32, 2 v_perm_b32 reading them                       (two masks, 6 instructions, 4 half-rate)
 //   0 / 5 / 3 / 4:   one v_lshlrev_b64 by 8 / v_lshlrev_b32 by 8 / v_pk_lshlrev_b16 by 8 / v_mul_u32_u24 by 256 held in a VGPR
+//   6 / 7:           v_mul_u32_u24 by the literal 256 / v_add_u32 (what a full-rate instruction costs in the shift's place)
 //                    (the last two: one-for-one stand-ins for v_lshlrev_b32 by 8 in front of the expander's v_perm_b32)
 // (the two adds stand between a shift and its readers, as other edges' instructions do in the layer step.)  MIX: the unit inside the
 // layer step's 7 : 3 mix - full-rate instructions (v_bitop3_b32 / v_add_u32 alternating) behind it.  "paired" and "two single"
@@ -54,6 +55,8 @@ __device__ __forceinline__ void body(uint32_t (&a)[8], uint32_t b, uint32_t c)
 #define SHL_B32 "v_lshlrev_b32 %[m0], 8, %[m0]"
 #define SHL_PK16 "v_pk_lshlrev_b16 %[m0], 8, %[m0] op_sel_hi:[0,1]"
 #define MUL_U24 "v_mul_u32_u24 %[m0], %[m0], %[k]"
+#define MUL_LIT "v_mul_u32_u24 %[m0], 0x100, %[m0]"
+#define ADD_FULL "v_add_u32 %[m0], %[m0], %[k]"
 template <int OP, bool MIX> constexpr int unit_len() { return OP == 1 ? (MIX ? 12 : 5) : OP == 2 ? (MIX ? 13 : 6) : MIX ? 6 : 1; }
 template <int I, int OP, bool MIX>
 __device__ __forceinline__ void body_pair(uint32_t (&m)[8], uint32_t b, uint32_t c, uint32_t k256, uint32_t (&t)[8])
@@ -73,6 +76,10 @@ __device__ __forceinline__ void body_pair(uint32_t (&m)[8], uint32_t b, uint32_t
         else if constexpr (OP == 3) LONE(SHL_PK16, LONE_MIX);
         else if constexpr (OP == 4 && !MIX) LONE(MUL_U24, "");
         else if constexpr (OP == 4) LONE(MUL_U24, LONE_MIX);
+        else if constexpr (OP == 6 && !MIX) LONE(MUL_LIT, "");
+        else if constexpr (OP == 6) LONE(MUL_LIT, LONE_MIX);
+        else if constexpr (OP == 7 && !MIX) LONE(ADD_FULL, "");
+        else if constexpr (OP == 7) LONE(ADD_FULL, LONE_MIX);
         else if constexpr (OP == 2 && !MIX) SINGLES(FILL_0);
         else if constexpr (OP == 2) SINGLES(FILL_7);
         else if constexpr (I % 4 == 0) { if constexpr (MIX) PAIRED(100, 101, FILL_7); else PAIRED(100, 101, FILL_0); }
@@ -81,6 +88,54 @@ __device__ __forceinline__ void body_pair(uint32_t (&m)[8], uint32_t b, uint32_t
         else { if constexpr (MIX) PAIRED(106, 107, FILL_7); else PAIRED(106, 107, FILL_0); }
         body_pair<I + 1, OP, MIX>(m, b, c, k256, t);
     }
+}
+
+// The 64-bit shift and its readers, a unit per asm statement on the fixed pairs of "paired", four chains:
+//   6 "b64, no reader":   v_lshlrev_b64, 2 v_add_u32 that do not read it                                        (3 instructions)
+//   7 "b64, reader at 2": v_lshlrev_b64, v_add_u32, the wait state the compiler puts there, v_add_u32 reading the low half  (3 + s_nop)
+//   8 "two mul lit":      2 v_mul_u32_u24 by the literal 256, 2 v_add_u32 of which one reads a product          (4 instructions)
+//   9 "two shl":          2 v_lshlrev_b32 by 8, 2 v_add_u32 of which one reads a shifted word                   (4 instructions)
+#define B64_FREE(LO, HI) asm volatile("v_lshlrev_b64 v[" #LO ":" #HI "], 8, v[" #LO ":" #HI "]\n\t" ADDS : [m0] "+v"(m0), [m1] "+v"(m1) : [b] "v"(b) : "v" #LO, "v" #HI)
+#define B64_READ(LO, HI) asm volatile("v_lshlrev_b64 v[" #LO ":" #HI "], 8, v[" #LO ":" #HI "]\n\tv_add_u32 %[m0], %[m0], %[b]\n\ts_nop 0\n\tv_add_u32 %[m1], %[m1], v" #LO "\n\t" \
+                                      : [m0] "+v"(m0), [m1] "+v"(m1) : [b] "v"(b) : "v" #LO, "v" #HI)
+template <int I, int OP>
+__device__ __forceinline__ void body_b64(uint32_t (&m)[8], uint32_t b, uint32_t (&t)[8])
+{
+    if constexpr (I < UNITS) {
+        uint32_t& t0 = t[2 * (I % 4)];
+        uint32_t& t1 = t[2 * (I % 4) + 1];
+        uint32_t& m0 = m[2 * (I % 4)];
+        uint32_t& m1 = m[2 * (I % 4) + 1];
+        if constexpr (OP == 6 && I % 4 == 0) B64_FREE(100, 101);
+        else if constexpr (OP == 6 && I % 4 == 1) B64_FREE(102, 103);
+        else if constexpr (OP == 6 && I % 4 == 2) B64_FREE(104, 105);
+        else if constexpr (OP == 6) B64_FREE(106, 107);
+        else if constexpr (OP == 7 && I % 4 == 0) B64_READ(100, 101);
+        else if constexpr (OP == 7 && I % 4 == 1) B64_READ(102, 103);
+        else if constexpr (OP == 7 && I % 4 == 2) B64_READ(104, 105);
+        else if constexpr (OP == 7) B64_READ(106, 107);
+        else if constexpr (OP == 8) asm volatile("v_mul_u32_u24 %[t0], 0x100, %[m0]\n\tv_mul_u32_u24 %[t1], 0x100, %[m1]\n\tv_add_u32 %[m0], %[m0], %[b]\n\tv_add_u32 %[m1], %[m1], %[t0]\n\t"
+                                                 : [m0] "+v"(m0), [m1] "+v"(m1), [t0] "+v"(t0), [t1] "+v"(t1) : [b] "v"(b));
+        else asm volatile("v_lshlrev_b32 %[t0], 8, %[m0]\n\tv_lshlrev_b32 %[t1], 8, %[m1]\n\tv_add_u32 %[m0], %[m0], %[b]\n\tv_add_u32 %[m1], %[m1], %[t0]\n\t"
+                          : [m0] "+v"(m0), [m1] "+v"(m1), [t0] "+v"(t0), [t1] "+v"(t1) : [b] "v"(b));
+        body_b64<I + 1, OP>(m, b, t);
+    }
+}
+template <int OP>
+__global__ __launch_bounds__(64) void k_b64(uint32_t* out, uint32_t seed)
+{
+    extern __shared__ uint32_t dyn[];
+    uint32_t m[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) m[i] = seed * (2 * i + 5) + threadIdx.x;
+    uint32_t b = seed * 31 + 1;
+    uint32_t t[8] = { 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u };
+    for (int r = 0; r < TRIPS; ++r) body_b64<0, OP>(m, b, t);
+    uint32_t s = 0;
+#pragma unroll
+    for (int i = 0; i < 8; ++i) s ^= m[i] ^ t[i];
+    if (dyn[0] == 0x12345678u) s ^= 1;
+    out[blockIdx.x * 64 + threadIdx.x] = s;
 }
 
 template <int OP, bool MIX>
@@ -106,8 +161,11 @@ __global__ __launch_bounds__(64) void k_pair(uint32_t* out, uint32_t seed)
 // 7 v_and_or_b32 with an SGPR source  8 v_lshlrev_b32 (inline constant)  9 v_and_b32 with a 32-bit literal
 // 10 v_mov_b32_sdwa (byte 1 of the source)  11 v_or_b32_sdwa (byte 0 of one source)  12 the same with an SGPR source  13 v_lshrrev_b32 by 8
 // 14 v_lshlrev_b32 by 8  15 v_lshrrev_b32 by 1  16 / 17 the shifts by a register  18 v_sub_u32
+// the candidates of DESIGN.md 3.1j: 19 v_mul_u32_u24 by the literal 256  20 v_mul_u32_u24 by 256 held in a VGPR  21 v_mul_lo_u32
+// 22 v_mad_u32_u24  23 v_lshl_add_u32  24 v_lshl_or_b32  25 v_add_u32 x, x, x (a left shift by one)  26 v_bitop3_b32 with an SGPR source
+// 27 v_mul_u32_u24 by 256 held in an SGPR
 template <int I, int OP>
-__device__ __forceinline__ void body_one(uint32_t (&a)[8], uint32_t b, uint32_t c, uint32_t sg)
+__device__ __forceinline__ void body_one(uint32_t (&a)[8], uint32_t b, uint32_t c, uint32_t sg, uint32_t k256)
 {
     if constexpr (I < BODY) {
         uint32_t& x = a[I % 4];
@@ -129,8 +187,17 @@ __device__ __forceinline__ void body_one(uint32_t (&a)[8], uint32_t b, uint32_t 
         else if constexpr (OP == 16) asm volatile("v_lshlrev_b32 %0, %1, %0" : "+v"(x) : "v"(b));
         else if constexpr (OP == 17) asm volatile("v_lshrrev_b32 %0, %1, %0" : "+v"(x) : "v"(b));
         else if constexpr (OP == 18) asm volatile("v_sub_u32 %0, %0, %1" : "+v"(x) : "v"(b));
+        else if constexpr (OP == 19) asm volatile("v_mul_u32_u24 %0, 0x100, %0" : "+v"(x));
+        else if constexpr (OP == 20) asm volatile("v_mul_u32_u24 %0, %0, %1" : "+v"(x) : "v"(k256));
+        else if constexpr (OP == 21) asm volatile("v_mul_lo_u32 %0, %0, %1" : "+v"(x) : "v"(k256));
+        else if constexpr (OP == 22) asm volatile("v_mad_u32_u24 %0, %0, %1, %2" : "+v"(x) : "v"(k256), "v"(c));
+        else if constexpr (OP == 23) asm volatile("v_lshl_add_u32 %0, %0, 8, %1" : "+v"(x) : "v"(c));
+        else if constexpr (OP == 24) asm volatile("v_lshl_or_b32 %0, %0, 8, %1" : "+v"(x) : "v"(c));
+        else if constexpr (OP == 25) asm volatile("v_add_u32 %0, %0, %0" : "+v"(x));
+        else if constexpr (OP == 26) asm volatile("v_bitop3_b32 %0, %0, %1, %2 bitop3:0x96" : "+v"(x) : "v"(b), "s"(sg));
+        else if constexpr (OP == 27) asm volatile("v_mul_u32_u24 %0, %1, %0" : "+v"(x) : "s"(sg));
         else asm volatile("v_and_b32 %0, 0x87878787, %0" : "+v"(x));
-        body_one<I + 1, OP>(a, b, c, sg);
+        body_one<I + 1, OP>(a, b, c, sg, k256);
     }
 }
 
@@ -143,7 +210,9 @@ __global__ __launch_bounds__(64) void k_one(uint32_t* out, uint32_t seed)
     for (int i = 0; i < 8; ++i) a[i] = seed * (2 * i + 3) + threadIdx.x;
     uint32_t b = seed * 31 + 1, c = seed ^ 0x12345;
     const uint32_t sg = seed * 7;
-    for (int r = 0; r < TRIPS; ++r) body_one<0, OP>(a, b, c, sg);
+    uint32_t k256 = 256u;
+    asm volatile("" : "+v"(k256));
+    for (int r = 0; r < TRIPS; ++r) body_one<0, OP>(a, b, c, sg, k256);
     uint32_t s = 0;
 #pragma unroll
     for (int i = 0; i < 8; ++i) s ^= a[i];
@@ -250,6 +319,42 @@ int shift_forms(uint32_t* d, double ghz)
     return 0;
 }
 
+// "classes": the table of DESIGN.md 3.1j - one class per kernel at two waves per SIMD, the 64-bit shift's units, and the lone shift forms in the mix
+int issue_classes(uint32_t* d, double ghz)
+{
+    printf("one instruction class per kernel, four chains, two waves per SIMD:\n");
+    const int w = 2;
+    run(k_one<0>, "add", d, w, ghz);
+    run(k_one<18>, "sub", d, w, ghz);
+    run(k_one<1>, "bitop3", d, w, ghz);
+    run(k_one<26>, "bitop3 sg", d, w, ghz);
+    run(k_one<9>, "and lit", d, w, ghz);
+    run(k_one<13>, "shr 8", d, w, ghz);
+    run(k_one<14>, "shl 8", d, w, ghz);
+    run(k_one<25>, "add x,x,x", d, w, ghz);
+    run(k_one<6>, "add sgpr", d, w, ghz);
+    run(k_one<2>, "perm", d, w, ghz);
+    run(k_one<4>, "add3", d, w, ghz);
+    run(k_one<19>, "mul24 lit", d, w, ghz);
+    run(k_one<20>, "mul24 vgpr", d, w, ghz);
+    run(k_one<27>, "mul24 sgpr", d, w, ghz);
+    run(k_one<21>, "mul_lo", d, w, ghz);
+    run(k_one<22>, "mad24", d, w, ghz);
+    run(k_one<23>, "lshl_add", d, w, ghz);
+    run(k_one<24>, "lshl_or", d, w, ghz);
+    printf("the 64-bit shift and what could stand in for it, per unit:\n");
+    run_unit(k_b64<6>, "b64, 2 add, no reader", 3, d, w, ghz);
+    run_unit(k_b64<7>, "b64, add, s_nop, add reading it", 3, d, w, ghz);
+    run_unit(k_b64<8>, "2 mul24 lit, 2 add (one reads)", 4, d, w, ghz);
+    run_unit(k_b64<9>, "2 shl 8, 2 add (one reads)", 4, d, w, ghz);
+    printf("a lone left shift by 8 in the layer step's mix (shift, perm, 4 full-rate):\n");
+    RUN_UNIT(5, true, "mix: v_lshlrev_b32, perm, 4 full", w);
+    RUN_UNIT(4, true, "mix: v_mul_u32_u24 VGPR, perm, 4 full", w);
+    RUN_UNIT(6, true, "mix: v_mul_u32_u24 lit, perm, 4 full", w);
+    RUN_UNIT(7, true, "mix: v_add_u32 (full), perm, 4 full", w);
+    return 0;
+}
+
 int main(int argc, char** argv)
 {
     hipDeviceProp_t p;
@@ -260,6 +365,7 @@ int main(int argc, char** argv)
     uint32_t* d;
     (void)hipMalloc(&d, (size_t)256 * 4 * 8 * 4 * 64 * 4);
     if (argc > 1 && argv[1][0] == 's') return shift_forms(d, ghz); // "shifts": only the table of DESIGN.md 3.1h
+    if (argc > 1 && argv[1][0] == 'c') return issue_classes(d, ghz); // "classes": only the table of DESIGN.md 3.1j
     run_alone(k<4>, "4 chains", d, ghz);
     run_alone(k<8>, "8 chains", d, ghz);
     for (int w : { 2, 3, 4, 5, 8 }) {
