@@ -997,8 +997,9 @@ int lnsfaid_code_zero_shift_order(const lnsfaid_code* code, int32_t* groups, int
 int lnsfaid_code_bf_walk(const lnsfaid_code* code, int32_t col_weight, uint32_t* full, uint32_t* flipped, uint32_t* fixed, int32_t* info);
 
 /* Workgroups (codewords) of the selected decode kernel a compute unit holds at once, from the HIP occupancy query, next to
- * what the kernel's LDS footprint alone would allow (50G-PON: 8 and 8).  A smaller first number means a build lost residency to
- * registers - about 40 % of the throughput for the one-wave-per-codeword kernel.  Also checks that the kernel has no static LDS
+ * what the kernel's LDS footprint alone would allow, at most the 8 per compute unit the kernels' register budget is written for
+ * (50G-PON: 8 and 8; a code with a smaller LDS image: still 8; a wider one: fewer, 5 for N = 27648).  A smaller first number means
+ * a build lost residency to registers - about 40 % of the throughput for the one-wave-per-codeword kernel.  Also checks that the kernel has no static LDS
  * (LNSFAID_E_INTERNAL otherwise; every decode call checks the same once per kernel instance). */
 int lnsfaid_kernel_residency(lnsfaid_ctx* ctx, int32_t* workgroups_per_cu, int32_t* lds_limit);
 

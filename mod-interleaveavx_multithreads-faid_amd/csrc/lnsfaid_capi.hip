@@ -843,7 +843,10 @@ extern "C" int lnsfaid_message_store(const lnsfaid_ctx* ctx)
  *    (adding a __shared__ variable to a decode kernel would otherwise corrupt En silently);
  *  - how many of its workgroups a CU holds.  The decoders are sized so that LDS alone decides that (50G-PON: 20 424 B per
  *    codeword, 8 per CU); one more register or LDS word in the wrong place halves it, which costs ~40 % of the throughput and
- *    nothing else would show.  Recorded for lnsfaid_kernel_residency, printed under LNSFAID_TRACE. */
+ *    nothing else would show.  Recorded for lnsfaid_kernel_residency, printed under LNSFAID_TRACE.  The LDS limit is capped at
+ *    the 8 workgroups per CU the kernels' launch bounds are written for: the image of a narrower code would let more of them in,
+ *    but their register budget stops at 8 by design, and (8, 20) would read as residency lost to registers. */
+#define LF_BUILT_RESIDENCY 8
 static int kernel_check(lnsfaid_ctx* ctx, int rule, bool packed = false)
 {
     int threads = 0;
@@ -867,6 +870,7 @@ static int kernel_check(lnsfaid_ctx* ctx, int rule, bool packed = false)
     int by_lds = (int)(lds_cu / ((ctx->lds_bytes + gran - 1) / gran * gran));
     const int by_waves = 32 / ((threads + 63) / 64); /* 32 wave slots per CU */
     if (by_lds > by_waves) by_lds = by_waves;
+    if (by_lds > LF_BUILT_RESIDENCY) by_lds = LF_BUILT_RESIDENCY;
     ctx->checked_fn[slot] = fn; ctx->resident_wg[slot] = wg; ctx->lds_wg[slot] = by_lds;
     static const bool trace = getenv("LNSFAID_TRACE") != nullptr;
     if (trace)

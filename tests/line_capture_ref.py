@@ -25,7 +25,7 @@ def words(code, fmt):
 def unpack(w):
     """uint32 [n, words] -> uint8 0 / 1 [n, 32 words], bit b of word w at position 32 w + b"""
     w = np.ascontiguousarray(w, dtype="<u4")
-    return np.unpackbits(w.view(np.uint8).reshape(w.shape[0], -1), axis=1, bitorder="little")
+    return np.unpackbits(w.view(np.uint8).reshape(w.shape[0], 4 * w.shape[1]), axis=1, bitorder="little")  # (no -1: n may be 0)
 
 
 def pack(b):
