@@ -21,84 +21,7 @@
 #include "lnsfaid_burst.h"
 #include "lnsfaid_quantise.h"
 #include "lnsfaid_swar.h" /* sw_nms_fits / sw_nms_tables (host side) */
-
-extern "C" hipError_t lf_launch_decode(int method, int uniform_w, const LfKernelArgs* args, size_t lds_bytes,
-                                       hipStream_t stream);
-extern "C" const void* lf_decode_func(int method, int uniform_w);
-extern "C" int lf_decode_threads(void);
-extern "C" const void* lf_decode4_func(int method, int ef, int rm);
-extern "C" int lf_decode4_threads(void);
-extern "C" hipError_t lf_launch_decode4(int method, int ef, int rm, const LfKernelArgs* args, size_t lds_bytes, hipStream_t stream);
-extern "C" int lf_decode4_rm_layers(void);
-extern "C" const void* lf_decode4cw_func(int method, int ef, int rm);
-extern "C" hipError_t lf_launch_decode4cw(int method, int ef, int rm, const LfCwArgs* args, size_t lds_bytes, hipStream_t stream);
-extern "C" const void* lf_decode4p_func(int method, int ef, int rm, int per_codeword);
-extern "C" hipError_t lf_launch_decode4p(int method, int ef, int rm, const LfKernelArgs* args, size_t lds_bytes, hipStream_t stream);
-extern "C" hipError_t lf_launch_decode4pcw(int method, int ef, int rm, const LfCwArgs* args, size_t lds_bytes, hipStream_t stream);
-extern "C" const void* lf_decode4l_func(int method, int ef, int rm);
-extern "C" hipError_t lf_launch_decode4l(int method, int ef, int rm, const LfLineArgs* args, size_t lds_bytes, hipStream_t stream);
-extern "C" hipError_t lf_launch_unpack_llr4(const uint8_t* d_llr4, int8_t* d_fix, size_t n_values, hipStream_t stream);
-extern "C" hipError_t lf_launch_pack_bits(const int8_t* d_decoded, uint32_t* d_bits, size_t n_values, hipStream_t stream);
-extern "C" hipError_t lf_launch_count_errors_packed(const uint32_t* d_bits, const uint32_t* d_msg, int n_var, int k_info, size_t n_cw,
-                                                    unsigned long long* out, hipStream_t stream);
-extern "C" int lf_decode4z_inst(int deg, int zg);
-extern "C" const void* lf_decode4z_func(int method);
-extern "C" hipError_t lf_launch_decode4z(int method, const LfKernelArgs* args, size_t lds_bytes, hipStream_t stream);
-extern "C" int lf_decode4s_matches(const LfDevCode* code);
-extern "C" const void* lf_decode4s_func(int method);
-extern "C" hipError_t lf_launch_decode4s(int method, const LfKernelArgs* args, size_t lds_bytes, hipStream_t stream);
-extern "C" const void* lf_decode4w_func(int method);
-extern "C" hipError_t lf_launch_decode4w(int method, const LfKernelArgs* args, size_t lds_bytes, hipStream_t stream);
-extern "C" const void* lf_decode5_func(int method);
-extern "C" int lf_decode5_threads(void);
-extern "C" hipError_t lf_launch_decode5(int method, const LfKernelArgs* args, size_t lds_bytes, hipStream_t stream);
-extern "C" hipError_t lf_launch_count_errors(const int8_t* decoded, const int8_t* input_bits, int n_var, int k_info,
-                                             size_t n_cw, unsigned long long* out, hipStream_t stream);
-
-extern "C" hipError_t lf_launch_frontend(const uint32_t* d_seeds, const unsigned long long* d_draws, int n_streams, int mod_type,
-                                         float sigma_ch, float scale, const int8_t* d_codeword, const int8_t* d_frames, int n_var,
-                                         int n_check, int interleave, int fast, int8_t* d_fix, int count_limit,
-                                         unsigned long long* d_frame_cnt, hipStream_t stream);
-extern "C" hipError_t lf_launch_prefec(const float* d_rx, const int8_t* d_sent, size_t n_groups, int mod_type, int n_var, int n_check,
-                                       int interleave, int scope, unsigned long long* d_out, hipStream_t stream);
-extern "C" hipError_t lf_launch_prefec_fold(unsigned long long* d_frame_cnt, size_t n_streams, unsigned long long* d_acc, hipStream_t stream);
-extern "C" hipError_t lf_launch_capture(const int8_t* d_fix, const int8_t* d_decoded, const int8_t* d_sent, size_t n_groups, int n_var,
-                                        int n_check, uint32_t skip, uint32_t cap, uint2* d_cnt, uint32_t* d_slots,
-                                        lnsfaid_error_record* d_records, int8_t* d_payload, unsigned long long* d_meta,
-                                        unsigned long long* d_out, hipStream_t stream);
-extern "C" hipError_t lf_launch_fec_status(const LfDevCode* d_code, int n_var, int packed, const void* d_fix, const void* d_decided,
-                                           const int8_t* d_sent, size_t n_groups, lnsfaid_fec_record* d_records, int want_sent,
-                                           unsigned long long* d_acc, hipStream_t stream);
-extern "C" hipError_t lf_launch_demap(const float* d_rx, size_t n_groups, int mod_type, float scale, int n_var, int n_check,
-                                      int interleave, int packed, void* d_out, hipStream_t stream);
-extern "C" hipError_t lf_frontend_fastpath_scan(double* d_out2, hipStream_t stream);
-extern "C" void lf_frontend_fastpath_assumed(double* eps2);
-extern "C" hipError_t lf_launch_encode(const LfDevCode* d_code, int n_check, const uint32_t* d_bsup, const uint32_t* d_bsup_off,
-                                       const int8_t* d_in, const unsigned long long* d_keys, size_t n_groups, int8_t* d_out,
-                                       int8_t* d_info, hipStream_t stream);
-extern "C" hipError_t lf_launch_encode_line(const LfDevCode* d_code, int n_check, const uint32_t* d_bsup, const uint32_t* d_bsup_off,
-                                            const uint32_t* d_payload, size_t n_codewords, uint32_t* d_line, uint32_t* d_bits,
-                                            hipStream_t stream);
-
-extern "C" const void* lf_decode4b_func(int method, int ef, int rm);
-extern "C" hipError_t lf_launch_decode4b(int method, int ef, int rm, const LfBurstArgs* args, size_t lds_bytes, hipStream_t stream);
-extern "C" hipError_t lf_launch_encode_burst(const LfDevCode* d_code, int n_check, const uint32_t* d_bsup, const uint32_t* d_bsup_off,
-                                             const uint32_t* d_payload, const LfBurstDesc* d_desc, int where, size_t n_codewords,
-                                             uint32_t* d_line, uint32_t* d_bits, hipStream_t stream);
-extern "C" hipError_t lf_launch_line_bsc(const uint32_t* d_in, uint32_t* d_out, size_t n_cw, uint32_t lw, uint64_t key, uint64_t first,
-                                         uint32_t threshold, uint32_t* d_flips, unsigned long long* d_total, hipStream_t stream);
-extern "C" hipError_t lf_launch_line_payload(uint32_t* d_payload, size_t n_cw, uint32_t kw, uint64_t key, uint64_t first, hipStream_t stream);
-extern "C" hipError_t lf_launch_line_count(const uint32_t* d_payload, const uint32_t* d_sent, const lnsfaid_line_stats* d_stats, size_t n_cw,
-                                           uint32_t kw, unsigned long long* d_acc, hipStream_t stream);
-extern "C" hipError_t lf_launch_line_soft(const uint32_t* d_in, uint8_t* d_out, size_t n_cw, uint32_t lw, uint64_t key, uint64_t first,
-                                          const uint32_t table[14], uint32_t* d_flips, unsigned long long* d_total, hipStream_t stream);
-extern "C" hipError_t lf_launch_line_markov(const uint32_t* d_in, uint32_t* d_out, size_t n_cw, uint32_t lw, uint64_t key, uint64_t first,
-                                            const uint32_t t[3], uint32_t* d_flips, uint32_t* d_runs, unsigned long long* d_totals,
-                                            hipStream_t stream);
-extern "C" hipError_t lf_launch_line_capture(const LfDevCode* d_code, int n_var, int puncture_tail, const void* d_line, int format,
-                                             const uint32_t* d_bits, const uint32_t* d_sent, size_t n_cw, uint64_t first, int select,
-                                             uint32_t skip, uint32_t cap, uint4* d_cnt, uint32_t* d_slots, lnsfaid_line_failure* d_records,
-                                             uint32_t* d_payload, unsigned long long* d_meta, hipStream_t stream);
+#include "lnsfaid_launch.h" /* what the kernel files export */
 
 #include <atomic>
 #include <chrono>
@@ -175,12 +98,10 @@ struct lnsfaid_ctx {
     /* staging for lnsfaid_decode_line, allocated at its first call; line and bits go through d_pk_in / d_pk_out */
     uint32_t* d_ln_payload = nullptr;       /* K words per group */
     lnsfaid_line_stats* d_ln_stats = nullptr;
-    const void* checked_line_fn = nullptr;  /* line kernel instance whose static LDS has been looked at */
     /* burst-format line calls, allocated at their first call */
     LfBurstDesc* d_burst_desc = nullptr;    /* [32 * max_groups] descriptors of the call in flight */
     LfBurstDesc* h_burst_desc = nullptr;    /* pinned: where the host forms its prefix sums */
     uint32_t* d_burst_ones = nullptr;       /* short_ones of the host-pointer decode */
-    const void* checked_burst_fn = nullptr; /* burst kernel instance whose static LDS has been looked at */
     int early_stop = LNSFAID_STOP_GROUP; /* rule of lnsfaid_decode / lnsfaid_decode_device (lnsfaid_set_early_stop) */
     int rows_per_lane = 0; /* 0: pick per configuration; 2 / 4: forced (lnsfaid_select_kernel) */
     int waves_per_cw = 0;  /* 0 / 1: one wave per codeword; 2: lnsfaid_kernel5.hip where it applies (lnsfaid_select_waves) */
@@ -192,8 +113,9 @@ struct lnsfaid_ctx {
     mutable int static_code = -1; /* the code's zero-first edge tables equal the layer-static kernel's constants: -1 not compared yet */
     struct LfCombiner* comb = nullptr; /* call combiner this one-group context is a member of (see below) */
     int comb_slot = -1;
-    const void* checked_fn[4] = {};           /* kernel instance kernel_check() last looked at, per early-stop rule (+ 2: packed I/O) */
-    int resident_wg[4] = {}, lds_wg[4] = {};  /* its workgroups per CU: what the occupancy query says / what its LDS alone allows */
+    const void* checked_fn[6] = {};           /* kernel instance kernel_check() last looked at, per entry kind (LF_ENTRY_*) */
+    int resident_wg[4] = {}, lds_wg[4] = {};  /* its workgroups per CU: what the occupancy query says / what its LDS alone allows
+                                               * (the four entry kinds of the decode calls) */
     void* comm = nullptr;      /* ncclComm_t for lnsfaid_allreduce_counters */
     bool comm_owned = false;
     unsigned long long* d_reduce = nullptr;
@@ -688,7 +610,7 @@ static int layer_zero_groups(const lnsfaid_ctx* ctx, int br) { return (ctx->hcod
 static bool zero_shift_possible(const lnsfaid_ctx* ctx)
 {
     if (!use_kernel4(ctx) || use_kernel5(ctx) || !use_msg_registers(ctx)) return false;
-    if (ctx->hcfg.method < 1 || ctx->hcfg.method > 5 || !lf_decode4z_func(ctx->hcfg.method)) return false;
+    if (ctx->hcfg.method < 1 || ctx->hcfg.method > 5) return false; /* what lnsfaid_kernel4z / 4s / 4w.hip are built for */
     for (int br = 0; br < ctx->hcode.nbr; ++br)
         if (layer_zero_groups(ctx, br) >= 1) return true;
     return false;
@@ -700,7 +622,7 @@ static bool use_zero_shift(const lnsfaid_ctx* ctx) { return ctx->zero_shift != L
 static bool static_layers_possible(const lnsfaid_ctx* ctx)
 {
     if (ctx->static_code < 0) ctx->static_code = lf_decode4s_matches(&ctx->hcode); /* (the tables never change after creation) */
-    return ctx->static_code == 1 && zero_shift_possible(ctx) && lf_decode4s_func(ctx->hcfg.method);
+    return ctx->static_code == 1 && zero_shift_possible(ctx);
 }
 static bool use_static_layers(const lnsfaid_ctx* ctx)
 {
@@ -710,8 +632,7 @@ static bool use_static_layers(const lnsfaid_ctx* ctx)
  * error-floor window: nombre_iterations <= floor_iter_thresh never holds for a negative threshold (the shipped DecodeMethod 2). */
 static bool use_window_free(const lnsfaid_ctx* ctx)
 {
-    return use_static_layers(ctx) && ctx->zero_shift != LNSFAID_ZERO_SHIFT_WINDOWED && ctx->hcfg.floor_iter_thresh < 0 &&
-           lf_decode4w_func(ctx->hcfg.method);
+    return use_static_layers(ctx) && ctx->zero_shift != LNSFAID_ZERO_SHIFT_WINDOWED && ctx->hcfg.floor_iter_thresh < 0;
 }
 
 extern "C" int lnsfaid_select_zero_shift(lnsfaid_ctx* ctx, int32_t mode)
@@ -796,31 +717,36 @@ static bool cw_possible(const lnsfaid_ctx* ctx) { return ctx->waves_per_cw != 2 
  * packed I/O through conversion kernels around the int8 decode. */
 static bool packed_kernel(const lnsfaid_ctx* ctx) { return use_kernel4(ctx) && !use_kernel5(ctx); }
 
-static const void* selected_kernel(const lnsfaid_ctx* ctx, int* threads, int rule, bool packed = false)
+/* ---- select, check, launch: the one path from a context to a running decode kernel ----
+ * The entry kinds: the two early-stop rules of the decode calls (LNSFAID_STOP_GROUP, LNSFAID_STOP_CODEWORD), the same on packed
+ * I/O, and the line formats.  An instance is what a launch needs of a kernel. */
+enum { LF_ENTRY_GROUP = LNSFAID_STOP_GROUP, LF_ENTRY_CW = LNSFAID_STOP_CODEWORD, LF_ENTRY_PACKED = 2 /* + rule */, LF_ENTRY_LINE = 4, LF_ENTRY_BURST };
+static int decode_entry(int rule, bool packed) { return rule + (packed ? LF_ENTRY_PACKED : 0); }
+struct LfInst {
+    const void* fn; /* null: the configuration has no instance of this kind */
+    int threads;    /* per workgroup; one workgroup per codeword */
+};
+
+/* the instance the context runs an entry kind on: the only place that asks the kernel files */
+static LfInst select_kernel(const lnsfaid_ctx* ctx, int entry)
 {
-    if (packed) {
-        *threads = lf_decode4_threads();
-        return lf_decode4p_func(ctx->hcfg.method, ctx->hcfg.ef, use_msg_registers(ctx) ? 1 : 0, rule == LNSFAID_STOP_CODEWORD ? 1 : 0);
+    const int m = ctx->hcfg.method, ef = ctx->hcfg.ef, rm = use_msg_registers(ctx) ? 1 : 0;
+    LfInst k = { nullptr, lf_decode4_threads() };
+    switch (entry) {
+    case LF_ENTRY_PACKED + LF_ENTRY_GROUP: k.fn = lf_decode4p_func(m, ef, rm, 0); break;
+    case LF_ENTRY_PACKED + LF_ENTRY_CW: k.fn = lf_decode4p_func(m, ef, rm, 1); break;
+    case LF_ENTRY_CW: if (cw_possible(ctx)) k.fn = lf_decode4cw_func(m, ef, rm); break;
+    case LF_ENTRY_LINE: k.fn = lf_decode4l_func(m, ef, rm); break;
+    case LF_ENTRY_BURST: k.fn = lf_decode4b_func(m, ef, rm); break;
+    default: /* the group rule on int8 I/O: every kernel has it */
+        if (use_kernel5(ctx)) { k.fn = lf_decode5_func(m); k.threads = lf_decode5_threads(); }
+        else if (use_window_free(ctx)) k.fn = lf_decode4w_func(m);
+        else if (use_static_layers(ctx)) k.fn = lf_decode4s_func(m);
+        else if (use_zero_shift(ctx)) k.fn = lf_decode4z_func(m);
+        else if (use_kernel4(ctx)) k.fn = lf_decode4_func(m, ef, rm);
+        else { k.fn = lf_decode_func(m, ctx->hcfg.uniform_w); k.threads = lf_decode_threads(); }
     }
-    if (rule == LNSFAID_STOP_CODEWORD) {
-        *threads = lf_decode4_threads();
-        return cw_possible(ctx) ? lf_decode4cw_func(ctx->hcfg.method, ctx->hcfg.ef, use_msg_registers(ctx) ? 1 : 0) : nullptr;
-    }
-    if (use_kernel5(ctx)) {
-        *threads = lf_decode5_threads();
-        return lf_decode5_func(ctx->hcfg.method);
-    }
-    if (use_zero_shift(ctx)) {
-        *threads = lf_decode4_threads();
-        if (use_window_free(ctx)) return lf_decode4w_func(ctx->hcfg.method);
-        return use_static_layers(ctx) ? lf_decode4s_func(ctx->hcfg.method) : lf_decode4z_func(ctx->hcfg.method);
-    }
-    if (use_kernel4(ctx)) {
-        *threads = lf_decode4_threads();
-        return lf_decode4_func(ctx->hcfg.method, ctx->hcfg.ef, use_msg_registers(ctx) ? 1 : 0);
-    }
-    *threads = lf_decode_threads();
-    return lf_decode_func(ctx->hcfg.method, ctx->hcfg.uniform_w);
+    return k;
 }
 
 extern "C" int lnsfaid_select_message_store(lnsfaid_ctx* ctx, int32_t where)
@@ -847,19 +773,26 @@ extern "C" int lnsfaid_message_store(const lnsfaid_ctx* ctx)
  *    the 8 workgroups per CU the kernels' launch bounds are written for: the image of a narrower code would let more of them in,
  *    but their register budget stops at 8 by design, and (8, 20) would read as residency lost to registers. */
 #define LF_BUILT_RESIDENCY 8
-static int kernel_check(lnsfaid_ctx* ctx, int rule, bool packed = false)
+/* Selects the instance of an entry kind into *inst and checks it: what a caller launches is what was looked at.  (The line
+ * formats' kernels get the first look only: their calls have no residency to report.) */
+static int kernel_check(lnsfaid_ctx* ctx, int entry, LfInst* inst)
 {
-    int threads = 0;
-    const void* fn = selected_kernel(ctx, &threads, rule, packed);
-    if (!fn) return rule == LNSFAID_STOP_CODEWORD ? LNSFAID_E_INVAL : LNSFAID_E_INTERNAL; /* no per-codeword instance */
-    const int slot = rule + (packed ? 2 : 0);
-    if (fn == ctx->checked_fn[slot]) return LNSFAID_OK;
+    *inst = select_kernel(ctx, entry);
+    const void* fn = inst->fn;
+    const int threads = inst->threads;
+    const bool group_rule = entry == LF_ENTRY_GROUP || entry == LF_ENTRY_PACKED + LF_ENTRY_GROUP;
+    if (!fn) return group_rule ? LNSFAID_E_INTERNAL : LNSFAID_E_INVAL; /* no per-codeword instance */
+    if (fn == ctx->checked_fn[entry]) return LNSFAID_OK;
     hipFuncAttributes at;
     HIP_TRY(hipFuncGetAttributes(&at, fn));
     if (at.sharedSizeBytes != 0) {
-        snprintf(g_hip_err, sizeof(g_hip_err), "decode kernel has %zu bytes of static LDS: its En image would not start at LDS offset 0",
-                 (size_t)at.sharedSizeBytes);
+        snprintf(g_hip_err, sizeof(g_hip_err), "%sdecode kernel has %zu bytes of static LDS: its En image would not start at LDS offset 0",
+                 entry == LF_ENTRY_LINE ? "line " : entry == LF_ENTRY_BURST ? "burst " : "", (size_t)at.sharedSizeBytes);
         return LNSFAID_E_INTERNAL;
+    }
+    if (entry >= LF_ENTRY_LINE) {
+        ctx->checked_fn[entry] = fn;
+        return LNSFAID_OK;
     }
     int wg = 0;
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg, fn, threads, ctx->lds_bytes));
@@ -871,7 +804,7 @@ static int kernel_check(lnsfaid_ctx* ctx, int rule, bool packed = false)
     const int by_waves = 32 / ((threads + 63) / 64); /* 32 wave slots per CU */
     if (by_lds > by_waves) by_lds = by_waves;
     if (by_lds > LF_BUILT_RESIDENCY) by_lds = LF_BUILT_RESIDENCY;
-    ctx->checked_fn[slot] = fn; ctx->resident_wg[slot] = wg; ctx->lds_wg[slot] = by_lds;
+    ctx->checked_fn[entry] = fn; ctx->resident_wg[entry] = wg; ctx->lds_wg[entry] = by_lds;
     static const bool trace = getenv("LNSFAID_TRACE") != nullptr;
     if (trace)
         fprintf(stderr, "[lnsfaid] decode kernel: %d threads, %d VGPRs, %zu B LDS per workgroup, %d workgroups per CU (LDS alone: %d)%s\n",
@@ -883,10 +816,34 @@ extern "C" int lnsfaid_kernel_residency(lnsfaid_ctx* ctx, int32_t* workgroups_pe
 {
     if (!ctx) return LNSFAID_E_INVAL;
     HIP_TRY(hipSetDevice(ctx->device));
-    const int rc = kernel_check(ctx, ctx->early_stop);
+    LfInst k;
+    const int rc = kernel_check(ctx, decode_entry(ctx->early_stop, false), &k);
     if (rc) return rc;
     if (workgroups_per_cu) *workgroups_per_cu = ctx->resident_wg[ctx->early_stop];
     if (lds_limit) *lds_limit = ctx->lds_wg[ctx->early_stop];
+    return LNSFAID_OK;
+}
+
+/* one workgroup per codeword on a checked instance; args: the kernel's argument struct */
+static hipError_t launch_decode(const lnsfaid_ctx* ctx, const LfInst& k, const void* args, size_t n_cw)
+{
+    void* kargs[] = { (void*)args };
+    return hipLaunchKernel(k.fn, dim3((unsigned)n_cw), dim3((unsigned)k.threads), kargs, ctx->lds_bytes, ctx->stream);
+}
+
+/* one launch, one wait: the calls without a chain (the per-codeword rule, the line formats).  what: the call's name in the trace */
+static int launch_decode_timed(lnsfaid_ctx* ctx, const LfInst& k, const void* args, size_t n_cw, const char* what)
+{
+    static const bool trace = getenv("LNSFAID_TRACE") != nullptr;
+    HIP_TRY(hipEventRecord(ctx->ev_chain[0], ctx->stream));
+    HIP_TRY(launch_decode(ctx, k, args, n_cw));
+    HIP_TRY(hipEventRecord(ctx->ev_chain[1], ctx->stream));
+    { const int rcw = stream_wait(ctx); if (rcw) return rcw; }
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_chain[0], ctx->ev_chain[1]));
+    ctx->kernel_ms += ms;
+    ctx->kernel_launches += 1;
+    if (trace) fprintf(stderr, "[lnsfaid] %s launch: %.3f ms, %zu codewords\n", what, ms, n_cw);
     return LNSFAID_OK;
 }
 
@@ -937,8 +894,9 @@ static int decode_cw_device_impl(lnsfaid_ctx* ctx, const int8_t* d_fixInput, siz
     if (!cw_possible(ctx)) return LNSFAID_E_INVAL;
     if (n_groups == 0) return LNSFAID_OK;
     HIP_TRY(hipSetDevice(ctx->device));
+    LfInst k;
     {
-        const int rc = kernel_check(ctx, LNSFAID_STOP_CODEWORD, packed);
+        const int rc = kernel_check(ctx, decode_entry(LNSFAID_STOP_CODEWORD, packed), &k);
         if (rc) return rc;
     }
     const size_t n_cw = n_groups * LNSFAID_GROUP;
@@ -949,18 +907,7 @@ static int decode_cw_device_impl(lnsfaid_ctx* ctx, const int8_t* d_fixInput, siz
     a.skip = status_preloaded ? ctx->d_status[0] : nullptr;
     a.stats = d_stats; a.cw_stats = d_cw_stats; a.n_cw = (int32_t)n_cw;
     if (d_stats) HIP_TRY(hipMemsetAsync(d_stats, 0, n_groups * sizeof(lnsfaid_group_stats), ctx->stream));
-    static const bool trace = getenv("LNSFAID_TRACE") != nullptr;
-    HIP_TRY(hipEventRecord(ctx->ev_chain[0], ctx->stream));
-    if (packed) HIP_TRY(lf_launch_decode4pcw(ctx->hcfg.method, ctx->hcfg.ef, use_msg_registers(ctx) ? 1 : 0, &a, ctx->lds_bytes, ctx->stream));
-    else HIP_TRY(lf_launch_decode4cw(ctx->hcfg.method, ctx->hcfg.ef, use_msg_registers(ctx) ? 1 : 0, &a, ctx->lds_bytes, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_chain[1], ctx->stream));
-    { const int rcw = stream_wait(ctx); if (rcw) return rcw; }
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_chain[0], ctx->ev_chain[1]));
-    ctx->kernel_ms += ms;
-    ctx->kernel_launches += 1;
-    if (trace) fprintf(stderr, "[lnsfaid] per-codeword launch: %.3f ms, %zu codewords\n", ms, n_cw);
-    return LNSFAID_OK;
+    return launch_decode_timed(ctx, k, &a, n_cw, "per-codeword");
 }
 
 static int decode_device_impl(lnsfaid_ctx* ctx, const int8_t* d_fixInput, size_t n_groups, int8_t* d_decodedBits,
@@ -970,8 +917,9 @@ static int decode_device_impl(lnsfaid_ctx* ctx, const int8_t* d_fixInput, size_t
     if (n_groups > ctx->max_groups) return LNSFAID_E_INVAL;
     if (n_groups == 0) return LNSFAID_OK;
     HIP_TRY(hipSetDevice(ctx->device));
+    LfInst k; /* picked and checked once per call: every launch of the chain below runs it */
     {
-        const int rc = kernel_check(ctx, LNSFAID_STOP_GROUP, packed);
+        const int rc = kernel_check(ctx, decode_entry(LNSFAID_STOP_GROUP, packed), &k);
         if (rc) return rc;
     }
     const size_t n_cw = n_groups * LNSFAID_GROUP;
@@ -1008,13 +956,7 @@ static int decode_device_impl(lnsfaid_ctx* ctx, const int8_t* d_fixInput, size_t
             a.status_next = ctx->d_status[cur ^ 1];
             a.remaining = ctx->d_remaining + j;
             HIP_TRY(hipEventRecord(ctx->ev_chain[j], ctx->stream));
-            if (packed) HIP_TRY(lf_launch_decode4p(ctx->hcfg.method, ctx->hcfg.ef, use_msg_registers(ctx) ? 1 : 0, &a, ctx->lds_bytes, ctx->stream));
-            else if (use_kernel5(ctx)) HIP_TRY(lf_launch_decode5(ctx->hcfg.method, &a, ctx->lds_bytes, ctx->stream));
-            else if (use_window_free(ctx)) HIP_TRY(lf_launch_decode4w(ctx->hcfg.method, &a, ctx->lds_bytes, ctx->stream));
-            else if (use_static_layers(ctx)) HIP_TRY(lf_launch_decode4s(ctx->hcfg.method, &a, ctx->lds_bytes, ctx->stream));
-            else if (use_zero_shift(ctx)) HIP_TRY(lf_launch_decode4z(ctx->hcfg.method, &a, ctx->lds_bytes, ctx->stream));
-            else if (use_kernel4(ctx)) HIP_TRY(lf_launch_decode4(ctx->hcfg.method, ctx->hcfg.ef, use_msg_registers(ctx) ? 1 : 0, &a, ctx->lds_bytes, ctx->stream));
-            else HIP_TRY(lf_launch_decode(ctx->hcfg.method, ctx->hcfg.uniform_w, &a, ctx->lds_bytes, ctx->stream));
+            HIP_TRY(launch_decode(ctx, k, &a, n_cw));
             cur ^= 1;
         }
         HIP_TRY(hipEventRecord(ctx->ev_chain[chain], ctx->stream));
@@ -1742,18 +1684,10 @@ static size_t line_bytes(const lnsfaid_ctx* ctx, int32_t format)
 static int decode_line_launch(lnsfaid_ctx* ctx, const void* d_line, int32_t format, int32_t magnitude, size_t n_codewords,
                               uint32_t* d_payload, uint32_t* d_bits, lnsfaid_line_stats* d_stats)
 {
-    const int rm = use_msg_registers(ctx) ? 1 : 0;
-    const void* fn = lf_decode4l_func(ctx->hcfg.method, ctx->hcfg.ef, rm);
-    if (!fn) return LNSFAID_E_INVAL;
-    if (fn != ctx->checked_line_fn) { /* as kernel_check: the En image must start at LDS offset 0 */
-        hipFuncAttributes at;
-        HIP_TRY(hipFuncGetAttributes(&at, fn));
-        if (at.sharedSizeBytes != 0) {
-            snprintf(g_hip_err, sizeof(g_hip_err), "line decode kernel has %zu bytes of static LDS: its En image would not start at LDS offset 0",
-                     (size_t)at.sharedSizeBytes);
-            return LNSFAID_E_INTERNAL;
-        }
-        ctx->checked_line_fn = fn;
+    LfInst k;
+    {
+        const int rc = kernel_check(ctx, LF_ENTRY_LINE, &k);
+        if (rc) return rc;
     }
     LfLineArgs a;
     a.code = ctx->d_code; a.cfg = ctx->d_cfg;
@@ -1761,17 +1695,7 @@ static int decode_line_launch(lnsfaid_ctx* ctx, const void* d_line, int32_t form
     a.st_rows = ctx->d_rows;
     a.stats = d_stats;
     a.format = format; a.magnitude = magnitude; a.n_cw = (int32_t)n_codewords;
-    static const bool trace = getenv("LNSFAID_TRACE") != nullptr;
-    HIP_TRY(hipEventRecord(ctx->ev_chain[0], ctx->stream));
-    HIP_TRY(lf_launch_decode4l(ctx->hcfg.method, ctx->hcfg.ef, rm, &a, ctx->lds_bytes, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_chain[1], ctx->stream));
-    { const int rcw = stream_wait(ctx); if (rcw) return rcw; }
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_chain[0], ctx->ev_chain[1]));
-    ctx->kernel_ms += ms;
-    ctx->kernel_launches += 1;
-    if (trace) fprintf(stderr, "[lnsfaid] line launch: %.3f ms, %zu codewords\n", ms, n_codewords);
-    return LNSFAID_OK;
+    return launch_decode_timed(ctx, k, &a, n_codewords, "line");
 }
 
 extern "C" int lnsfaid_decode_line_device(lnsfaid_ctx* ctx, const void* d_line, int32_t format, int32_t magnitude, size_t n_codewords,
@@ -2503,18 +2427,10 @@ static int burst_descriptors(lnsfaid_ctx* ctx, const uint32_t* shortened, int32_
 static int decode_burst_launch(lnsfaid_ctx* ctx, const void* d_line, int32_t format, int32_t magnitude, int32_t where, size_t n_codewords,
                                uint32_t* d_payload, uint32_t* d_bits, lnsfaid_line_stats* d_stats, uint32_t* d_short_ones)
 {
-    const int rm = use_msg_registers(ctx) ? 1 : 0;
-    const void* fn = lf_decode4b_func(ctx->hcfg.method, ctx->hcfg.ef, rm);
-    if (!fn) return LNSFAID_E_INVAL;
-    if (fn != ctx->checked_burst_fn) { /* as kernel_check: the En image must start at LDS offset 0 */
-        hipFuncAttributes at;
-        HIP_TRY(hipFuncGetAttributes(&at, fn));
-        if (at.sharedSizeBytes != 0) {
-            snprintf(g_hip_err, sizeof(g_hip_err), "burst decode kernel has %zu bytes of static LDS: its En image would not start at LDS offset 0",
-                     (size_t)at.sharedSizeBytes);
-            return LNSFAID_E_INTERNAL;
-        }
-        ctx->checked_burst_fn = fn;
+    LfInst k;
+    {
+        const int rc = kernel_check(ctx, LF_ENTRY_BURST, &k);
+        if (rc) return rc;
     }
     LfBurstArgs a;
     a.code = ctx->d_code; a.cfg = ctx->d_cfg;
@@ -2523,17 +2439,7 @@ static int decode_burst_launch(lnsfaid_ctx* ctx, const void* d_line, int32_t for
     a.stats = d_stats; a.short_ones = d_short_ones;
     a.desc = ctx->d_burst_desc;
     a.format = format; a.magnitude = magnitude; a.where = where; a.n_cw = (int32_t)n_codewords;
-    static const bool trace = getenv("LNSFAID_TRACE") != nullptr;
-    HIP_TRY(hipEventRecord(ctx->ev_chain[0], ctx->stream));
-    HIP_TRY(lf_launch_decode4b(ctx->hcfg.method, ctx->hcfg.ef, rm, &a, ctx->lds_bytes, ctx->stream));
-    HIP_TRY(hipEventRecord(ctx->ev_chain[1], ctx->stream));
-    { const int rcw = stream_wait(ctx); if (rcw) return rcw; }
-    float ms = 0.f;
-    HIP_TRY(hipEventElapsedTime(&ms, ctx->ev_chain[0], ctx->ev_chain[1]));
-    ctx->kernel_ms += ms;
-    ctx->kernel_launches += 1;
-    if (trace) fprintf(stderr, "[lnsfaid] burst launch: %.3f ms, %zu codewords\n", ms, n_codewords);
-    return LNSFAID_OK;
+    return launch_decode_timed(ctx, k, &a, n_codewords, "burst");
 }
 
 extern "C" int lnsfaid_decode_burst_device(lnsfaid_ctx* ctx, const void* d_line, int32_t format, int32_t magnitude, const uint32_t* shortened,

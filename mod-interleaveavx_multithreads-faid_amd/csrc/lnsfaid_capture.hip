@@ -18,6 +18,7 @@
 #include <stdint.h>
 
 #include "lnsfaid.h"
+#include "lnsfaid_launch.h"
 
 #define CAP_UNITS 8     /* loads a lane has in flight before the first use */
 #define CAP_CHUNK 1024u /* codewords per chunk of the rank kernel = its workgroup size */

@@ -27,6 +27,7 @@
 
 #include "lnsfaid.h"
 #include "lnsfaid_quantise.h"
+#include "lnsfaid_launch.h"
 
 #define DM_STREAM 0
 #define DM_GATHER 1

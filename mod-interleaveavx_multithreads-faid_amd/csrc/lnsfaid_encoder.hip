@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "lnsfaid_device.h"
+#include "lnsfaid_launch.h"
 
 #define ENC_T 256 /* threads per workgroup = circulant size */
 

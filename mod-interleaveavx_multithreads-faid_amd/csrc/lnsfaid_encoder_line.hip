@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "lnsfaid_device.h"
+#include "lnsfaid_launch.h"
 
 #define ENL_T 256                     /* threads per workgroup = circulant size */
 #define ENL_RAW_STRIDE 33             /* words per codeword of the raw image: column reads hit 32 banks */

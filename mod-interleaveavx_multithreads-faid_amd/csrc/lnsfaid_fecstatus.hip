@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "lnsfaid_device.h"
+#include "lnsfaid_launch.h"
 
 #define FS_WAVES 4   /* codewords in flight per workgroup */
 #define FS_UNITS 4   /* loads a lane has in flight per stream before the first use */

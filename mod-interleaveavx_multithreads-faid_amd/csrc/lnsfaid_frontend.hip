@@ -23,6 +23,7 @@
 
 #include "lnsfaid.h"
 #include "lnsfaid_quantise.h"
+#include "lnsfaid_launch.h"
 
 #define FE_RUN 32 /* symbols (QPSK: LLR pairs, 16-QAM: LLR quadruples) per thread */
 

@@ -12,12 +12,14 @@
  *   - the payload is the information words without the known ones, at the codeword's own payload offset; the corrected count runs
  *     against the shifted line words and skips the known range, whose decided ones are counted on their own (short_ones);
  *   - the descriptor lives in scalar registers and is read again in the epilogue: nothing of it is carried across the decode.
- * Everything between staging and output is the macro text of lnsfaid_rows4.h; no expanded line exists anywhere.
+ * Everything between staging and output is macro text (the per-codeword frame of lnsfaid_frame4.h, the loops of lnsfaid_rows4.h); no
+ * expanded line exists anywhere.
  */
 #include <hip/hip_runtime.h>
 
-#include "lnsfaid_rows4.h"
+#include "lnsfaid_frame4.h"
 #include "lnsfaid_burst.h"
+#include "lnsfaid_launch.h"
 
 /* the descriptor of this workgroup's codeword, uniform: through an opaque scalar copy of the address, so that the epilogue's read is
  * a read of its own and not the staging's values kept alive */
@@ -160,61 +162,13 @@ __device__ __forceinline__ void burst_counts(const LfBurstArgs& a, const LbRange
     ones = k;
 }
 
-#define LF4_ON_FRONT true
-#define LF4_CLEAN_STOPS(t) true
-#define LF4_ON_STOP(t)
-#define LF4_ON_PASS(t)
+#define LF4_RULE CW
 
 template <int METHOD, bool RM, bool EF2>
 __global__ __launch_bounds__(LF_T4, 2) void lnsfaid_decode4b_kernel(LfBurstArgs a)
 {
-    extern __shared__ __align__(16) unsigned char smem[];
-    CCode c = (CCode)a.code;
-    CCfg f = (CCfg)a.cfg;
-    const int tid = (int)threadIdx.x;
-    const int cw = (int)blockIdx.x;
-    const int N = c->n_var, K = c->k_info, nw = c->n_words, pw = c->p_words;
-    uint32_t* sHard0 = (uint32_t*)smem;
-    uint32_t* sHard2 = (uint32_t*)smem + nw;
-    uint32_t* sHard = (uint32_t*)(smem + lf_lds_off_hard(N));
-    uint32_t* sP = (uint32_t*)(smem + lf_lds_off_p(N, nw));
-    int* sStat = (int*)(smem + lf_lds_off_stat(N, nw, pw));
-    int* sRed = sStat + LNSFAID_GROUP;
-
-    const int max_iter = f->max_iter, max_bf = f->max_bf;
-    const int t_bf0 = max_iter + 1;
-    const int t_end = t_bf0 + max_bf;
-    if (tid == LNSFAID_GROUP) sRed[LF_ZERO_SLOT] = 0;
-
-    SwRow* g_rows = (SwRow*)(a.st_rows + (size_t)cw * (size_t)(c->nbr * LF_T));
-    LfLaneState ls = { 0, 0, 0, 0 };
-    SwRegs R;
-    if (RM) regs_clear(R);
-
-    LF4B_STAGE_INPUT()
-    LF_WG_SYNC();
-    int prog = 1;
-    bool in_bf = false;
-    bool parked = false;
-    uint32_t pA = 0, pB = 0;
-    {
-        LF4_LAYERED_LOOP()
-        LF4_ENTER_BF()
-    }
-    LF4_BF_LOOPS()
-    const bool clean = parked;
-
-    if (!clean && !in_bf) build_plane4<false>(c, sHard, 0, tid);
-    int unsat = 0;
-    if (!clean && a.stats) {
-        if (RM || syn_cache_fits(c->nbr)) {
-            SynCache sc;
-            syn_cache_load(a.code, c->nbr, tid, sc);
-            unsat = syndrome<LF_T4, false, true>(c, a.code, sP, tid, pA, pB, sRed, &sc);
-        } else {
-            unsat = syndrome<LF_T4, false>(c, a.code, sP, tid, pA, pB, sRed);
-        }
-    }
+    LF4_LOCALS()
+    LF4_CW_CORE(LF4B_STAGE_INPUT, a.stats)
     /* the lane number as the output sees it: opaque, as in lnsfaid_decode4l_kernel */
     int tid_o = tid;
     asm volatile("" : "+v"(tid_o));
@@ -246,20 +200,5 @@ __global__ __launch_bounds__(LF_T4, 2) void lnsfaid_decode4b_kernel(LfBurstArgs 
 /* the same set of instances as lf_decode4l_func */
 extern "C" const void* lf_decode4b_func(int method, int ef, int rm)
 {
-    if (method == 2 && ef == 2) return (const void*)lnsfaid_decode4b_kernel<2, false, true>;
-#define LF4B_FUNC(M) case M: return rm ? (const void*)lnsfaid_decode4b_kernel<M, true, false> : (const void*)lnsfaid_decode4b_kernel<M, false, false>;
-    switch (method) {
-    case 0: return (const void*)lnsfaid_decode4b_kernel<0, false, false>;
-        LF4B_FUNC(1) LF4B_FUNC(2) LF4B_FUNC(3) LF4B_FUNC(4) LF4B_FUNC(5)
-    default: return nullptr;
-    }
-#undef LF4B_FUNC
-}
-
-extern "C" hipError_t lf_launch_decode4b(int method, int ef, int rm, const LfBurstArgs* args, size_t lds_bytes, hipStream_t stream)
-{
-    const void* fn = lf_decode4b_func(method, ef, rm);
-    if (!fn) return hipErrorInvalidValue;
-    void* kargs[] = { (void*)args };
-    return hipLaunchKernel(fn, dim3((unsigned)args->n_cw), dim3(LF_T4), kargs, lds_bytes, stream);
+    LF4_INSTANCE_TABLE(lnsfaid_decode4b_kernel)
 }

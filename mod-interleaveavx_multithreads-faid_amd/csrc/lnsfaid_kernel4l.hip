@@ -13,12 +13,13 @@
  *   - the format is a kernel argument, uniform over the launch, branched on in staging and in the corrected count: one set of
  *     instances serves both formats;
  *   - the output is the payload, the plane only when asked for, and a record with the corrected count; no group records.
- * Everything between staging and output is the macro text of lnsfaid_rows4.h.
+ * Everything between staging and output is macro text: the per-codeword frame of lnsfaid_frame4.h, the loops of lnsfaid_rows4.h.
  */
 #include <hip/hip_runtime.h>
 
-#include "lnsfaid_rows4.h"
+#include "lnsfaid_frame4.h"
 #include "lnsfaid_line.h"
+#include "lnsfaid_launch.h"
 
 /* ---- staging from a line.  As LF4P_STAGE_INPUT: lane tid owns variable nodes 4 tid .. 4 tid + 3 of every block column, the loads
  * of a round of 23 columns are in flight together, and the four values go to their bytes of the interleaved En image (node n of a
@@ -130,61 +131,13 @@ __device__ __forceinline__ int line_corrected(const LfLineArgs& a, const uint32_
     return n;
 }
 
-#define LF4_ON_FRONT true
-#define LF4_CLEAN_STOPS(t) true
-#define LF4_ON_STOP(t)
-#define LF4_ON_PASS(t)
+#define LF4_RULE CW
 
 template <int METHOD, bool RM, bool EF2>
 __global__ __launch_bounds__(LF_T4, 2) void lnsfaid_decode4l_kernel(LfLineArgs a)
 {
-    extern __shared__ __align__(16) unsigned char smem[];
-    CCode c = (CCode)a.code;
-    CCfg f = (CCfg)a.cfg;
-    const int tid = (int)threadIdx.x;
-    const int cw = (int)blockIdx.x;
-    const int N = c->n_var, K = c->k_info, nw = c->n_words, pw = c->p_words;
-    uint32_t* sHard0 = (uint32_t*)smem;
-    uint32_t* sHard2 = (uint32_t*)smem + nw;
-    uint32_t* sHard = (uint32_t*)(smem + lf_lds_off_hard(N));
-    uint32_t* sP = (uint32_t*)(smem + lf_lds_off_p(N, nw));
-    int* sStat = (int*)(smem + lf_lds_off_stat(N, nw, pw));
-    int* sRed = sStat + LNSFAID_GROUP;
-
-    const int max_iter = f->max_iter, max_bf = f->max_bf;
-    const int t_bf0 = max_iter + 1;
-    const int t_end = t_bf0 + max_bf;
-    if (tid == LNSFAID_GROUP) sRed[LF_ZERO_SLOT] = 0;
-
-    SwRow* g_rows = (SwRow*)(a.st_rows + (size_t)cw * (size_t)(c->nbr * LF_T));
-    LfLaneState ls = { 0, 0, 0, 0 };
-    SwRegs R;
-    if (RM) regs_clear(R);
-
-    LF4L_STAGE_INPUT()
-    LF_WG_SYNC();
-    int prog = 1;
-    bool in_bf = false;
-    bool parked = false;
-    uint32_t pA = 0, pB = 0;
-    {
-        LF4_LAYERED_LOOP()
-        LF4_ENTER_BF()
-    }
-    LF4_BF_LOOPS()
-    const bool clean = parked;
-
-    if (!clean && !in_bf) build_plane4<false>(c, sHard, 0, tid);
-    int unsat = 0;
-    if (!clean && a.stats) {
-        if (RM || syn_cache_fits(c->nbr)) {
-            SynCache sc;
-            syn_cache_load(a.code, c->nbr, tid, sc);
-            unsat = syndrome<LF_T4, false, true>(c, a.code, sP, tid, pA, pB, sRed, &sc);
-        } else {
-            unsat = syndrome<LF_T4, false>(c, a.code, sP, tid, pA, pB, sRed);
-        }
-    }
+    LF4_LOCALS()
+    LF4_CW_CORE(LF4L_STAGE_INPUT, a.stats)
     /* the lane number as the output sees it: opaque, so that no address staging has computed from it (16 * tid) is kept alive -
      * spilled, with the messages in registers - through the whole decode for the stores below */
     int tid_o = tid;
@@ -208,20 +161,5 @@ __global__ __launch_bounds__(LF_T4, 2) void lnsfaid_decode4l_kernel(LfLineArgs a
 /* the same set of instances as lf_decode4p_func(.., per_codeword = 1) */
 extern "C" const void* lf_decode4l_func(int method, int ef, int rm)
 {
-    if (method == 2 && ef == 2) return (const void*)lnsfaid_decode4l_kernel<2, false, true>;
-#define LF4L_FUNC(M) case M: return rm ? (const void*)lnsfaid_decode4l_kernel<M, true, false> : (const void*)lnsfaid_decode4l_kernel<M, false, false>;
-    switch (method) {
-    case 0: return (const void*)lnsfaid_decode4l_kernel<0, false, false>;
-        LF4L_FUNC(1) LF4L_FUNC(2) LF4L_FUNC(3) LF4L_FUNC(4) LF4L_FUNC(5)
-    default: return nullptr;
-    }
-#undef LF4L_FUNC
-}
-
-extern "C" hipError_t lf_launch_decode4l(int method, int ef, int rm, const LfLineArgs* args, size_t lds_bytes, hipStream_t stream)
-{
-    const void* fn = lf_decode4l_func(method, ef, rm);
-    if (!fn) return hipErrorInvalidValue;
-    void* kargs[] = { (void*)args };
-    return hipLaunchKernel(fn, dim3((unsigned)args->n_cw), dim3(LF_T4), kargs, lds_bytes, stream);
+    LF4_INSTANCE_TABLE(lnsfaid_decode4l_kernel)
 }

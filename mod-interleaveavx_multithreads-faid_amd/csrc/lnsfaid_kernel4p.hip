@@ -12,11 +12,13 @@
  *   - the output is the hard-decision plane itself: sHard[i] bit b is decodedBits[32 i + b], so the 552 words of a 50G-PON
  *     codeword are stored as they are, 2 208 bytes (the int8 kernels expand every word into 32 bytes, 17 664).
  * They take the int8 kernels' argument structs and reinterpret fix_input / decoded, so the int8 kernels keep their instances,
- * names and instructions.  Everything between staging and output is the same macro text of lnsfaid_rows4.h.
+ * names and instructions.  Everything between staging and output is the same macro text: the kernel frames of
+ * lnsfaid_frame4.h around the loops of lnsfaid_rows4.h.
  */
 #include <hip/hip_runtime.h>
 
-#include "lnsfaid_rows4.h"
+#include "lnsfaid_frame4.h"
+#include "lnsfaid_launch.h"
 
 /* ---- staging from llr4, in the shape of LF4_STAGE_INPUT including its byte path for a buffer that is not dword aligned.  The
  * host refuses such device pointers, so that path does not run; it is kept because the register allocation of the whole kernel
@@ -98,249 +100,37 @@ __device__ __forceinline__ void write_bits(const uint32_t* sHard, uint32_t* g_ou
     }
 }
 
-/* ==== group rule: lnsfaid_kernel4.hip with packed staging and output ==== */
-#define LF4_ON_FRONT prog >= kmax
-#define LF4_CLEAN_STOPS(t) prog >= kmax && !group_passed(a.live, g, prog, t)
-#define LF4_ON_STOP(t) if (RM && prog >= 2) regs_store(R, g_rows, c->nbr, t);
-#define LF4_ON_PASS(t) publish_pass(a.live, cw, prog, t);
+/* ==== group rule: lnsfaid_kernel4.hip's frame with packed staging and output ==== */
+#define LF4_RULE GROUP
 
 template <int METHOD, bool RM, bool EF2>
 __global__ __launch_bounds__(LF_T4, 2) void lnsfaid_decode4p_kernel(LfKernelArgs a)
 {
-    extern __shared__ __align__(16) unsigned char smem[];
-    CCode c = (CCode)a.code;
-    CCfg f = (CCfg)a.cfg;
-    const int tid = (int)threadIdx.x;
-    const int cw = (int)blockIdx.x;
-    const int N = c->n_var, M = c->n_check, K = c->k_info, nw = c->n_words, pw = c->p_words;
-    uint32_t* sHard0 = (uint32_t*)smem;
-    uint32_t* sHard2 = (uint32_t*)smem + nw;
-    uint32_t* sHard = (uint32_t*)(smem + lf_lds_off_hard(N));
-    uint32_t* sP = (uint32_t*)(smem + lf_lds_off_p(N, nw));
-    int* sStat = (int*)(smem + lf_lds_off_stat(N, nw, pw));
-    int* sRed = sStat + LNSFAID_GROUP;
-
-    const int max_iter = f->max_iter, max_bf = f->max_bf;
-    const int t_bf0 = max_iter + 1;
-    const int t_end = t_bf0 + max_bf;
-
-    const int g = cw >> 5, lane_in_group = cw & 31;
-    const int sv = a.status_cur ? a.status_cur[g * LNSFAID_GROUP + (tid & 31)] : 0;
-    const int my_status = __builtin_amdgcn_readlane(sv, lane_in_group);
-    if (my_status & LF_DONE) {
-        if (tid == 0) a.status_next[cw] = my_status;
-        return;
-    }
-    if (tid == LNSFAID_GROUP) sRed[LF_ZERO_SLOT] = 0;
-    int kmax;
-    {
-        int v = sv & LF_PROG_MASK;
-        v = imax(v, __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false));
-        v = imax(v, __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false));
-        v = imax(v, __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false));
-        v = imax(v, __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false));
-        v = imax(v, __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false));
-        kmax = __builtin_amdgcn_readlane(v, 31);
-    }
-    const int all_same = __ballot(sv != my_status) == 0ull;
-    LF_WG_SYNC();
-    int prog = my_status & LF_PROG_MASK;
-
-    uint32_t* g_en = (uint32_t*)(a.st_en + (size_t)cw * (size_t)N);
-    SwRow* g_rows = (SwRow*)(a.st_rows + (size_t)cw * (size_t)(c->nbr * LF_T));
-    uint32_t* g_bits = a.st_bits + (size_t)cw * (size_t)(3 * nw);
-    uint32_t* g_out = (uint32_t*)a.decoded + (size_t)cw * (size_t)nw; /* packed decisions */
-
-    if (prog != 0 && prog == kmax && !all_same) {
-        if (tid == 0) { a.status_next[cw] = my_status; atomicAdd(a.remaining, 1u); }
-        return;
-    }
-    if (my_status != 0 && all_same) {
-        if (tid == 0) {
-            a.status_next[cw] = my_status | LF_DONE;
-            if (a.stats && lane_in_group == 0) {
-                lnsfaid_group_stats st;
-                st.iterations = prog <= max_iter ? prog - 1 : max_iter;
-                st.bf_iterations = prog <= max_iter ? 0 : prog - t_bf0;
-                a.stats[g] = st;
-            }
-        }
-        return;
-    }
-
-    bool in_bf = max_bf > 0 && prog >= t_bf0 && prog != 0;
-    LfLaneState ls = { 0, 0, 0, 0 };
-    SwRegs R;
-    if (RM) regs_clear(R);
-
-    if (prog == 0) {
-        LF4P_STAGE_INPUT()
-        LF_WG_SYNC();
-        prog = 1;
-    } else if (!in_bf) {
-        copy_in<23>((uint32_t*)smem, g_en, N >> 2, tid);
-        if (RM && prog >= 2) regs_load(R, g_rows, c->nbr, tid);
-        LF_WG_SYNC();
-    } else {
-        copy_in<9>(sHard, g_bits, nw, tid);
-        copy_in<9>(sHard0, g_bits + nw, nw, tid);
-        copy_in<9>(sHard2, g_bits + 2 * nw, nw, tid);
-        ls = a.st_lane[cw];
-        LF_WG_SYNC();
-    }
-
-    bool parked = false;
-    uint32_t pA = 0, pB = 0;
-    if (!in_bf) {
-        LF4_LAYERED_LOOP()
-        LF4_ENTER_BF()
-    }
-    LF4_BF_LOOPS()
-
-    const bool finished = prog >= t_end;
-    if (finished) {
-        if (!in_bf) build_plane4<false>(c, sHard, 0, tid);
-        write_bits(sHard, g_out, N, tid);
-        if (tid == 0) {
-            a.status_next[cw] = prog | LF_DONE;
-            if (a.stats && lane_in_group == 0) {
-                lnsfaid_group_stats st;
-                st.iterations = prog <= max_iter ? prog - 1 : max_iter;
-                st.bf_iterations = prog <= max_iter ? 0 : prog - t_bf0;
-                a.stats[g] = st;
-            }
-        }
-    } else {
-        /* parking: state to HBM, and the plane as the speculative output for the case that the group stops here */
-        if (!in_bf) {
-            copy_out<23>(g_en, (const uint32_t*)smem, N >> 2, tid);
-        } else {
-            copy_out<9>(g_bits, sHard, nw, tid);
-            copy_out<9>(g_bits + nw, sHard0, nw, tid);
-            copy_out<9>(g_bits + 2 * nw, sHard2, nw, tid);
-            if (tid == 0) a.st_lane[cw] = ls;
-        }
-        write_bits(sHard, g_out, N, tid);
-        if (tid == 0) { a.status_next[cw] = prog; atomicAdd(a.remaining, 1u); }
-    }
+    LF4_GROUP_FRAME(LF4P_STAGE_INPUT, write_bits, uint32_t, nw)
 }
 
-#undef LF4_ON_FRONT
-#undef LF4_CLEAN_STOPS
-#undef LF4_ON_STOP
-#undef LF4_ON_PASS
-
-/* ==== per-codeword rule: lnsfaid_kernel4cw.hip with packed staging and output ==== */
-#define LF4_ON_FRONT true
-#define LF4_CLEAN_STOPS(t) true
-#define LF4_ON_STOP(t)
-#define LF4_ON_PASS(t)
+/* ==== per-codeword rule: lnsfaid_kernel4cw.hip's frame with packed staging and output ==== */
+#undef LF4_RULE
+#define LF4_RULE CW
 
 template <int METHOD, bool RM, bool EF2>
 __global__ __launch_bounds__(LF_T4, 2) void lnsfaid_decode4pcw_kernel(LfCwArgs a)
 {
-    extern __shared__ __align__(16) unsigned char smem[];
-    CCode c = (CCode)a.code;
-    CCfg f = (CCfg)a.cfg;
-    const int tid = (int)threadIdx.x;
-    const int cw = (int)blockIdx.x;
-    const int N = c->n_var, M = c->n_check, K = c->k_info, nw = c->n_words, pw = c->p_words;
-    uint32_t* sHard0 = (uint32_t*)smem;
-    uint32_t* sHard2 = (uint32_t*)smem + nw;
-    uint32_t* sHard = (uint32_t*)(smem + lf_lds_off_hard(N));
-    uint32_t* sP = (uint32_t*)(smem + lf_lds_off_p(N, nw));
-    int* sStat = (int*)(smem + lf_lds_off_stat(N, nw, pw));
-    int* sRed = sStat + LNSFAID_GROUP;
-
-    const int max_iter = f->max_iter, max_bf = f->max_bf;
-    const int t_bf0 = max_iter + 1;
-    const int t_end = t_bf0 + max_bf;
+    LF4_LOCALS()
     const int g = cw >> 5, lane_in_group = cw & 31;
-    if (tid == LNSFAID_GROUP) sRed[LF_ZERO_SLOT] = 0;
-
-    SwRow* g_rows = (SwRow*)(a.st_rows + (size_t)cw * (size_t)(c->nbr * LF_T));
+    LF4_CW_CORE(LF4P_STAGE_INPUT, a.cw_stats)
     uint32_t* g_out = (uint32_t*)a.decoded + (size_t)cw * (size_t)nw; /* packed decisions */
-    LfLaneState ls = { 0, 0, 0, 0 };
-    SwRegs R;
-    if (RM) regs_clear(R);
-
-    LF4P_STAGE_INPUT()
-    LF_WG_SYNC();
-    int prog = 1;
-    bool in_bf = false;
-    bool parked = false;
-    uint32_t pA = 0, pB = 0;
-    {
-        LF4_LAYERED_LOOP()
-        LF4_ENTER_BF()
-    }
-    LF4_BF_LOOPS()
-    const bool clean = parked;
-
-    if (!clean && !in_bf) build_plane4<false>(c, sHard, 0, tid);
-    int unsat = 0;
-    if (!clean && a.cw_stats) {
-        if (RM || syn_cache_fits(c->nbr)) {
-            SynCache sc;
-            syn_cache_load(a.code, c->nbr, tid, sc);
-            unsat = syndrome<LF_T4, false, true>(c, a.code, sP, tid, pA, pB, sRed, &sc);
-        } else {
-            unsat = syndrome<LF_T4, false>(c, a.code, sP, tid, pA, pB, sRed);
-        }
-    }
     write_bits(sHard, g_out, N, tid);
-    if (tid == 0) {
-        const int it = prog <= max_iter ? prog - 1 : max_iter;
-        const int bf = prog <= max_iter ? 0 : prog - t_bf0;
-        if (a.cw_stats) {
-            lnsfaid_codeword_stats st;
-            st.iterations = it; st.bf_iterations = bf; st.unsatisfied = unsat;
-            a.cw_stats[cw] = st;
-        }
-        if (a.stats) {
-            atomicMax(&a.stats[g].iterations, it);
-            atomicMax(&a.stats[g].bf_iterations, bf);
-        }
-    }
+    LF4_CW_RECORDS()
 }
 
 /* the packed instances: the same set as lf_decode4_func / lf_decode4cw_func */
 extern "C" const void* lf_decode4p_func(int method, int ef, int rm, int per_codeword)
 {
     if (per_codeword) {
-        if (method == 2 && ef == 2) return (const void*)lnsfaid_decode4pcw_kernel<2, false, true>;
-#define LF4PCW_FUNC(M) case M: return rm ? (const void*)lnsfaid_decode4pcw_kernel<M, true, false> : (const void*)lnsfaid_decode4pcw_kernel<M, false, false>;
-        switch (method) {
-        case 0: return (const void*)lnsfaid_decode4pcw_kernel<0, false, false>;
-            LF4PCW_FUNC(1) LF4PCW_FUNC(2) LF4PCW_FUNC(3) LF4PCW_FUNC(4) LF4PCW_FUNC(5)
-        default: return nullptr;
-        }
-#undef LF4PCW_FUNC
+        LF4_INSTANCE_TABLE(lnsfaid_decode4pcw_kernel)
     }
-    if (method == 2 && ef == 2) return (const void*)lnsfaid_decode4p_kernel<2, false, true>;
-#define LF4P_FUNC(M) case M: return rm ? (const void*)lnsfaid_decode4p_kernel<M, true, false> : (const void*)lnsfaid_decode4p_kernel<M, false, false>;
-    switch (method) {
-    case 0: return (const void*)lnsfaid_decode4p_kernel<0, false, false>;
-        LF4P_FUNC(1) LF4P_FUNC(2) LF4P_FUNC(3) LF4P_FUNC(4) LF4P_FUNC(5)
-    default: return nullptr;
-    }
-#undef LF4P_FUNC
-}
-
-extern "C" hipError_t lf_launch_decode4p(int method, int ef, int rm, const LfKernelArgs* args, size_t lds_bytes, hipStream_t stream)
-{
-    const void* fn = lf_decode4p_func(method, ef, rm, 0);
-    if (!fn) return hipErrorInvalidValue;
-    void* kargs[] = { (void*)args };
-    return hipLaunchKernel(fn, dim3((unsigned)args->n_cw), dim3(LF_T4), kargs, lds_bytes, stream);
-}
-
-extern "C" hipError_t lf_launch_decode4pcw(int method, int ef, int rm, const LfCwArgs* args, size_t lds_bytes, hipStream_t stream)
-{
-    const void* fn = lf_decode4p_func(method, ef, rm, 1);
-    if (!fn) return hipErrorInvalidValue;
-    void* kargs[] = { (void*)args };
-    return hipLaunchKernel(fn, dim3((unsigned)args->n_cw), dim3(LF_T4), kargs, lds_bytes, stream);
+    LF4_INSTANCE_TABLE(lnsfaid_decode4p_kernel)
 }
 
 /* ==== configurations without a packed decoder (two-rows kernel, two waves per codeword): llr4 -> int8 in front of the int8

@@ -30,6 +30,7 @@ __device__ __forceinline__ void lf5_barrier()
 }
 
 #include "lnsfaid_rows4.h"
+#include "lnsfaid_launch.h"
 
 /* exchange area of the two waves: the hard-decision plane's LDS, dead between the syndrome stage and the next one; slot k of
  * lane i at word k * 64 + i */
@@ -409,11 +410,3 @@ extern "C" const void* lf_decode5_func(int method)
     }
 }
 extern "C" int lf_decode5_threads(void) { return 2 * LF_T4; }
-
-extern "C" hipError_t lf_launch_decode5(int method, const LfKernelArgs* args, size_t lds_bytes, hipStream_t stream)
-{
-    const void* fn = lf_decode5_func(method);
-    if (!fn) return hipErrorInvalidValue;
-    void* kargs[] = { (void*)args };
-    return hipLaunchKernel(fn, dim3((unsigned)args->n_cw), dim3(2 * LF_T4), kargs, lds_bytes, stream);
-}

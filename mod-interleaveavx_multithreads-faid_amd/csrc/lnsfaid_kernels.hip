@@ -41,6 +41,7 @@
 
 #include "lnsfaid_device.h"
 #include "lnsfaid_phases.h"
+#include "lnsfaid_launch.h"
 
 /* DecodeMethods whose layered loop is Decode_OMS's: 1 (alone), 3 (+ plain bit flipping), 4 (+ DTBF) */
 #define LF_OMS(M) ((M) == 1 || (M) == 3 || (M) == 4)
@@ -776,15 +777,6 @@ extern "C" const void* lf_decode_func(int method, int uniform_w)
     }
 }
 extern "C" int lf_decode_threads(void) { return LF_T; }
-
-extern "C" hipError_t lf_launch_decode(int method, int uniform_w, const LfKernelArgs* args, size_t lds_bytes,
-                                       hipStream_t stream)
-{
-    const void* fn = lf_decode_func(method, uniform_w);
-    if (!fn) return hipErrorInvalidValue;
-    void* kargs[] = { (void*)args };
-    return hipLaunchKernel(fn, dim3((unsigned)args->n_cw), dim3(LF_T), kargs, lds_bytes, stream);
-}
 
 extern "C" hipError_t lf_launch_count_errors(const int8_t* decoded, const int8_t* input_bits, int n_var, int k_info,
                                              size_t n_cw, unsigned long long* out, hipStream_t stream)

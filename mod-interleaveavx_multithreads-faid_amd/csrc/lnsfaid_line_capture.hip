@@ -25,6 +25,7 @@
 #include <stdint.h>
 
 #include "lnsfaid_device.h"
+#include "lnsfaid_launch.h"
 
 #define LC_WAVES 4      /* codewords in flight per workgroup of the flag kernel */
 #define LC_UNITS 4      /* loads a lane has in flight per stream before the first use */

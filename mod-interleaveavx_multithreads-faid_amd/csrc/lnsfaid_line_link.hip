@@ -21,6 +21,7 @@
 #include <stdint.h>
 
 #include "lnsfaid.h"
+#include "lnsfaid_launch.h"
 
 #define LK_T 256       /* threads per workgroup of the payload and channel kernels */
 #define LK_CW 32u      /* codewords per workgroup */

@@ -30,6 +30,7 @@
 #include <stdint.h>
 
 #include "lnsfaid.h"
+#include "lnsfaid_launch.h"
 
 #define LM_WAVES 4        /* codewords in flight per workgroup */
 #define LM_MAX_WG 2048u   /* 8 192 waves: every SIMD of the device full once, then the waves stride */

@@ -35,6 +35,7 @@
 #include <stdint.h>
 
 #include "lnsfaid.h"
+#include "lnsfaid_launch.h"
 
 #define LS_T 256   /* threads per workgroup */
 #define LS_CW 32u  /* codewords per workgroup */

@@ -20,6 +20,7 @@
 #include <stdint.h>
 
 #include "lnsfaid.h"
+#include "lnsfaid_launch.h"
 
 #define PF_UNITS 4 /* loads of 16 bytes a lane has in flight before the first use */
 
