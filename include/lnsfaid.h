@@ -497,6 +497,79 @@ int lnsfaid_burst_to_llr4(const lnsfaid_code* code, const void* line, int32_t fo
 int lnsfaid_burst_words(const lnsfaid_code* code, const uint32_t* shortened, size_t n_codewords, uint64_t* line_bits,
                         uint64_t* payload_bits);
 
+/* ---- burst-format link ------------------------------------------------------------------------------------
+ * The four link calls - payload source, BSC, soft channel, counters - on the burst formats above, so that
+ * lnsfaid_burst_payload_random_device -> lnsfaid_encode_burst_device -> channel -> lnsfaid_decode_burst_device ->
+ * lnsfaid_burst_count_errors_device runs on the device and only counters leave it: the frame error rate of a burst whose last
+ * codeword is shortened by S, at a given input BER or Eb/N0.  `shortened` (a host pointer in every form, NULL = all zero,
+ * S_c % 32 == 0, 0 <= S_c <= K - 32) and `where` follow the rules of the burst-format section; N, K, L as there.
+ *
+ * One definition: draws are indexed by MOTHER position.  The generator is the link's, unchanged: mix64, cwkey(key, C, d),
+ * draw(key, C, d, q), d = 1 payload, 2 BSC, 3 soft; C = first_codeword + i, wrapping.  A burst codeword C with known range
+ * [k0, k0 + S_c) uses, for the mother position k of each transmitted position, exactly the draw the line call uses for position k of
+ * codeword C: draw q = k / 2, the low half for even k and the high half for odd k.  S_c is a multiple of 32, so a line word is always
+ * 16 whole draws: with k0w = k0 / 32 and Sw = S_c / 32, word wl of the burst codeword is mother word wi = wl + (wl >= k0w ? Sw : 0), and
+ * mother word wi outside the known words is burst word wl = wi - (wi >= k0w + Sw ? Sw : 0).  Exact consequences:
+ *   1. Expand, run, drop.  Expand the burst line with anything in the known range, run lnsfaid_line_bsc_* / lnsfaid_line_soft_*, drop
+ *      the known words: the burst channel gives the same bytes.  flips counts transmitted positions only, never the known range: it is
+ *      the line call's flips minus what that call counted inside the known words.
+ *   2. Payload.  The burst payload of codeword C is lnsfaid_line_payload_random_host's payload of C with the known words dropped.
+ *   3. No shortening.  With shortened == NULL or all zero every output, counter and total is byte for byte that of the corresponding
+ *      lnsfaid_line_* call.
+ *   4. Split invariance.  A run cut into calls of any size gives the bytes of the one-shot run: first_codeword is advanced and
+ *      `shortened` sliced accordingly; burst offsets restart per call, and concatenation restores the stream.  The same holds for a
+ *      run dealt to ranks.
+ *   5. Common random numbers.  A sweep over S on one key sees the same noise on every position that survives.
+ * The error-propagation channel has no burst form: its chain has to decide what it does across the gap.
+ *
+ * Formats.  payload and sent are burst payloads ((K - S_c) / 32 words per codeword, back to back; sent == NULL is the all-zero
+ * payload).  Lines are burst lines: (L - S_c) / 32 words (LNSFAID_LINE_HARD), (L - S_c) / 2 bytes (LNSFAID_LINE_LLR4).  Input word u of
+ * the soft channel, counted over the whole burst line, is output bytes 16 u .. 16 u + 15, as on a line.
+ *   lnsfaid_burst_bsc_*   LNSFAID_LINE_HARD burst lines in and out; line_out == line_in is allowed (in place), any other overlap is
+ *                         undefined.  threshold as lnsfaid_line_bsc_*: 0 copies.
+ *   lnsfaid_burst_soft_*  a HARD burst line in, an LLR4 burst line out; table, levels and the rule of flips as lnsfaid_line_soft_*; the
+ *                         two byte ranges must not overlap.
+ *   flips, total_flips    as in the line calls: optional uint32_t [n_codewords] (the _device forms: a device pointer) and an optional
+ *                         host uint64_t that is ADDED to.  The pre-FEC BER of a run is total_flips over the line_bits of
+ *                         lnsfaid_burst_words.
+ * Counters.  errors, fec and vs_sent are the words of lnsfaid_line_count_errors_* with one change, stated by the burst-format
+ * section itself: a receiver treats short_ones > 0 like unsatisfied > 0.  With w = the bits of a codeword's burst payload that differ
+ * from sent and failed = unsatisfied > 0 || short_ones > 0:  fec[1] counts failed codewords, fec[2] those with !failed and
+ * corrected > 0, fec[3] sums corrected over the codewords that are not failed, vs_sent[2] counts w > 0 && !failed, vs_sent[3]
+ * w == 0 && failed; every other word is unchanged.  stats and short_ones are what lnsfaid_decode_burst* returned (the _device form:
+ * device pointers); short_ones == NULL means zeros; fec or vs_sent with stats == NULL is LNSFAID_E_INVAL.  Each set is ADDED to and
+ * is four words, so lnsfaid_allreduce_counters sums it unchanged.  The counters need no `where`: a burst payload is walked by its
+ * lengths alone.  The denominators of a BER come from lnsfaid_burst_words.
+ * Rules: those of the link section plus the burst-format section.  n_codewords 0 is a no-op, up to 32 * max_groups (device forms);
+ * device pointers, optional ones included, 4-byte aligned; a bad `shortened` entry or a bad `where` is LNSFAID_E_INVAL, as are a NULL
+ * context or code, a NULL required buffer, a table that decreases, and overlapping ranges of the soft channel.  A refused call writes
+ * nothing and adds nothing.  The device forms queue on the context's stream and return when their host outputs are complete; their
+ * accumulators are the link's, their descriptors the burst calls'.  They do not depend on the decoder configuration.  On the GPU only
+ * the built-in code's circulant size is served, as for the burst calls.  The host forms need no context and no GPU, take pointers of
+ * any alignment, have no limit on n_codewords, and are the definition of what the device forms return. */
+int lnsfaid_burst_payload_random_device(lnsfaid_ctx* ctx, uint64_t key, uint64_t first_codeword, const uint32_t* shortened, int32_t where,
+                                        size_t n_codewords, uint32_t* d_payload);
+int lnsfaid_burst_payload_random_host(const lnsfaid_code* code, uint64_t key, uint64_t first_codeword, const uint32_t* shortened,
+                                      int32_t where, size_t n_codewords, uint32_t* payload);
+int lnsfaid_burst_bsc_device(lnsfaid_ctx* ctx, const uint32_t* d_line_in, const uint32_t* shortened, int32_t where, size_t n_codewords,
+                             uint64_t key, uint64_t first_codeword, uint32_t threshold, uint32_t* d_line_out, uint32_t* d_flips,
+                             uint64_t* total_flips);
+int lnsfaid_burst_bsc_host(const lnsfaid_code* code, const uint32_t* line_in, const uint32_t* shortened, int32_t where, size_t n_codewords,
+                           uint64_t key, uint64_t first_codeword, uint32_t threshold, uint32_t* line_out, uint32_t* flips,
+                           uint64_t* total_flips);
+int lnsfaid_burst_soft_device(lnsfaid_ctx* ctx, const uint32_t* d_line_in, const uint32_t* shortened, int32_t where, size_t n_codewords,
+                              uint64_t key, uint64_t first_codeword, const uint32_t table[14], uint8_t* d_llr4_out, uint32_t* d_flips,
+                              uint64_t* total_flips);
+int lnsfaid_burst_soft_host(const lnsfaid_code* code, const uint32_t* line_in, const uint32_t* shortened, int32_t where, size_t n_codewords,
+                            uint64_t key, uint64_t first_codeword, const uint32_t table[14], uint8_t* llr4_out, uint32_t* flips,
+                            uint64_t* total_flips);
+int lnsfaid_burst_count_errors_device(lnsfaid_ctx* ctx, const uint32_t* d_payload, const uint32_t* d_sent, const lnsfaid_line_stats* d_stats,
+                                      const uint32_t* d_short_ones, const uint32_t* shortened, size_t n_codewords, uint64_t errors[4],
+                                      uint64_t fec[4], uint64_t vs_sent[4]);
+int lnsfaid_burst_count_errors_host(const lnsfaid_code* code, const uint32_t* payload, const uint32_t* sent, const lnsfaid_line_stats* stats,
+                                    const uint32_t* short_ones, const uint32_t* shortened, size_t n_codewords, uint64_t errors[4],
+                                    uint64_t fec[4], uint64_t vs_sent[4]);
+
 /* ---- line-format failure capture ---------------------------------------------------------------------------
  * The codewords of a line call that fail, as ordered, compact records: what the decoder did with them.  (key, global codeword number)
  * reproduces payload, codeword and every channel draw on the host (the link's generators are counter-based); the records hold what

@@ -22,6 +22,7 @@
 #include "lnsfaid_quantise.h"
 #include "lnsfaid_swar.h" /* sw_nms_fits / sw_nms_tables (host side) */
 #include "lnsfaid_launch.h" /* what the kernel files export */
+#include "lnsfaid_burst_link.h" /* and lnsfaid_burst_link.hip, in a header of its own */
 
 #include <atomic>
 #include <chrono>
@@ -2664,6 +2665,114 @@ extern "C" int lnsfaid_line_markov_device(lnsfaid_ctx* ctx, const uint32_t* d_li
     if (rc) return rc;
     if (total_flips) *total_flips += ctx->h_link_acc[12];
     if (total_runs) *total_runs += ctx->h_link_acc[13];
+    return LNSFAID_OK;
+}
+
+/* ---- burst-format link (include/lnsfaid.h "burst-format link", DESIGN.md 3.22, lnsfaid_burst_link.hip; host forms in
+ * lnsfaid_tables.c) ----
+ * The link's rules and accumulators, the burst calls' descriptors: every refusal comes before the descriptors are uploaded or follows
+ * from their totals, so a refused call has launched nothing. */
+extern "C" int lnsfaid_burst_payload_random_device(lnsfaid_ctx* ctx, uint64_t key, uint64_t first_codeword, const uint32_t* shortened,
+                                                   int32_t where, size_t n_codewords, uint32_t* d_payload)
+{
+    int rc = line_link_rules(ctx, n_codewords);
+    if (rc < 0) return rc;
+    if (where != LNSFAID_SHORTEN_TAIL && where != LNSFAID_SHORTEN_HEAD) return LNSFAID_E_INVAL;
+    if (rc) return LNSFAID_OK;
+    if (!d_payload || !dword_aligned(d_payload)) return LNSFAID_E_INVAL;
+    size_t lu, pw;
+    rc = burst_descriptors(ctx, shortened, where, n_codewords, &lu, &pw);
+    if (rc) return rc;
+    HIP_TRY(lf_launch_burst_payload(d_payload, ctx->d_burst_desc, where, n_codewords, (uint32_t)ctx->k_info / 32u, key, first_codeword,
+                                    ctx->stream));
+    return stream_wait(ctx);
+}
+
+extern "C" int lnsfaid_burst_bsc_device(lnsfaid_ctx* ctx, const uint32_t* d_line_in, const uint32_t* shortened, int32_t where,
+                                        size_t n_codewords, uint64_t key, uint64_t first_codeword, uint32_t threshold, uint32_t* d_line_out,
+                                        uint32_t* d_flips, uint64_t* total_flips)
+{
+    int rc = line_link_rules(ctx, n_codewords);
+    if (rc < 0) return rc;
+    if (where != LNSFAID_SHORTEN_TAIL && where != LNSFAID_SHORTEN_HEAD) return LNSFAID_E_INVAL;
+    if (rc) return LNSFAID_OK;
+    if (!d_line_in || !d_line_out) return LNSFAID_E_INVAL;
+    if (!dword_aligned(d_line_in) || !dword_aligned(d_line_out) || !dword_aligned(d_flips)) return LNSFAID_E_INVAL;
+    size_t lu, pw;
+    rc = burst_descriptors(ctx, shortened, where, n_codewords, &lu, &pw);
+    if (rc) return rc;
+    rc = ensure_link_acc(ctx);
+    if (rc) return rc;
+    unsigned long long* d_total = ctx->d_link_acc + 12;
+    HIP_TRY(hipMemsetAsync(d_total, 0, sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(lf_launch_burst_bsc(d_line_in, d_line_out, ctx->d_burst_desc, where, n_codewords,
+                                (uint32_t)(ctx->n_var - ctx->hcode.puncture_tail) / 32u, (uint32_t)ctx->k_info / 32u, key, first_codeword,
+                                threshold, d_flips, d_total, ctx->stream));
+    if (total_flips) HIP_TRY(hipMemcpyAsync(ctx->h_link_acc + 12, d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    rc = stream_wait(ctx);
+    if (rc) return rc;
+    if (total_flips) *total_flips += ctx->h_link_acc[12];
+    return LNSFAID_OK;
+}
+
+extern "C" int lnsfaid_burst_soft_device(lnsfaid_ctx* ctx, const uint32_t* d_line_in, const uint32_t* shortened, int32_t where,
+                                         size_t n_codewords, uint64_t key, uint64_t first_codeword, const uint32_t table[14],
+                                         uint8_t* d_llr4_out, uint32_t* d_flips, uint64_t* total_flips)
+{
+    int rc = line_link_rules(ctx, n_codewords);
+    if (rc < 0) return rc;
+    if (where != LNSFAID_SHORTEN_TAIL && where != LNSFAID_SHORTEN_HEAD) return LNSFAID_E_INVAL;
+    if (rc) return LNSFAID_OK;
+    if (!d_line_in || !d_llr4_out || !table) return LNSFAID_E_INVAL;
+    if (!dword_aligned(d_line_in) || !dword_aligned(d_llr4_out) || !dword_aligned(d_flips)) return LNSFAID_E_INVAL;
+    for (int i = 1; i < 14; ++i)
+        if (table[i] < table[i - 1]) return LNSFAID_E_INVAL;
+    size_t lu, pw;
+    rc = burst_descriptors(ctx, shortened, where, n_codewords, &lu, &pw);
+    if (rc) return rc;
+    const uintptr_t a = (uintptr_t)d_line_in, b = (uintptr_t)d_llr4_out; /* four times the input: no overlap can be right */
+    if (a < b + lu * 16u && b < a + lu * 4u) {
+        (void)stream_wait(ctx); /* the descriptors' copy: the pinned array is free again for the next call */
+        return LNSFAID_E_INVAL;
+    }
+    rc = ensure_link_acc(ctx);
+    if (rc) return rc;
+    unsigned long long* d_total = ctx->d_link_acc + 12;
+    HIP_TRY(hipMemsetAsync(d_total, 0, sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(lf_launch_burst_soft(d_line_in, d_llr4_out, ctx->d_burst_desc, where, n_codewords,
+                                 (uint32_t)(ctx->n_var - ctx->hcode.puncture_tail) / 32u, (uint32_t)ctx->k_info / 32u, key, first_codeword,
+                                 table, d_flips, d_total, ctx->stream));
+    if (total_flips) HIP_TRY(hipMemcpyAsync(ctx->h_link_acc + 12, d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    rc = stream_wait(ctx);
+    if (rc) return rc;
+    if (total_flips) *total_flips += ctx->h_link_acc[12];
+    return LNSFAID_OK;
+}
+
+extern "C" int lnsfaid_burst_count_errors_device(lnsfaid_ctx* ctx, const uint32_t* d_payload, const uint32_t* d_sent,
+                                                 const lnsfaid_line_stats* d_stats, const uint32_t* d_short_ones, const uint32_t* shortened,
+                                                 size_t n_codewords, uint64_t errors[4], uint64_t fec[4], uint64_t vs_sent[4])
+{
+    int rc = line_link_rules(ctx, n_codewords);
+    if (rc) return rc < 0 ? rc : LNSFAID_OK;
+    if (!d_payload || ((fec || vs_sent) && !d_stats)) return LNSFAID_E_INVAL;
+    if (!dword_aligned(d_payload) || !dword_aligned(d_sent) || !dword_aligned(d_stats) || !dword_aligned(d_short_ones)) return LNSFAID_E_INVAL;
+    size_t lu, pw;
+    rc = burst_descriptors(ctx, shortened, LNSFAID_SHORTEN_TAIL, n_codewords, &lu, &pw); /* pay_off and s_words do not depend on `where` */
+    if (rc) return rc;
+    rc = ensure_link_acc(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(ctx->d_link_acc, 0, 12 * sizeof(unsigned long long), ctx->stream));
+    HIP_TRY(lf_launch_burst_count(d_payload, d_sent, d_stats, d_short_ones, ctx->d_burst_desc, n_codewords, (uint32_t)ctx->k_info / 32u,
+                                  ctx->d_link_acc, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->h_link_acc, ctx->d_link_acc, 12 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    rc = stream_wait(ctx);
+    if (rc) return rc;
+    for (int i = 0; i < 4; ++i) {
+        if (errors) errors[i] += ctx->h_link_acc[i];
+        if (fec) fec[i] += ctx->h_link_acc[4 + i];
+        if (vs_sent) vs_sent[i] += ctx->h_link_acc[8 + i];
+    }
     return LNSFAID_OK;
 }
 

@@ -754,6 +754,166 @@ int lnsfaid_encode_burst_host(const lnsfaid_code* code, const uint8_t* circ, siz
     return rc;
 }
 
+/* ---- burst-format link, host forms (include/lnsfaid.h "burst-format link") ----
+ * The definition of what the lnsfaid_burst_*_device link calls return.  Every draw is indexed by the MOTHER position: transmitted word
+ * wl of a codeword with known words [k0w, k0w + Sw) is mother word wi = wl + (wl >= k0w ? Sw : 0), and uses the draws 16 wi .. 16 wi + 15
+ * that lnsfaid_line_*_host uses for word wi of the same global codeword.  Own loops over the transmitted words, no expanded image;
+ * words are read and written byte by byte, so host pointers of any alignment do. */
+static int burst_link_rules(const lnsfaid_code* code, const uint32_t* shortened, int32_t where, size_t n_codewords, uint64_t* line_bits)
+{
+    const int rc = line_code_rules(code, LNSFAID_LINE_HARD);
+    if (rc) return rc;
+    if (burst_where_rules(where)) return LNSFAID_E_INVAL;
+    return burst_rules(code, shortened, n_codewords, line_bits, NULL);
+}
+
+int lnsfaid_burst_payload_random_host(const lnsfaid_code* code, uint64_t key, uint64_t first_codeword, const uint32_t* shortened,
+                                      int32_t where, size_t n_codewords, uint32_t* payload)
+{
+    const int rc = burst_link_rules(code, shortened, where, n_codewords, NULL);
+    if (rc) return rc;
+    if (n_codewords == 0) return LNSFAID_OK;
+    if (!payload) return LNSFAID_E_INVAL;
+    const size_t kw = (size_t)(code->n_var - code->n_check) / 32;
+    uint8_t* out = (uint8_t*)payload;
+    for (size_t i = 0; i < n_codewords; ++i) {
+        const uint64_t ck = link_cwkey(key, first_codeword + (uint64_t)i, 1u);
+        const size_t sw = burst_s(shortened, i) / 32u, k0w = where == LNSFAID_SHORTEN_HEAD ? 0 : kw - sw;
+        for (size_t wl = 0; wl < kw - sw; ++wl) {
+            const size_t wi = wl + (wl >= k0w ? sw : 0); /* the mother word: the low half of draw wi / 2 when even, else the high half */
+            const uint64_t h = link_draw(ck, (uint64_t)(wi / 2));
+            link_st32(out, (wi & 1u) ? (uint32_t)(h >> 32) : (uint32_t)h);
+            out += 4;
+        }
+    }
+    return LNSFAID_OK;
+}
+
+int lnsfaid_burst_bsc_host(const lnsfaid_code* code, const uint32_t* line_in, const uint32_t* shortened, int32_t where, size_t n_codewords,
+                           uint64_t key, uint64_t first_codeword, uint32_t threshold, uint32_t* line_out, uint32_t* flips,
+                           uint64_t* total_flips)
+{
+    const int rc = burst_link_rules(code, shortened, where, n_codewords, NULL);
+    if (rc) return rc;
+    if (n_codewords == 0) return LNSFAID_OK;
+    if (!line_in || !line_out) return LNSFAID_E_INVAL;
+    const size_t kw = (size_t)(code->n_var - code->n_check) / 32, lw = (size_t)(code->n_var - code->puncture_tail) / 32;
+    const uint8_t* in = (const uint8_t*)line_in;
+    uint8_t* out = (uint8_t*)line_out;
+    uint64_t total = 0;
+    for (size_t i = 0; i < n_codewords; ++i) {
+        const uint64_t ck = link_cwkey(key, first_codeword + (uint64_t)i, 2u);
+        const size_t sw = burst_s(shortened, i) / 32u, k0w = where == LNSFAID_SHORTEN_HEAD ? 0 : kw - sw;
+        uint32_t n = 0;
+        for (size_t wl = 0; wl < lw - sw; ++wl) {
+            const size_t wi = wl + (wl >= k0w ? sw : 0);
+            uint32_t mask = 0;
+            for (uint32_t j = 0; j < 16u; ++j) { /* mother position 32 wi + 2 j: the low half of draw 16 wi + j, + 1: the high half */
+                const uint64_t h = link_draw(ck, (uint64_t)(16 * wi + j));
+                mask |= (uint32_t)((uint32_t)h < threshold) << (2u * j);
+                mask |= (uint32_t)((uint32_t)(h >> 32) < threshold) << (2u * j + 1u);
+            }
+            link_st32(out, link_ld32(in) ^ mask);
+            in += 4; out += 4;
+            n += link_popcount(mask);
+        }
+        if (flips) link_st32((uint8_t*)flips + 4 * i, n);
+        total += n;
+    }
+    if (total_flips) *total_flips += total;
+    return LNSFAID_OK;
+}
+
+int lnsfaid_burst_soft_host(const lnsfaid_code* code, const uint32_t* line_in, const uint32_t* shortened, int32_t where, size_t n_codewords,
+                            uint64_t key, uint64_t first_codeword, const uint32_t table[14], uint8_t* llr4_out, uint32_t* flips,
+                            uint64_t* total_flips)
+{
+    uint64_t line_bits = 0;
+    const int rc = burst_link_rules(code, shortened, where, n_codewords, &line_bits);
+    if (rc) return rc;
+    if (n_codewords == 0) return LNSFAID_OK;
+    uint32_t thr[14];
+    if (!line_in || !llr4_out || soft_table_rules(table, thr)) return LNSFAID_E_INVAL;
+    const size_t kw = (size_t)(code->n_var - code->n_check) / 32, lw = (size_t)(code->n_var - code->puncture_tail) / 32;
+    const uint8_t* in = (const uint8_t*)line_in;
+    uint8_t* out = llr4_out;
+    const uintptr_t a = (uintptr_t)in, b = (uintptr_t)out; /* the output is four times the input: no overlap can be right */
+    if (a < b + (size_t)(line_bits / 2) && b < a + (size_t)(line_bits / 8)) return LNSFAID_E_INVAL;
+    uint64_t total = 0;
+    for (size_t i = 0; i < n_codewords; ++i) {
+        const uint64_t ck = link_cwkey(key, first_codeword + (uint64_t)i, 3u);
+        const size_t sw = burst_s(shortened, i) / 32u, k0w = where == LNSFAID_SHORTEN_HEAD ? 0 : kw - sw;
+        uint32_t n = 0;
+        for (size_t wl = 0; wl < lw - sw; ++wl) {
+            const size_t wi = wl + (wl >= k0w ? sw : 0);
+            const uint32_t x = link_ld32(in);
+            for (uint32_t j = 0; j < 16u; ++j) { /* mother positions 32 wi + 2 j and + 1: draw 16 wi + j, one output byte */
+                const uint64_t h = link_draw(ck, (uint64_t)(16 * wi + j));
+                unsigned byte = 0;
+                for (unsigned half = 0; half < 2u; ++half) {
+                    const uint32_t u = half ? (uint32_t)(h >> 32) : (uint32_t)h;
+                    int m = -7;
+                    for (int t = 0; t < 14; ++t) m += u >= thr[t];
+                    const int bit = (int)(x >> (2u * j + half)) & 1;
+                    const int level = bit ? m : -m;
+                    n += (uint32_t)((level > 0) != bit);
+                    byte |= ((unsigned)level & 15u) << (4u * half);
+                }
+                out[j] = (uint8_t)byte;
+            }
+            in += 4; out += 16;
+        }
+        if (flips) link_st32((uint8_t*)flips + 4 * i, n);
+        total += n;
+    }
+    if (total_flips) *total_flips += total;
+    return LNSFAID_OK;
+}
+
+/* the counters of lnsfaid_line_count_errors_host on payloads of (K - S_c) / 32 words, with failed = unsatisfied > 0 || short_ones > 0
+ * where the line counters have unsatisfied > 0 */
+int lnsfaid_burst_count_errors_host(const lnsfaid_code* code, const uint32_t* payload, const uint32_t* sent, const lnsfaid_line_stats* stats,
+                                    const uint32_t* short_ones, const uint32_t* shortened, size_t n_codewords, uint64_t errors[4],
+                                    uint64_t fec[4], uint64_t vs_sent[4])
+{
+    const int rc = burst_rules(code, shortened, n_codewords, NULL, NULL);
+    if (rc) return rc;
+    if (n_codewords == 0) return LNSFAID_OK;
+    if (!payload || ((fec || vs_sent) && !stats)) return LNSFAID_E_INVAL;
+    const size_t kw = (size_t)(code->n_var - code->n_check) / 32;
+    const uint8_t* got = (const uint8_t*)payload;
+    const uint8_t* ref = (const uint8_t*)sent;
+    const uint8_t* st = (const uint8_t*)stats;
+    uint64_t e[4] = { 0, 0, 0, 0 }, f[4] = { 0, 0, 0, 0 }, v[4] = { 0, 0, 0, 0 };
+    for (size_t i = 0; i < n_codewords; ++i) {
+        const size_t words = kw - burst_s(shortened, i) / 32u;
+        uint64_t wrong = 0;
+        for (size_t w = 0; w < words; ++w) {
+            wrong += link_popcount(link_ld32(got) ^ (ref ? link_ld32(ref) : 0u));
+            got += 4;
+            if (ref) ref += 4;
+        }
+        e[0] += 1; e[1] += wrong > 0; e[2] += wrong; e[3] += wrong == 1 || wrong == 2;
+        if (st) {
+            const int32_t unsatisfied = (int32_t)link_ld32(st + sizeof(lnsfaid_line_stats) * i + 8);
+            const int32_t corrected = (int32_t)link_ld32(st + sizeof(lnsfaid_line_stats) * i + 12);
+            const int failed = unsatisfied > 0 || (short_ones && link_ld32((const uint8_t*)short_ones + 4 * i) > 0u);
+            f[0] += 1;
+            if (failed) f[1] += 1;
+            else if (unsatisfied == 0 && corrected > 0) { f[2] += 1; f[3] += (uint64_t)corrected; }
+            v[0] += 1;
+            if (wrong > 0) { v[1] += 1; v[2] += !failed && unsatisfied == 0; }
+            else v[3] += failed;
+        }
+    }
+    for (int k = 0; k < 4; ++k) {
+        if (errors) errors[k] += e[k];
+        if (fec) fec[k] += f[k];
+        if (vs_sent) vs_sent[k] += v[k];
+    }
+    return LNSFAID_OK;
+}
+
 /* ---- line-format failure capture, host form (include/lnsfaid.h "line-format failure capture") ----
  * The definition of what lnsfaid_line_capture_device returns: the syndrome row by row from pos_vn, no quasi-cyclic shortcut.  Bytes
  * in, bytes out (little-endian words), so host pointers of any alignment do. */

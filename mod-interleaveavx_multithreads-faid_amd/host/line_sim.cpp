@@ -12,7 +12,14 @@
  * error frames or after --max-calls calls.  One row per point goes to LineResult.txt (in the working directory) and to the console.
  * With --capture-failures CAPACITY (include/lnsfaid.h "line-format failure capture") the encode and decode calls also
  * write their `bits`, and after the counters of every call lnsfaid_line_capture_device pages through the codewords that are
- * uncorrectable or wrong, CAPACITY records at a time; one text row per failure is appended to --capture-file (LineFailures.txt). */
+ * uncorrectable or wrong, CAPACITY records at a time; one text row per failure is appended to --capture-file (LineFailures.txt).
+ * With --burst-length B --shorten S[,S...] [--where tail|head] (include/lnsfaid.h "burst-format link") the run is bursts
+ * of B codewords: the last codeword of burst j is shortened by S[j % len] bits and all others by 0 - a function of the global codeword
+ * number alone, so a run cut into calls is the same run - and every call is the burst form:
+ *   lnsfaid_burst_payload_random_device -> lnsfaid_encode_burst_device -> lnsfaid_burst_bsc_device | lnsfaid_burst_soft_device ->
+ *   lnsfaid_decode_burst_device -> lnsfaid_burst_count_errors_device
+ * The input BER is then taken over transmitted bits and the output BER over payload bits, and three columns are appended to a row:
+ * transmitted bits, payload bits, codewords with short_ones > 0.  Not with --propagation or --capture-failures. */
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -25,7 +32,7 @@
 #include "lnsfaid.h"
 
 static const char* kUsage =
-    "usage: %s --ber P[,P...] [--magnitude 4] [--propagation A] | --ebn0 D[,D...] [--scale 9.19238816] --codewords N --max-calls C --min-errors E [--method 2] [--iterations 10] [--key K] [--device D] [--capture-failures CAPACITY [--capture-file LineFailures.txt]]\n";
+    "usage: %s --ber P[,P...] [--magnitude 4] [--propagation A] | --ebn0 D[,D...] [--scale 9.19238816] --codewords N --max-calls C --min-errors E [--method 2] [--iterations 10] [--key K] [--device D] [--capture-failures CAPACITY [--capture-file LineFailures.txt]] [--burst-length B --shorten S[,S...] [--where tail|head]]\n";
 
 static bool parse_u64(const char* s, uint64_t* v)
 {
@@ -58,6 +65,21 @@ static bool parse_ebn0(const char* s, std::vector<double>* out)
         const double v = strtod(p, &end);
         if (end == p || !std::isfinite(v)) return false;
         out->push_back(v);
+        if (*end == '\0') return true;
+        if (*end != ',') return false;
+        p = end + 1;
+    }
+}
+
+static bool parse_shorten(const char* s, std::vector<uint32_t>* out)
+{
+    const char* p = s;
+    while (true) {
+        char* end = nullptr;
+        if (*p < '0' || *p > '9') return false;
+        const unsigned long long v = strtoull(p, &end, 10);
+        if (end == p || v > 0xffffffffull) return false; /* the rule S % 32 == 0, S <= K - 32 is the library's: checked below */
+        out->push_back((uint32_t)v);
         if (*end == '\0') return true;
         if (*end != ',') return false;
         p = end + 1;
@@ -97,6 +119,10 @@ int main(int argc, char** argv)
     uint64_t codewords = 0, max_calls = 0, min_errors = 0, method = 2, iterations = 10, magnitude = 4, key = 1, device = 0;
     uint64_t capture = 0; /* --capture-failures: records per page, 0 = off */
     const char* capture_file = nullptr;
+    uint64_t burst_length = 0; /* --burst-length: codewords per burst, 0 = the line formats */
+    std::vector<uint32_t> shorten;
+    int32_t where = LNSFAID_SHORTEN_TAIL;
+    bool have_where = false;
     bool have[4] = { false, false, false, false }, ok = true;
     for (int i = 1; i < argc && ok; ++i) {
         const char* a = argv[i];
@@ -116,6 +142,12 @@ int main(int argc, char** argv)
         else if (!strcmp(a, "--device")) ok = parse_u64(v, &device) && device < 1024;
         else if (!strcmp(a, "--capture-failures")) ok = parse_u64(v, &capture) && capture > 0 && capture <= 0x7fffffffull;
         else if (!strcmp(a, "--capture-file")) ok = *(capture_file = v) != '\0';
+        else if (!strcmp(a, "--burst-length")) ok = parse_u64(v, &burst_length) && burst_length > 0;
+        else if (!strcmp(a, "--shorten")) ok = shorten.empty() && parse_shorten(v, &shorten);
+        else if (!strcmp(a, "--where")) {
+            have_where = ok = !strcmp(v, "tail") || !strcmp(v, "head");
+            where = !strcmp(v, "head") ? LNSFAID_SHORTEN_HEAD : LNSFAID_SHORTEN_TAIL;
+        }
         else ok = false;
         ++i;
     }
@@ -124,6 +156,8 @@ int main(int argc, char** argv)
     else if (have_scale) ok = false;                    /* and --scale to --ebn0 */
     if (capture_file && !capture) ok = false;           /* and --capture-file to --capture-failures */
     if (capture && !capture_file) capture_file = "LineFailures.txt";
+    const bool burst = burst_length > 0;
+    if (burst ? (shorten.empty() || markov || capture) : (!shorten.empty() || have_where)) ok = false; /* the three belong together */
     if (!ok || !have[0] || !have[1] || !have[2] || !have[3]) {
         fprintf(stderr, kUsage, argv[0]);
         return 2;
@@ -137,6 +171,10 @@ int main(int argc, char** argv)
     int rc = lnsfaid_code_50gpon(&code, pos.get(), deg, rows);
     if (!rc) rc = lnsfaid_cfg_default(&cfg, (int32_t)method, (int32_t)iterations);
     const size_t n = (size_t)codewords, groups = (n + LNSFAID_GROUP - 1) / LNSFAID_GROUP;
+    if (!rc && burst && lnsfaid_burst_words(&code, shorten.data(), shorten.size(), nullptr, nullptr)) { /* S % 32 == 0, S <= K - 32 */
+        fprintf(stderr, kUsage, argv[0]);
+        return 2;
+    }
     if (!rc) rc = lnsfaid_create(&ctx, &code, &cfg, (int32_t)device, groups);
     int8_t *d_a = nullptr, *d_b = nullptr;
     if (!rc) rc = lnsfaid_io_buffers(ctx, &d_a, &d_b, nullptr);
@@ -154,8 +192,9 @@ int main(int argc, char** argv)
                  o_stats = align256(n * K / 8);
     const size_t o_runs = o_flips + align256(4 * n);
     const size_t o_sent = o_runs + (markov ? align256(4 * n) : 0), o_bits = o_stats + align256(sizeof(lnsfaid_line_stats) * n);
+    const size_t o_ones = o_bits; /* --burst-length: short_ones behind the stats (no --capture-failures then) */
     if (o_flips + 4 * n > room || (markov && o_runs + 4 * n > room) || o_stats + sizeof(lnsfaid_line_stats) * n > room ||
-        (capture && (o_sent + n * N / 8 > room || o_bits + n * N / 8 > room))) {
+        (capture && (o_sent + n * N / 8 > room || o_bits + n * N / 8 > room)) || (burst && o_ones + 4 * n > room)) {
         fprintf(stderr, "lnsfaid_line_sim: the context's buffers are too small for this code\n");
         lnsfaid_destroy(ctx);
         return 1;
@@ -169,6 +208,10 @@ int main(int argc, char** argv)
     lnsfaid_line_stats* d_stats = (lnsfaid_line_stats*)(d_b + o_stats);
     uint32_t* d_sent = capture ? (uint32_t*)(d_a + o_sent) : nullptr;  /* the encode call's bits */
     uint32_t* d_bits = capture ? (uint32_t*)(d_b + o_bits) : nullptr;  /* the decode call's bits */
+    uint32_t* d_ones = burst ? (uint32_t*)(d_b + o_ones) : nullptr;    /* the burst decode's short_ones */
+    /* the call's S_c, and S = K - 32 for all: with it short_ones [n] reads as a burst payload of one word per codeword, and
+     * ErrorFrame of the counters against the all-zero payload is the number of codewords with short_ones > 0 */
+    std::vector<uint32_t> shortened(burst ? n : 0), one_word(burst ? n : 0, (uint32_t)K - 32u);
     const int32_t format = soft ? LNSFAID_LINE_LLR4 : LNSFAID_LINE_HARD;
     const size_t page = capture < n ? (size_t)capture : n;
     uint32_t W = 0;
@@ -208,11 +251,21 @@ int main(int argc, char** argv)
                               "TotalCodewords UncorrectableCodewords CorrectedCodewords CorrectedBits "
                               "vsTestFrame vsErrorFrame UndetectedErrorFrame FalseAlarmFrame seconds propagation t_idle t_after runs mean_run\n";
     if (markov) head = markov_head;
+    std::string burst_head;
+    if (burst) {
+        burst_head = std::string(soft ? soft_head : head);
+        burst_head.replace(burst_head.size() - 1, 1, " transmitted_bits payload_bits ShortOnesCodewords\n");
+        fprintf(f, "# lnsfaid_line_sim: bursts of %llu codewords, the last shortened by", (unsigned long long)burst_length);
+        for (size_t i = 0; i < shorten.size(); ++i) fprintf(f, "%s%u", i ? "," : " ", shorten[i]);
+        fprintf(f, " bits at the %s\n", where == LNSFAID_SHORTEN_HEAD ? "head" : "tail");
+    }
     if (soft) {
         head = soft_head;
+        if (burst) head = burst_head.c_str();
         fprintf(f, "# lnsfaid_line_sim: soft, DecodeMethod %llu, %llu iterations, scale %.9g, key %llu, %zu codewords per call\n%s",
                 (unsigned long long)method, (unsigned long long)iterations, scale, (unsigned long long)key, n, head);
     } else {
+        if (burst) head = burst_head.c_str();
         fprintf(f, "# lnsfaid_line_sim: DecodeMethod %llu, %llu iterations, magnitude %llu, key %llu, %zu codewords per call\n%s",
                 (unsigned long long)method, (unsigned long long)iterations, (unsigned long long)magnitude, (unsigned long long)key, n, head);
     }
@@ -227,8 +280,32 @@ int main(int argc, char** argv)
         const double a = propagation > x ? propagation : x; /* positive correlation only: below p the channel is the BSC */
         if (markov) rc = lnsfaid_line_markov_thresholds(x, a, mt); /* mt[2], the threshold of the marginal BER, is `threshold` */
         uint64_t errors[4] = { 0, 0, 0, 0 }, fec[4] = { 0, 0, 0, 0 }, vs[4] = { 0, 0, 0, 0 }, flips = 0, runs = 0;
+        uint64_t sent_bits = 0, payload_bits = 0, ones[4] = { 0, 0, 0, 0 }; /* --burst-length: the denominators, short_ones > 0 in ones[1] */
         const auto t0 = std::chrono::steady_clock::now();
-        for (uint64_t call = 0; call < max_calls && !rc && errors[1] < min_errors; ++call, first += n) {
+        for (uint64_t call = 0; burst && call < max_calls && !rc && errors[1] < min_errors; ++call, first += n) {
+            for (size_t i = 0; i < n; ++i) { /* the last codeword of burst j = C / B is shortened by S[j % len] */
+                const uint64_t C = first + i;
+                shortened[i] = C % burst_length == burst_length - 1 ? shorten[(size_t)((C / burst_length) % shorten.size())] : 0u;
+            }
+            const uint32_t* sh = shortened.data();
+            uint64_t lb = 0, pb = 0;
+            rc = lnsfaid_burst_words(&code, sh, n, &lb, &pb);
+            if (!rc) rc = lnsfaid_burst_payload_random_device(ctx, key, first, sh, where, n, d_payload);
+            if (!rc) rc = lnsfaid_encode_burst_device(ctx, d_payload, sh, where, n, d_line, nullptr);
+            if (soft) {
+                if (!rc) rc = lnsfaid_burst_soft_device(ctx, d_line, sh, where, n, key, first, table, d_llr4, d_flips, &flips);
+                if (!rc) rc = lnsfaid_decode_burst_device(ctx, d_llr4, LNSFAID_LINE_LLR4, 0, sh, where, n, d_decoded, nullptr, d_stats, d_ones);
+            } else {
+                if (!rc) rc = lnsfaid_burst_bsc_device(ctx, d_line, sh, where, n, key, first, threshold, d_line, d_flips, &flips);
+                if (!rc) rc = lnsfaid_decode_burst_device(ctx, d_line, LNSFAID_LINE_HARD, (int32_t)magnitude, sh, where, n, d_decoded, nullptr,
+                                                          d_stats, d_ones);
+            }
+            if (!rc) rc = lnsfaid_burst_count_errors_device(ctx, d_decoded, d_payload, d_stats, d_ones, sh, n, errors, fec, vs);
+            if (!rc) rc = lnsfaid_burst_count_errors_device(ctx, d_ones, nullptr, nullptr, nullptr, one_word.data(), n, ones, nullptr, nullptr);
+            sent_bits += lb;
+            payload_bits += pb;
+        }
+        for (uint64_t call = 0; !burst && call < max_calls && !rc && errors[1] < min_errors; ++call, first += n) {
             rc = lnsfaid_line_payload_random_device(ctx, key, first, n, d_payload);
             if (!rc) rc = lnsfaid_encode_line_device(ctx, d_payload, n, d_line, d_sent);
             if (soft) {
@@ -263,15 +340,18 @@ int main(int argc, char** argv)
         char row[704];
         int len = snprintf(row, sizeof(row), "%.9g %u %llu %llu %.6e %llu %llu %llu %llu %.6e %.6e %llu %llu %llu %llu %llu %llu %llu %llu %.3f", x,
                            soft ? table[7] : threshold, (unsigned long long)errors[0], (unsigned long long)flips,
-                           cw > 0 ? (double)flips / (cw * (double)L) : 0.0,
+                           burst ? (sent_bits ? (double)flips / (double)sent_bits : 0.0) : cw > 0 ? (double)flips / (cw * (double)L) : 0.0,
                            (unsigned long long)errors[0], (unsigned long long)errors[1], (unsigned long long)errors[2], (unsigned long long)errors[3],
-                           cw > 0 ? (double)errors[1] / cw : 0.0, cw > 0 ? (double)errors[2] / (cw * (double)K) : 0.0,
+                           cw > 0 ? (double)errors[1] / cw : 0.0, burst ? (payload_bits ? (double)errors[2] / (double)payload_bits : 0.0) : cw > 0 ? (double)errors[2] / (cw * (double)K) : 0.0,
                            (unsigned long long)fec[0], (unsigned long long)fec[1], (unsigned long long)fec[2], (unsigned long long)fec[3],
                            (unsigned long long)vs[0], (unsigned long long)vs[1], (unsigned long long)vs[2], (unsigned long long)vs[3], seconds);
         if (soft) len += snprintf(row + len, sizeof(row) - (size_t)len, " %.9g %.9g", sigma, scale);
         if (markov)
             len += snprintf(row + len, sizeof(row) - (size_t)len, " %.9g %u %u %llu %.6f", a, mt[0], mt[1], (unsigned long long)runs,
                             runs ? (double)flips / (double)runs : 0.0);
+        if (burst)
+            len += snprintf(row + len, sizeof(row) - (size_t)len, " %llu %llu %llu", (unsigned long long)sent_bits, (unsigned long long)payload_bits,
+                            (unsigned long long)ones[1]);
         snprintf(row + len, sizeof(row) - (size_t)len, "\n");
         fputs(row, f);
         fflush(f);

@@ -127,6 +127,20 @@ SYMBOLS = {
                                            C.POINTER(C.c_uint64)]),
     "lnsfaid_line_soft_host": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                          C.POINTER(C.c_uint64)]),
+    "lnsfaid_burst_payload_random_device": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p]),
+    "lnsfaid_burst_payload_random_host": (C.c_int, [C.POINTER(Code), C.c_uint64, C.c_uint64, C.c_void_p, C.c_int32, C.c_size_t, C.c_void_p]),
+    "lnsfaid_burst_bsc_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint32,
+                                           C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "lnsfaid_burst_bsc_host": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_void_p, C.c_int32, C.c_size_t, C.c_uint64, C.c_uint64, C.c_uint32,
+                                         C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "lnsfaid_burst_soft_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int32, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "lnsfaid_burst_soft_host": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_void_p, C.c_int32, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p,
+                                          C.c_void_p, C.c_void_p, C.POINTER(C.c_uint64)]),
+    "lnsfaid_burst_count_errors_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                    C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
+    "lnsfaid_burst_count_errors_host": (C.c_int, [C.POINTER(Code), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t,
+                                                  C.POINTER(C.c_uint64), C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
     "lnsfaid_line_markov_thresholds": (C.c_int, [C.c_double, C.c_double, C.c_void_p]),
     "lnsfaid_line_markov_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
                                              C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]),
@@ -615,6 +629,91 @@ def line_count_errors_host(code, payload, sent, stats, n_codewords, errors=True,
     return tuple(list(x) if x is not None else None for x in (e, f, v))
 
 
+def _sptr(shortened):
+    return None if shortened is None else shortened.ctypes.data
+
+
+def burst_payload_random_host(code, key, first_codeword, shortened, where, n_codewords, lib=None):
+    """lnsfaid_burst_payload_random_host: the burst payload (flat uint32, (K - S_c) / 32 words per codeword) of codewords
+    first_codeword .. of stream `key`: the line payload of each codeword with the known words dropped"""
+    import numpy as np
+    lib = lib or load()
+    shortened = _shortened(shortened, n_codewords)
+    _, payload_bits = burst_words(code, shortened, n_codewords, lib)
+    out = np.empty(payload_bits // 32, dtype=np.uint32)
+    rc = lib.lnsfaid_burst_payload_random_host(C.byref(code), key, first_codeword, _sptr(shortened), where, n_codewords, out.ctypes.data)
+    if rc != 0:
+        raise ValueError("lnsfaid_burst_payload_random_host failed: %d" % rc)
+    return out
+
+
+def burst_bsc_host(code, line, shortened, where, n_codewords, key, first_codeword, threshold, in_place=False, total=0, lib=None):
+    """lnsfaid_burst_bsc_host: burst line (flat uint32, LINE_HARD) through the binary symmetric channel of stream `key`, the draws
+    indexed by mother position.  Returns (line out, flips uint32 [n_codewords], total + the positions inverted); in_place writes into
+    `line` itself"""
+    import numpy as np
+    lib = lib or load()
+    shortened = _shortened(shortened, n_codewords)
+    line_bits, _ = burst_words(code, shortened, n_codewords, lib)
+    if not in_place:
+        line = np.ascontiguousarray(line, dtype=np.uint32)
+    if line.dtype != np.uint32 or not line.flags.c_contiguous or line.size != line_bits // 32:
+        raise ValueError("lnsfaid_burst_bsc_host: line must be contiguous uint32 with %d words" % (line_bits // 32))
+    out = line if in_place else np.empty_like(line)
+    flips = np.zeros(n_codewords, dtype=np.uint32)
+    t = C.c_uint64(total)
+    rc = lib.lnsfaid_burst_bsc_host(C.byref(code), line.ctypes.data, _sptr(shortened), where, n_codewords, key, first_codeword, threshold,
+                                    out.ctypes.data, flips.ctypes.data, C.byref(t))
+    if rc != 0:
+        raise ValueError("lnsfaid_burst_bsc_host failed: %d" % rc)
+    return out, flips, t.value
+
+
+def burst_soft_host(code, line, shortened, where, n_codewords, key, first_codeword, table, total=0, lib=None):
+    """lnsfaid_burst_soft_host: burst line (flat uint32, LINE_HARD) through the soft channel of stream `key` and `table`.  Returns
+    (llr4 burst line, flat uint8 (LINE_LLR4), flips uint32 [n_codewords], total + the flips of the call)"""
+    import numpy as np
+    lib = lib or load()
+    shortened = _shortened(shortened, n_codewords)
+    line_bits, _ = burst_words(code, shortened, n_codewords, lib)
+    line = np.ascontiguousarray(line, dtype=np.uint32)
+    if line.size != line_bits // 32:
+        raise ValueError("lnsfaid_burst_soft_host: line has %d words, not %d" % (line.size, line_bits // 32))
+    table = _soft_table(table)
+    out = np.empty(line_bits // 2, dtype=np.uint8)
+    flips = np.zeros(n_codewords, dtype=np.uint32)
+    t = C.c_uint64(total)
+    rc = lib.lnsfaid_burst_soft_host(C.byref(code), line.ctypes.data, _sptr(shortened), where, n_codewords, key, first_codeword,
+                                     table.ctypes.data, out.ctypes.data, flips.ctypes.data, C.byref(t))
+    if rc != 0:
+        raise ValueError("lnsfaid_burst_soft_host failed: %d" % rc)
+    return out, flips, t.value
+
+
+def burst_count_errors_host(code, payload, sent, stats, short_ones, shortened, n_codewords, errors=True, fec=None, vs_sent=None, lib=None):
+    """lnsfaid_burst_count_errors_host: payload / sent burst payloads (flat uint32; sent None: all-zero), stats a line_stats_dtype()
+    array or None, short_ones uint32 [n_codewords] or None (zeros).  errors / fec / vs_sent and the result as line_count_errors_host;
+    a codeword with short_ones > 0 counts as failed"""
+    import numpy as np
+    lib = lib or load()
+    shortened = _shortened(shortened, n_codewords)
+    _, payload_bits = burst_words(code, shortened, n_codewords, lib)
+    payload = np.ascontiguousarray(payload, dtype=np.uint32)
+    sent = None if sent is None else np.ascontiguousarray(sent, dtype=np.uint32)
+    stats = None if stats is None else np.ascontiguousarray(stats, dtype=line_stats_dtype())
+    short_ones = None if short_ones is None else np.ascontiguousarray(short_ones, dtype=np.uint32)
+    if (payload.size != payload_bits // 32 or (sent is not None and sent.size != payload.size)
+            or (stats is not None and stats.size != n_codewords) or (short_ones is not None and short_ones.size != n_codewords)):
+        raise ValueError("lnsfaid_burst_count_errors_host: buffer sizes do not fit %d codewords" % n_codewords)
+    e, f, v = _fec_counters(errors), _fec_counters(fec), _fec_counters(vs_sent)
+    rc = lib.lnsfaid_burst_count_errors_host(C.byref(code), payload.ctypes.data, None if sent is None else sent.ctypes.data,
+                                             None if stats is None else stats.ctypes.data,
+                                             None if short_ones is None else short_ones.ctypes.data, _sptr(shortened), n_codewords, e, f, v)
+    if rc != 0:
+        raise ValueError("lnsfaid_burst_count_errors_host failed: %d" % rc)
+    return tuple(list(x) if x is not None else None for x in (e, f, v))
+
+
 def line_failure_dtype():
     """numpy view of lnsfaid_line_failure"""
     import numpy as np
@@ -1049,6 +1148,47 @@ class Decoder:
         e, f, v = _fec_counters(errors), _fec_counters(fec), _fec_counters(vs_sent)
         self._check(self.lib.lnsfaid_line_count_errors_device(self.ctx, d_payload_ptr, d_sent_ptr, d_stats_ptr, n_codewords, e, f, v),
                     "lnsfaid_line_count_errors_device")
+        return tuple(list(x) if x is not None else None for x in (e, f, v))
+
+    def burst_payload_random_device(self, key, first_codeword, shortened, where, n_codewords, d_payload_ptr):
+        """lnsfaid_burst_payload_random_device: the burst payload of codewords first_codeword .. of stream `key` into a device buffer;
+        `shortened` a host array (uint32 [n_codewords], bits) or None"""
+        shortened = _shortened(shortened, n_codewords)
+        self._check(self.lib.lnsfaid_burst_payload_random_device(self.ctx, key, first_codeword, _sptr(shortened), where, n_codewords,
+                                                                 d_payload_ptr), "lnsfaid_burst_payload_random_device")
+
+    def burst_bsc_device(self, d_line_in_ptr, shortened, where, n_codewords, key, first_codeword, threshold, d_line_out_ptr,
+                         d_flips_ptr=None, total=0):
+        """lnsfaid_burst_bsc_device: a LINE_HARD burst line through the binary symmetric channel of stream `key` (d_line_out_ptr may
+        equal d_line_in_ptr).  Returns total + the positions inverted"""
+        shortened = _shortened(shortened, n_codewords)
+        t = C.c_uint64(total)
+        self._check(self.lib.lnsfaid_burst_bsc_device(self.ctx, d_line_in_ptr, _sptr(shortened), where, n_codewords, key, first_codeword,
+                                                      threshold, d_line_out_ptr, d_flips_ptr, C.byref(t)), "lnsfaid_burst_bsc_device")
+        return t.value
+
+    def burst_soft_device(self, d_line_in_ptr, shortened, where, n_codewords, key, first_codeword, table, d_llr4_out_ptr,
+                          d_flips_ptr=None, total=0):
+        """lnsfaid_burst_soft_device: a LINE_HARD burst line through the soft channel of stream `key` and `table` (14 thresholds, host
+        side) into a LINE_LLR4 burst line.  Returns total + the flips of the call"""
+        shortened = _shortened(shortened, n_codewords)
+        table = _soft_table(table)
+        t = C.c_uint64(total)
+        self._check(self.lib.lnsfaid_burst_soft_device(self.ctx, d_line_in_ptr, _sptr(shortened), where, n_codewords, key, first_codeword,
+                                                       table.ctypes.data, d_llr4_out_ptr, d_flips_ptr, C.byref(t)),
+                    "lnsfaid_burst_soft_device")
+        return t.value
+
+    def burst_count_errors_device(self, d_payload_ptr, d_sent_ptr, d_stats_ptr, d_short_ones_ptr, shortened, n_codewords, errors=True,
+                                  fec=None, vs_sent=None):
+        """lnsfaid_burst_count_errors_device: device pointers to burst payloads (d_sent_ptr None: all-zero), to the lnsfaid_line_stats
+        and the short_ones of decode_burst_device (either None); `shortened` a host array or None.  errors / fec / vs_sent and the
+        result as line_count_errors_host"""
+        shortened = _shortened(shortened, n_codewords)
+        e, f, v = _fec_counters(errors), _fec_counters(fec), _fec_counters(vs_sent)
+        self._check(self.lib.lnsfaid_burst_count_errors_device(self.ctx, d_payload_ptr, d_sent_ptr, d_stats_ptr, d_short_ones_ptr,
+                                                               _sptr(shortened), n_codewords, e, f, v),
+                    "lnsfaid_burst_count_errors_device")
         return tuple(list(x) if x is not None else None for x in (e, f, v))
 
     def count_errors_packed(self, bits, msg, n_groups):
