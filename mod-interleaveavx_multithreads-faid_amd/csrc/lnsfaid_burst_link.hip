@@ -3,11 +3,10 @@
  * payload source, binary symmetric channel, soft channel and error counters where every codeword c is shortened by its own S_c.  The
  * host forms in lnsfaid_tables.c are the definition; these kernels return the same bytes.
  *
- * Generator: the link's, indexed by MOTHER position.  Its three functions are repeated here on purpose, as lnsfaid_line_soft.hip
- * repeats them: the line files stay as they are.
- *   cwkey(key, C, d) = mix64(mix64(key + d) + (C + 1) * 0xD1B54A32D192ED03),  draw(q) = mix64(cwkey + (q + 1) * 0x9E3779B97F4A7C15)
- * d = 1 payload, 2 BSC, 3 soft.  Word wl of a burst codeword whose known words are [k0w, k0w + Sw) is mother word
- * wi = wl + (wl >= k0w ? Sw : 0) and uses the draws 16 wi .. 16 wi + 15 (payload: half of draw wi / 2) of the line kernels.
+ * Generator: the link's (lnsfaid_link.h), indexed by MOTHER position; d = 1 payload, 2 BSC, 3 soft.  The inversion mask, the soft
+ * channel's tree, walk and unit loop, the flip sums and the counter's tallies are the line kernels', from the same header.
+ * Word wl of a burst codeword whose known words are [k0w, k0w + Sw) is mother word wi = wl + (wl >= k0w ? Sw : 0) and uses the draws
+ * 16 wi .. 16 wi + 15 (payload: half of draw wi / 2) of the line kernels.
  *
  * Shape of the payload and channel kernels (the line kernels', plus a search).  A workgroup of BL_T threads owns BL_CW consecutive
  * codewords.  Threads 0 .. BL_CW load the descriptors: thread t < cws writes codeword t's key, its Sw and its first unit relative to
@@ -41,23 +40,14 @@
 #include <stdint.h>
 
 #include "lnsfaid.h"
-#include "lnsfaid_burst_link.h"
+#include "lnsfaid_burst.h"
+#include "lnsfaid_launch.h"
+#include "lnsfaid_link.h"
 
 #define BL_T 256       /* threads per workgroup of the payload and channel kernels */
 #define BL_CW 32u      /* codewords per workgroup */
 #define BC_WAVES 4     /* codewords in flight per workgroup of the counter kernel */
 #define BC_MAX_WG 2048u
-
-struct BlTable { uint32_t t[14]; };
-
-__device__ __forceinline__ uint64_t bl_mix64(uint64_t x)
-{
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27; x *= 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-__device__ __forceinline__ uint64_t bl_cwkey(uint64_t key, uint64_t C, uint64_t d) { return bl_mix64(bl_mix64(key + d) + (C + 1u) * 0xD1B54A32D192ED03ull); }
-__device__ __forceinline__ uint64_t bl_draw(uint64_t cwkey, uint64_t q) { return bl_mix64(cwkey + (q + 1u) * 0x9E3779B97F4A7C15ull); }
 
 /* what a workgroup keeps of its BL_CW codewords */
 struct BlFrame {
@@ -82,7 +72,7 @@ __device__ __forceinline__ uint32_t bl_frame(BlFrame& f, const LfBurstDesc* __re
         const uint32_t at = (PAYLOAD ? d.pay_off : d.line_off) - base;
         f.off[tid] = tid < cws ? at : at + words - d.s_words;
         if (tid < BL_CW) {
-            f.key[tid] = bl_cwkey(key, first + (uint64_t)cw0 + tid, domain);
+            f.key[tid] = lnk_cwkey(key, first + (uint64_t)cw0 + tid, domain);
             f.sw[tid] = tid < cws ? d.s_words : 0u;
             f.flips[tid] = 0u;
         }
@@ -108,19 +98,6 @@ __device__ __forceinline__ uint32_t bl_mother(const BlFrame& f, uint32_t c, uint
     return wl + (wl >= k0w ? sw : 0u);
 }
 
-/* wave 0: the codewords' flip sums out, their sum to the call's total */
-__device__ __forceinline__ void bl_flips_out(const BlFrame& f, uint32_t cw0, uint32_t cws, uint32_t* __restrict__ flips,
-                                             unsigned long long* __restrict__ total)
-{
-    const uint32_t tid = threadIdx.x;
-    if (tid < 64u) {
-        uint32_t n = tid < cws ? f.flips[tid] : 0u;
-        if (flips && tid < cws) flips[cw0 + tid] = n;
-        for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o);
-        if (tid == 0u && n) atomicAdd(total, (unsigned long long)n);
-    }
-}
-
 __global__ __launch_bounds__(BL_T) void lnsfaid_burst_payload_kernel(uint32_t* __restrict__ payload, const LfBurstDesc* __restrict__ desc,
                                                                      uint32_t where, uint32_t n_cw, uint32_t kw, unsigned long long key,
                                                                      unsigned long long first)
@@ -132,23 +109,9 @@ __global__ __launch_bounds__(BL_T) void lnsfaid_burst_payload_kernel(uint32_t* _
     const uint32_t units = f.off[cws];
     for (uint32_t u = threadIdx.x; u < units; u += BL_T) {
         const uint32_t c = bl_find(f, u), wi = bl_mother(f, c, u, kw, where);
-        const uint64_t h = bl_draw(f.key[c], wi >> 1);
+        const uint64_t h = lnk_draw(f.key[c], wi >> 1);
         payload[(size_t)base + u] = (wi & 1u) ? (uint32_t)(h >> 32) : (uint32_t)h;
     }
-}
-
-/* the inversion mask of mother word w: bit 2 j from the low half of draw 16 w + j, bit 2 j + 1 from the high half */
-__device__ __forceinline__ uint32_t bl_flip_mask(uint64_t cwkey, uint32_t w, uint32_t threshold)
-{
-    uint32_t mask = 0u;
-    const uint64_t base = cwkey + ((uint64_t)(16u * w) + 1u) * 0x9E3779B97F4A7C15ull;
-#pragma unroll
-    for (uint32_t j = 0; j < 16u; ++j) {
-        const uint64_t h = bl_mix64(base + (uint64_t)j * 0x9E3779B97F4A7C15ull);
-        mask |= ((uint32_t)h < threshold ? 1u : 0u) << (2u * j);
-        mask |= ((uint32_t)(h >> 32) < threshold ? 2u : 0u) << (2u * j);
-    }
-    return mask;
 }
 
 /* line_in == line_out is allowed: a thread reads a word before it writes that word, and no other thread touches it */
@@ -164,40 +127,19 @@ __global__ __launch_bounds__(BL_T) void lnsfaid_burst_bsc_kernel(const uint32_t*
     const uint32_t units = f.off[cws];
     for (uint32_t u = threadIdx.x; u < units; u += BL_T) {
         const uint32_t c = bl_find(f, u), wi = bl_mother(f, c, u, kw, where);
-        const uint32_t m = bl_flip_mask(f.key[c], wi, threshold);
+        const uint32_t m = lnk_flip_mask(f.key[c], wi, threshold);
         line_out[(size_t)base + u] = line_in[(size_t)base + u] ^ m;
         if (m) atomicAdd(&f.flips[c], (unsigned int)__popc(m));
     }
     __syncthreads();
-    bl_flips_out(f, cw0, cws, flips, total);
-}
-
-/* the threshold at tree node k (1 .. 15): entry (2 p + 1) * 2^(3 - d) - 1 of [0, table[0 .. 13]], d the depth of k and p its place in it */
-__device__ __forceinline__ uint32_t bl_node(const BlTable& tab, int k)
-{
-    const int d = k < 2 ? 0 : k < 4 ? 1 : k < 8 ? 2 : 3, p = k - (1 << d);
-    const int s = (2 * p + 1) * (8 >> d) - 1;
-    return s == 0 ? 0u : tab.t[s - 1];
-}
-
-/* one position, as in lnsfaid_line_soft.hip: u against the LDS threshold tree, the line bit as sb = -b.  Shifts r = m - b into rw and
- * the level b ? m : -m into lv, top nibble first. */
-__device__ __forceinline__ void bl_position(uint32_t u, uint32_t root, const uint32_t* tree, int32_t sb, uint32_t& rw, uint32_t& lv)
-{
-    uint32_t a = u >= root ? 12u : 8u; /* the node's byte address, 4 * node */
-#pragma unroll
-    for (int s = 0; s < 2; ++s) a = 2u * a + (u >= *(const uint32_t*)((const char*)tree + a) ? 4u : 0u);
-    const uint32_t node = (a >> 1) + (u >= *(const uint32_t*)((const char*)tree + a) ? 1u : 0u);
-    const int32_t r = (int32_t)node - 24 + sb;
-    rw = __builtin_amdgcn_alignbit((uint32_t)r, rw, 4);
-    lv = __builtin_amdgcn_alignbit((uint32_t)-(r ^ sb), lv, 4);
+    lnk_flips_out(f.flips, cw0, cws, flips, total);
 }
 
 /* A16: llr4_out starts on 16 bytes (every unit's 16 bytes then do), else on 4 */
 template <bool A16>
 __global__ __launch_bounds__(BL_T) void lnsfaid_burst_soft_kernel(const uint32_t* __restrict__ line_in, uint32_t* __restrict__ llr4_out,
                                                                   const LfBurstDesc* __restrict__ desc, uint32_t where, uint32_t n_cw, uint32_t lw,
-                                                                  uint32_t kw, unsigned long long key, unsigned long long first, BlTable tab,
+                                                                  uint32_t kw, unsigned long long key, unsigned long long first, LnkTable tab,
                                                                   uint32_t* __restrict__ flips, unsigned long long* __restrict__ total)
 {
     __shared__ BlFrame f;
@@ -207,7 +149,7 @@ __global__ __launch_bounds__(BL_T) void lnsfaid_burst_soft_kernel(const uint32_t
     const uint32_t base = bl_frame<false>(f, desc, cw0, cws, lw, key, first, 3u);
     if (tid == 64u) { /* a lane of the second wave, beside the keys of the first */
 #pragma unroll
-        for (int k = 1; k < 16; ++k) sTree[k] = bl_node(tab, k);
+        for (int k = 1; k < 16; ++k) sTree[k] = lnk_node(tab, k);
     }
     __syncthreads();
     const uint32_t root = tab.t[6];
@@ -217,19 +159,7 @@ __global__ __launch_bounds__(BL_T) void lnsfaid_burst_soft_kernel(const uint32_t
         const uint32_t x = line_in[(size_t)base + u];
         const uint64_t q0 = f.key[c] + ((uint64_t)(16u * wi) + 1u) * 0x9E3779B97F4A7C15ull;
         uint32_t out[4], n = 0u;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { /* eight positions, four draws, one output word */
-            uint32_t rw = 0u, lv = 0u;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint64_t h = bl_mix64(q0 + (uint64_t)(4 * i + j) * 0x9E3779B97F4A7C15ull);
-                const int b = 8 * i + 2 * j;
-                bl_position((uint32_t)h, root, sTree, (int32_t)(x << (31 - b)) >> 31, rw, lv);
-                bl_position((uint32_t)(h >> 32), root, sTree, (int32_t)(x << (30 - b)) >> 31, rw, lv);
-            }
-            out[i] = lv;
-            n += (uint32_t)__popc(rw & 0x88888888u);
-        }
+        LNK_SOFT_UNIT(x, q0, root, sTree, out, n)
         uint32_t* o = llr4_out + 4u * ((size_t)base + u);
         if (A16) {
             *(uint4*)o = make_uint4(out[0], out[1], out[2], out[3]);
@@ -239,7 +169,7 @@ __global__ __launch_bounds__(BL_T) void lnsfaid_burst_soft_kernel(const uint32_t
         if (n) atomicAdd(&f.flips[c], n);
     }
     __syncthreads();
-    bl_flips_out(f, cw0, cws, flips, total);
+    lnk_flips_out(f.flips, cw0, cws, flips, total);
 }
 
 /* acc: errors[4], fec[4], vs_sent[4], ADDED to.  sent, stats and short_ones may be null. */
@@ -249,13 +179,8 @@ __global__ __launch_bounds__(64 * BC_WAVES) void lnsfaid_burst_count_kernel(cons
                                                                             const LfBurstDesc* __restrict__ desc, uint32_t n_cw, uint32_t kw,
                                                                             unsigned long long* __restrict__ acc)
 {
-    __shared__ unsigned int sAcc[9];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    if (tid < 9u) sAcc[tid] = 0u;
-    __syncthreads();
-    /* lane 0's tallies: error frames, error bits, frames with 1 or 2; failed, corrected codewords, corrected bits; undetected,
-     * false alarms */
-    uint32_t n_err = 0, n_bits = 0, n_lt3 = 0, n_unc = 0, n_cor = 0, n_cbits = 0, n_und = 0, n_fa = 0;
+    LNK_COUNT_LOCALS()
     for (uint32_t cw = blockIdx.x * BC_WAVES + wave; cw < n_cw; cw += gridDim.x * BC_WAVES) {
         const LfBurstDesc d = desc[cw];
         const uint32_t words = kw - d.s_words;
@@ -264,46 +189,12 @@ __global__ __launch_bounds__(64 * BC_WAVES) void lnsfaid_burst_count_kernel(cons
         uint32_t wrong = 0u;
         for (uint32_t w = lane; w < words; w += 64u) wrong += (uint32_t)__popc(p[w] ^ (s ? s[w] : 0u));
         for (int o = 32; o > 0; o >>= 1) wrong += __shfl_down(wrong, o);
-        if (lane == 0u) {
-            if (wrong > 0u) { n_err += 1u; n_bits += wrong; n_lt3 += wrong < 3u ? 1u : 0u; }
-            if (stats) {
-                const int32_t unsat = stats[cw].unsatisfied, corr = stats[cw].corrected;
-                const bool failed = unsat > 0 || (short_ones && short_ones[cw] > 0u);
-                if (failed) n_unc += 1u;
-                else if (unsat == 0 && corr > 0) { n_cor += 1u; n_cbits += (uint32_t)corr; }
-                if (wrong > 0u) n_und += !failed && unsat == 0 ? 1u : 0u;
-                else n_fa += failed ? 1u : 0u;
-            }
-        }
+        LNK_COUNT_TALLY(cw, wrong, const bool failed = unsat > 0 || (short_ones && short_ones[cw] > 0u);, failed, !failed && unsat == 0)
     }
-    if (lane == 0u) {
-        if (n_err) { atomicAdd(&sAcc[0], n_err); atomicAdd(&sAcc[1], n_bits); atomicAdd(&sAcc[2], n_lt3); }
-        if (n_unc) atomicAdd(&sAcc[3], n_unc);
-        if (n_cor) { atomicAdd(&sAcc[4], n_cor); atomicAdd(&sAcc[5], n_cbits); }
-        if (n_und) atomicAdd(&sAcc[6], n_und);
-        if (n_fa) atomicAdd(&sAcc[7], n_fa);
-    }
-    __syncthreads();
-    if (tid == 0u) {
-        uint32_t walked = 0; /* the codewords this workgroup walked */
-        for (uint32_t cw = blockIdx.x * BC_WAVES; cw < n_cw; cw += gridDim.x * BC_WAVES) walked += n_cw - cw < BC_WAVES ? n_cw - cw : BC_WAVES;
-        atomicAdd(&acc[0], (unsigned long long)walked);
-        if (sAcc[0]) atomicAdd(&acc[1], (unsigned long long)sAcc[0]);
-        if (sAcc[1]) atomicAdd(&acc[2], (unsigned long long)sAcc[1]);
-        if (sAcc[2]) atomicAdd(&acc[3], (unsigned long long)sAcc[2]);
-        if (stats) {
-            atomicAdd(&acc[4], (unsigned long long)walked);
-            if (sAcc[3]) atomicAdd(&acc[5], (unsigned long long)sAcc[3]);
-            if (sAcc[4]) atomicAdd(&acc[6], (unsigned long long)sAcc[4]);
-            if (sAcc[5]) atomicAdd(&acc[7], (unsigned long long)sAcc[5]);
-            atomicAdd(&acc[8], (unsigned long long)walked);
-            if (sAcc[0]) atomicAdd(&acc[9], (unsigned long long)sAcc[0]);
-            if (sAcc[6]) atomicAdd(&acc[10], (unsigned long long)sAcc[6]);
-            if (sAcc[7]) atomicAdd(&acc[11], (unsigned long long)sAcc[7]);
-        }
-    }
+    LNK_COUNT_TAIL(BC_WAVES)
 }
 
+/* lnsfaid_launch.h says what the caller has checked */
 extern "C" hipError_t lf_launch_burst_payload(uint32_t* d_payload, const LfBurstDesc* d_desc, int where, size_t n_cw, uint32_t kw, uint64_t key,
                                               uint64_t first, hipStream_t stream)
 {
@@ -327,7 +218,7 @@ extern "C" hipError_t lf_launch_burst_soft(const uint32_t* d_in, uint8_t* d_out,
                                            unsigned long long* d_total, hipStream_t stream)
 {
     const dim3 grid((unsigned)((n_cw + BL_CW - 1u) / BL_CW)), block(BL_T);
-    BlTable tab;
+    LnkTable tab;
     for (int i = 0; i < 14; ++i) tab.t[i] = table[i];
     if (((uintptr_t)d_out & 15u) == 0u)
         hipLaunchKernelGGL(lnsfaid_burst_soft_kernel<true>, grid, block, 0, stream, d_in, (uint32_t*)d_out, d_desc, (uint32_t)where, (uint32_t)n_cw,

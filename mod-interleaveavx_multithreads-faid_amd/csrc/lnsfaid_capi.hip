@@ -22,7 +22,6 @@
 #include "lnsfaid_quantise.h"
 #include "lnsfaid_swar.h" /* sw_nms_fits / sw_nms_tables (host side) */
 #include "lnsfaid_launch.h" /* what the kernel files export */
-#include "lnsfaid_burst_link.h" /* and lnsfaid_burst_link.hip, in a header of its own */
 
 #include <atomic>
 #include <chrono>
@@ -2391,12 +2390,14 @@ extern "C" int lnsfaid_encode_line(lnsfaid_ctx* ctx, const uint32_t* payload, si
 
 /* ---- burst-format line calls (include/lnsfaid.h "burst-format line calls", DESIGN.md 3.18, lnsfaid_kernel4b.hip,
  * lnsfaid_encoder_burst.hip; host forms in lnsfaid_tables.c) ----------------------------------------------------------------- */
+static bool shorten_where_ok(int32_t where) { return where == LNSFAID_SHORTEN_TAIL || where == LNSFAID_SHORTEN_HEAD; }
+
 /* `shortened` (a host pointer of any alignment, or NULL) by the rule of the header, and the descriptors of the call: prefix sums
  * into the context's pinned array, one copy on its stream into its device array.  The totals are in words of 32 positions. */
 static int burst_descriptors(lnsfaid_ctx* ctx, const uint32_t* shortened, int32_t where, size_t n_codewords, size_t* line_units,
                              size_t* payload_words)
 {
-    if (where != LNSFAID_SHORTEN_TAIL && where != LNSFAID_SHORTEN_HEAD) return LNSFAID_E_INVAL;
+    if (!shorten_where_ok(where)) return LNSFAID_E_INVAL;
     const uint32_t K = (uint32_t)ctx->k_info, L = (uint32_t)(ctx->n_var - ctx->hcode.puncture_tail);
     if (ctx->n_var % 32 != 0 || L < K) return LNSFAID_E_INVAL;
     for (size_t c = 0; shortened && c < n_codewords; ++c) {
@@ -2449,7 +2450,7 @@ extern "C" int lnsfaid_decode_burst_device(lnsfaid_ctx* ctx, const void* d_line,
 {
     int rc = line_rules(ctx, format, magnitude, n_codewords);
     if (rc < 0) return rc;
-    if (where != LNSFAID_SHORTEN_TAIL && where != LNSFAID_SHORTEN_HEAD) return LNSFAID_E_INVAL;
+    if (!shorten_where_ok(where)) return LNSFAID_E_INVAL;
     if (rc) return LNSFAID_OK;
     if (!d_line || !d_payload) return LNSFAID_E_INVAL;
     if (!dword_aligned(d_line) || !dword_aligned(d_payload) || !dword_aligned(d_bits) || !dword_aligned(d_stats) || !dword_aligned(d_short_ones))
@@ -2467,7 +2468,7 @@ extern "C" int lnsfaid_decode_burst(lnsfaid_ctx* ctx, const void* line, int32_t 
 {
     int rc = line_rules(ctx, format, magnitude, n_codewords);
     if (rc < 0) return rc;
-    if (where != LNSFAID_SHORTEN_TAIL && where != LNSFAID_SHORTEN_HEAD) return LNSFAID_E_INVAL;
+    if (!shorten_where_ok(where)) return LNSFAID_E_INVAL;
     if (rc) return LNSFAID_OK;
     if (!line || !payload) return LNSFAID_E_INVAL;
     size_t lu, pw;
@@ -2498,7 +2499,7 @@ extern "C" int lnsfaid_encode_burst_device(lnsfaid_ctx* ctx, const uint32_t* d_p
 {
     int rc = encode_line_rules(ctx, n_codewords);
     if (rc < 0) return rc;
-    if (where != LNSFAID_SHORTEN_TAIL && where != LNSFAID_SHORTEN_HEAD) return LNSFAID_E_INVAL;
+    if (!shorten_where_ok(where)) return LNSFAID_E_INVAL;
     if (rc) return LNSFAID_OK;
     if (!d_payload || !d_line) return LNSFAID_E_INVAL;
     if (!dword_aligned(d_payload) || !dword_aligned(d_line) || !dword_aligned(d_bits)) return LNSFAID_E_INVAL;
@@ -2518,7 +2519,7 @@ extern "C" int lnsfaid_encode_burst(lnsfaid_ctx* ctx, const uint32_t* payload, c
 {
     int rc = encode_line_rules(ctx, n_codewords);
     if (rc < 0) return rc;
-    if (where != LNSFAID_SHORTEN_TAIL && where != LNSFAID_SHORTEN_HEAD) return LNSFAID_E_INVAL;
+    if (!shorten_where_ok(where)) return LNSFAID_E_INVAL;
     if (rc) return LNSFAID_OK;
     if (!payload || !line) return LNSFAID_E_INVAL;
     rc = ensure_encoder(ctx);
@@ -2559,6 +2560,61 @@ static int ensure_link_acc(lnsfaid_ctx* ctx)
     return LNSFAID_OK;
 }
 
+/* the soft channels' table: non-decreasing */
+static bool soft_table_ok(const uint32_t table[14])
+{
+    for (int i = 1; i < 14; ++i)
+        if (table[i] < table[i - 1]) return false;
+    return true;
+}
+
+/* A channel call's n totals (1: flips; 2: flips and runs), accumulators 12 and 13: zeroed on the stream in front of the launch ... */
+static unsigned long long* link_totals(const lnsfaid_ctx* ctx) { return ctx->d_link_acc + 12; }
+static int link_totals_begin(lnsfaid_ctx* ctx, int n)
+{
+    const int rc = ensure_link_acc(ctx);
+    if (rc) return rc;
+    HIP_TRY(hipMemsetAsync(link_totals(ctx), 0, n * sizeof(unsigned long long), ctx->stream));
+    return LNSFAID_OK;
+}
+
+/* ... and behind it copied back if one is asked for, waited for and ADDED to what the caller holds */
+static int link_totals_end(lnsfaid_ctx* ctx, int n, uint64_t* total_flips, uint64_t* total_runs)
+{
+    if (total_flips || total_runs)
+        HIP_TRY(hipMemcpyAsync(ctx->h_link_acc + 12, link_totals(ctx), n * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    const int rc = stream_wait(ctx);
+    if (rc) return rc;
+    if (total_flips) *total_flips += ctx->h_link_acc[12];
+    if (total_runs) *total_runs += ctx->h_link_acc[13];
+    return LNSFAID_OK;
+}
+
+/* The counter call of either format, the rules checked and the device set: twelve counters zeroed, counted (d_desc: the burst's
+ * uploaded descriptors, null for a line), copied back, waited for and ADDED into errors / fec / vs_sent, each of which may be null. */
+static int link_count_run(lnsfaid_ctx* ctx, const uint32_t* d_payload, const uint32_t* d_sent, const lnsfaid_line_stats* d_stats,
+                          const uint32_t* d_short_ones, const LfBurstDesc* d_desc, size_t n_codewords, uint64_t errors[4], uint64_t fec[4],
+                          uint64_t vs_sent[4])
+{
+    int rc = ensure_link_acc(ctx);
+    if (rc) return rc;
+    const uint32_t kw = (uint32_t)ctx->k_info / 32u;
+    HIP_TRY(hipMemsetAsync(ctx->d_link_acc, 0, 12 * sizeof(unsigned long long), ctx->stream));
+    if (d_desc)
+        HIP_TRY(lf_launch_burst_count(d_payload, d_sent, d_stats, d_short_ones, d_desc, n_codewords, kw, ctx->d_link_acc, ctx->stream));
+    else
+        HIP_TRY(lf_launch_line_count(d_payload, d_sent, d_stats, n_codewords, kw, ctx->d_link_acc, ctx->stream));
+    HIP_TRY(hipMemcpyAsync(ctx->h_link_acc, ctx->d_link_acc, 12 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
+    rc = stream_wait(ctx);
+    if (rc) return rc;
+    for (int i = 0; i < 4; ++i) {
+        if (errors) errors[i] += ctx->h_link_acc[i];
+        if (fec) fec[i] += ctx->h_link_acc[4 + i];
+        if (vs_sent) vs_sent[i] += ctx->h_link_acc[8 + i];
+    }
+    return LNSFAID_OK;
+}
+
 extern "C" int lnsfaid_line_payload_random_device(lnsfaid_ctx* ctx, uint64_t key, uint64_t first_codeword, size_t n_codewords,
                                                   uint32_t* d_payload)
 {
@@ -2578,41 +2634,23 @@ extern "C" int lnsfaid_line_bsc_device(lnsfaid_ctx* ctx, const uint32_t* d_line_
     if (!d_line_in || !d_line_out) return LNSFAID_E_INVAL;
     if (!dword_aligned(d_line_in) || !dword_aligned(d_line_out) || !dword_aligned(d_flips)) return LNSFAID_E_INVAL;
     HIP_TRY(hipSetDevice(ctx->device));
-    rc = ensure_link_acc(ctx);
+    rc = link_totals_begin(ctx, 1);
     if (rc) return rc;
-    unsigned long long* d_total = ctx->d_link_acc + 12;
-    HIP_TRY(hipMemsetAsync(d_total, 0, sizeof(unsigned long long), ctx->stream));
     HIP_TRY(lf_launch_line_bsc(d_line_in, d_line_out, n_codewords, (uint32_t)(ctx->n_var - ctx->hcode.puncture_tail) / 32u, key, first_codeword,
-                               threshold, d_flips, d_total, ctx->stream));
-    if (total_flips) HIP_TRY(hipMemcpyAsync(ctx->h_link_acc + 12, d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    rc = stream_wait(ctx);
-    if (rc) return rc;
-    if (total_flips) *total_flips += ctx->h_link_acc[12];
-    return LNSFAID_OK;
+                               threshold, d_flips, link_totals(ctx), ctx->stream));
+    return link_totals_end(ctx, 1, total_flips, nullptr);
 }
 
 extern "C" int lnsfaid_line_count_errors_device(lnsfaid_ctx* ctx, const uint32_t* d_payload, const uint32_t* d_sent,
                                                 const lnsfaid_line_stats* d_stats, size_t n_codewords, uint64_t errors[4], uint64_t fec[4],
                                                 uint64_t vs_sent[4])
 {
-    int rc = line_link_rules(ctx, n_codewords);
+    const int rc = line_link_rules(ctx, n_codewords);
     if (rc) return rc < 0 ? rc : LNSFAID_OK;
     if (!d_payload || ((fec || vs_sent) && !d_stats)) return LNSFAID_E_INVAL;
     if (!dword_aligned(d_payload) || !dword_aligned(d_sent) || !dword_aligned(d_stats)) return LNSFAID_E_INVAL;
     HIP_TRY(hipSetDevice(ctx->device));
-    rc = ensure_link_acc(ctx);
-    if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(ctx->d_link_acc, 0, 12 * sizeof(unsigned long long), ctx->stream));
-    HIP_TRY(lf_launch_line_count(d_payload, d_sent, d_stats, n_codewords, (uint32_t)ctx->k_info / 32u, ctx->d_link_acc, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->h_link_acc, ctx->d_link_acc, 12 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    rc = stream_wait(ctx);
-    if (rc) return rc;
-    for (int i = 0; i < 4; ++i) {
-        if (errors) errors[i] += ctx->h_link_acc[i];
-        if (fec) fec[i] += ctx->h_link_acc[4 + i];
-        if (vs_sent) vs_sent[i] += ctx->h_link_acc[8 + i];
-    }
-    return LNSFAID_OK;
+    return link_count_run(ctx, d_payload, d_sent, d_stats, nullptr, nullptr, n_codewords, errors, fec, vs_sent);
 }
 
 /* ---- line-format soft channel (include/lnsfaid.h "line-format soft channel", DESIGN.md 3.17, lnsfaid_line_soft.hip) ---- */
@@ -2623,23 +2661,16 @@ extern "C" int lnsfaid_line_soft_device(lnsfaid_ctx* ctx, const uint32_t* d_line
     if (rc) return rc < 0 ? rc : LNSFAID_OK;
     if (!d_line_in || !d_llr4_out || !table) return LNSFAID_E_INVAL;
     if (!dword_aligned(d_line_in) || !dword_aligned(d_llr4_out) || !dword_aligned(d_flips)) return LNSFAID_E_INVAL;
-    for (int i = 1; i < 14; ++i)
-        if (table[i] < table[i - 1]) return LNSFAID_E_INVAL;
+    if (!soft_table_ok(table)) return LNSFAID_E_INVAL;
     const size_t l_bits = (size_t)(ctx->n_var - ctx->hcode.puncture_tail);
     const uintptr_t a = (uintptr_t)d_line_in, b = (uintptr_t)d_llr4_out; /* four times the input: no overlap can be right */
     if (a < b + n_codewords * (l_bits / 2) && b < a + n_codewords * (l_bits / 8)) return LNSFAID_E_INVAL;
     HIP_TRY(hipSetDevice(ctx->device));
-    rc = ensure_link_acc(ctx);
+    rc = link_totals_begin(ctx, 1);
     if (rc) return rc;
-    unsigned long long* d_total = ctx->d_link_acc + 12;
-    HIP_TRY(hipMemsetAsync(d_total, 0, sizeof(unsigned long long), ctx->stream));
-    HIP_TRY(lf_launch_line_soft(d_line_in, d_llr4_out, n_codewords, (uint32_t)l_bits / 32u, key, first_codeword, table, d_flips, d_total,
-                                ctx->stream));
-    if (total_flips) HIP_TRY(hipMemcpyAsync(ctx->h_link_acc + 12, d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    rc = stream_wait(ctx);
-    if (rc) return rc;
-    if (total_flips) *total_flips += ctx->h_link_acc[12];
-    return LNSFAID_OK;
+    HIP_TRY(lf_launch_line_soft(d_line_in, d_llr4_out, n_codewords, (uint32_t)l_bits / 32u, key, first_codeword, table, d_flips,
+                                link_totals(ctx), ctx->stream));
+    return link_totals_end(ctx, 1, total_flips, nullptr);
 }
 
 /* ---- line-format error-propagation channel (include/lnsfaid.h "line-format error-propagation channel", DESIGN.md 3.20,
@@ -2653,19 +2684,11 @@ extern "C" int lnsfaid_line_markov_device(lnsfaid_ctx* ctx, const uint32_t* d_li
     if (!d_line_in || !d_line_out || !t || t[0] > t[1]) return LNSFAID_E_INVAL;
     if (!dword_aligned(d_line_in) || !dword_aligned(d_line_out) || !dword_aligned(d_flips) || !dword_aligned(d_runs)) return LNSFAID_E_INVAL;
     HIP_TRY(hipSetDevice(ctx->device));
-    rc = ensure_link_acc(ctx);
+    rc = link_totals_begin(ctx, 2); /* [0] flips, [1] runs */
     if (rc) return rc;
-    unsigned long long* d_totals = ctx->d_link_acc + 12; /* [0] flips, [1] runs */
-    HIP_TRY(hipMemsetAsync(d_totals, 0, 2 * sizeof(unsigned long long), ctx->stream));
     HIP_TRY(lf_launch_line_markov(d_line_in, d_line_out, n_codewords, (uint32_t)(ctx->n_var - ctx->hcode.puncture_tail) / 32u, key, first_codeword,
-                                  t, d_flips, d_runs, d_totals, ctx->stream));
-    if (total_flips || total_runs)
-        HIP_TRY(hipMemcpyAsync(ctx->h_link_acc + 12, d_totals, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    rc = stream_wait(ctx);
-    if (rc) return rc;
-    if (total_flips) *total_flips += ctx->h_link_acc[12];
-    if (total_runs) *total_runs += ctx->h_link_acc[13];
-    return LNSFAID_OK;
+                                  t, d_flips, d_runs, link_totals(ctx), ctx->stream));
+    return link_totals_end(ctx, 2, total_flips, total_runs);
 }
 
 /* ---- burst-format link (include/lnsfaid.h "burst-format link", DESIGN.md 3.22, lnsfaid_burst_link.hip; host forms in
@@ -2677,7 +2700,7 @@ extern "C" int lnsfaid_burst_payload_random_device(lnsfaid_ctx* ctx, uint64_t ke
 {
     int rc = line_link_rules(ctx, n_codewords);
     if (rc < 0) return rc;
-    if (where != LNSFAID_SHORTEN_TAIL && where != LNSFAID_SHORTEN_HEAD) return LNSFAID_E_INVAL;
+    if (!shorten_where_ok(where)) return LNSFAID_E_INVAL;
     if (rc) return LNSFAID_OK;
     if (!d_payload || !dword_aligned(d_payload)) return LNSFAID_E_INVAL;
     size_t lu, pw;
@@ -2694,25 +2717,19 @@ extern "C" int lnsfaid_burst_bsc_device(lnsfaid_ctx* ctx, const uint32_t* d_line
 {
     int rc = line_link_rules(ctx, n_codewords);
     if (rc < 0) return rc;
-    if (where != LNSFAID_SHORTEN_TAIL && where != LNSFAID_SHORTEN_HEAD) return LNSFAID_E_INVAL;
+    if (!shorten_where_ok(where)) return LNSFAID_E_INVAL;
     if (rc) return LNSFAID_OK;
     if (!d_line_in || !d_line_out) return LNSFAID_E_INVAL;
     if (!dword_aligned(d_line_in) || !dword_aligned(d_line_out) || !dword_aligned(d_flips)) return LNSFAID_E_INVAL;
     size_t lu, pw;
     rc = burst_descriptors(ctx, shortened, where, n_codewords, &lu, &pw);
     if (rc) return rc;
-    rc = ensure_link_acc(ctx);
+    rc = link_totals_begin(ctx, 1);
     if (rc) return rc;
-    unsigned long long* d_total = ctx->d_link_acc + 12;
-    HIP_TRY(hipMemsetAsync(d_total, 0, sizeof(unsigned long long), ctx->stream));
     HIP_TRY(lf_launch_burst_bsc(d_line_in, d_line_out, ctx->d_burst_desc, where, n_codewords,
                                 (uint32_t)(ctx->n_var - ctx->hcode.puncture_tail) / 32u, (uint32_t)ctx->k_info / 32u, key, first_codeword,
-                                threshold, d_flips, d_total, ctx->stream));
-    if (total_flips) HIP_TRY(hipMemcpyAsync(ctx->h_link_acc + 12, d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    rc = stream_wait(ctx);
-    if (rc) return rc;
-    if (total_flips) *total_flips += ctx->h_link_acc[12];
-    return LNSFAID_OK;
+                                threshold, d_flips, link_totals(ctx), ctx->stream));
+    return link_totals_end(ctx, 1, total_flips, nullptr);
 }
 
 extern "C" int lnsfaid_burst_soft_device(lnsfaid_ctx* ctx, const uint32_t* d_line_in, const uint32_t* shortened, int32_t where,
@@ -2721,12 +2738,11 @@ extern "C" int lnsfaid_burst_soft_device(lnsfaid_ctx* ctx, const uint32_t* d_lin
 {
     int rc = line_link_rules(ctx, n_codewords);
     if (rc < 0) return rc;
-    if (where != LNSFAID_SHORTEN_TAIL && where != LNSFAID_SHORTEN_HEAD) return LNSFAID_E_INVAL;
+    if (!shorten_where_ok(where)) return LNSFAID_E_INVAL;
     if (rc) return LNSFAID_OK;
     if (!d_line_in || !d_llr4_out || !table) return LNSFAID_E_INVAL;
     if (!dword_aligned(d_line_in) || !dword_aligned(d_llr4_out) || !dword_aligned(d_flips)) return LNSFAID_E_INVAL;
-    for (int i = 1; i < 14; ++i)
-        if (table[i] < table[i - 1]) return LNSFAID_E_INVAL;
+    if (!soft_table_ok(table)) return LNSFAID_E_INVAL;
     size_t lu, pw;
     rc = burst_descriptors(ctx, shortened, where, n_codewords, &lu, &pw);
     if (rc) return rc;
@@ -2735,18 +2751,12 @@ extern "C" int lnsfaid_burst_soft_device(lnsfaid_ctx* ctx, const uint32_t* d_lin
         (void)stream_wait(ctx); /* the descriptors' copy: the pinned array is free again for the next call */
         return LNSFAID_E_INVAL;
     }
-    rc = ensure_link_acc(ctx);
+    rc = link_totals_begin(ctx, 1);
     if (rc) return rc;
-    unsigned long long* d_total = ctx->d_link_acc + 12;
-    HIP_TRY(hipMemsetAsync(d_total, 0, sizeof(unsigned long long), ctx->stream));
     HIP_TRY(lf_launch_burst_soft(d_line_in, d_llr4_out, ctx->d_burst_desc, where, n_codewords,
                                  (uint32_t)(ctx->n_var - ctx->hcode.puncture_tail) / 32u, (uint32_t)ctx->k_info / 32u, key, first_codeword,
-                                 table, d_flips, d_total, ctx->stream));
-    if (total_flips) HIP_TRY(hipMemcpyAsync(ctx->h_link_acc + 12, d_total, sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    rc = stream_wait(ctx);
-    if (rc) return rc;
-    if (total_flips) *total_flips += ctx->h_link_acc[12];
-    return LNSFAID_OK;
+                                 table, d_flips, link_totals(ctx), ctx->stream));
+    return link_totals_end(ctx, 1, total_flips, nullptr);
 }
 
 extern "C" int lnsfaid_burst_count_errors_device(lnsfaid_ctx* ctx, const uint32_t* d_payload, const uint32_t* d_sent,
@@ -2760,20 +2770,7 @@ extern "C" int lnsfaid_burst_count_errors_device(lnsfaid_ctx* ctx, const uint32_
     size_t lu, pw;
     rc = burst_descriptors(ctx, shortened, LNSFAID_SHORTEN_TAIL, n_codewords, &lu, &pw); /* pay_off and s_words do not depend on `where` */
     if (rc) return rc;
-    rc = ensure_link_acc(ctx);
-    if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(ctx->d_link_acc, 0, 12 * sizeof(unsigned long long), ctx->stream));
-    HIP_TRY(lf_launch_burst_count(d_payload, d_sent, d_stats, d_short_ones, ctx->d_burst_desc, n_codewords, (uint32_t)ctx->k_info / 32u,
-                                  ctx->d_link_acc, ctx->stream));
-    HIP_TRY(hipMemcpyAsync(ctx->h_link_acc, ctx->d_link_acc, 12 * sizeof(unsigned long long), hipMemcpyDeviceToHost, ctx->stream));
-    rc = stream_wait(ctx);
-    if (rc) return rc;
-    for (int i = 0; i < 4; ++i) {
-        if (errors) errors[i] += ctx->h_link_acc[i];
-        if (fec) fec[i] += ctx->h_link_acc[4 + i];
-        if (vs_sent) vs_sent[i] += ctx->h_link_acc[8 + i];
-    }
-    return LNSFAID_OK;
+    return link_count_run(ctx, d_payload, d_sent, d_stats, d_short_ones, ctx->d_burst_desc, n_codewords, errors, fec, vs_sent);
 }
 
 /* ---- line-format failure capture (include/lnsfaid.h "line-format failure capture", DESIGN.md 3.19, lnsfaid_line_capture.hip; the

@@ -7,7 +7,7 @@
  * zeros: they enter s = A u as zero, are not in the payload and are not stored to line; information word m behind them is word
  * m - Sw of both, and the parity words follow at kw - Sw.  bits is the mother codeword at its fixed stride, zeros included.
  *
- * Everything else is lnsfaid_encode_line_kernel (see there for the phases and the LDS plan): 32 codewords per workgroup, lane
+ * Everything else is lnsfaid_encode_line_kernel (see there for the phases and the LDS plan; lnsfaid_encoder_line.h has the sizes and helpers): 32 codewords per workgroup, lane
  * (l = t / 8, q = t % 8) moves the four mother words 32 r + 4 q of codeword l per round.  A kept payload length is no longer a multiple
  * of four words, so "four words inside or outside together" holds only for a quad that lies wholly in front of or wholly behind the
  * known range: such a quad moves as one 16-byte access (4-byte aligned), a quad that touches the range word by word.  With Sw = 0
@@ -18,58 +18,8 @@
 #include <stdint.h>
 
 #include "lnsfaid_burst.h"
+#include "lnsfaid_encoder_line.h"
 #include "lnsfaid_launch.h"
-
-#define ENL_T 256                     /* threads per workgroup = circulant size */
-#define ENL_RAW_STRIDE 33             /* words per codeword of the raw image: column reads hit 32 banks */
-#define ENL_RAW_WORDS (32 * ENL_RAW_STRIDE)
-#define ENL_U_WORDS 1024              /* one round: 32 words of 32 codewords = four block columns, bit-sliced */
-#define ENL_PST_STRIDE 9
-#define ENL_PST_WORDS (32 * ENL_PST_STRIDE)
-#define ENL_CT_WORDS 68               /* a round's circulants, LF_MAX_COLW slots for each of four block columns, and their weights */
-static_assert(LF_MAX_COLW == 16 && ENL_CT_WORDS == 4 * LF_MAX_COLW + 4, "the circulant table is indexed with shifts by 4");
-
-/* ---- the helpers of lnsfaid_encoder_line.hip, as they are there ---- */
-template <int D>
-__device__ __forceinline__ uint32_t enl_xor_lane(uint32_t x)
-{
-    return (uint32_t)__builtin_amdgcn_ds_swizzle((int)x, 0x1f | (D << 10));
-}
-
-template <int D>
-__device__ __forceinline__ uint32_t enl_exchange(uint32_t x, uint32_t lane, uint32_t keep)
-{
-    const uint32_t y = enl_xor_lane<D>(x);
-    const uint32_t up = 0u - ((lane / D) & 1u); /* all ones in the lanes with bit D set */
-    const uint32_t ys = ((y >> D) & up) | ((y << D) & ~up);
-    const uint32_t take = ~keep ^ up; /* the columns that come from the partner: keep where bit D is set, ~keep elsewhere */
-    return (x & ~take) | (ys & take);
-}
-
-/* lane i holds row i (bit c = element (i, c)) -> lane i holds column i (bit r = element (r, i)) */
-__device__ __forceinline__ uint32_t enl_transpose32(uint32_t x, uint32_t lane)
-{
-    x = enl_exchange<16>(x, lane, 0x0000ffffu);
-    x = enl_exchange<8>(x, lane, 0x00ff00ffu);
-    x = enl_exchange<4>(x, lane, 0x0f0f0f0fu);
-    x = enl_exchange<2>(x, lane, 0x33333333u);
-    x = enl_exchange<1>(x, lane, 0x55555555u);
-    return x;
-}
-
-typedef uint32_t enl_u32x4 __attribute__((ext_vector_type(4), aligned(4)));
-
-__device__ __forceinline__ void enl_lds_barrier()
-{
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-
-__device__ __forceinline__ uint32_t enl_s_word(const uint32_t* s, uint32_t x4, uint32_t t4)
-{
-    return *(const uint32_t*)((const char*)s + ((x4 & ~(4u * LF_Z - 1u)) | ((x4 + t4) & (4u * LF_Z - 4u))));
-}
 
 /* ---- the known range of a lane's codeword: mother words [k0w, k1w), sw = k1w - k0w ---- */
 struct EnbRange {

@@ -3,8 +3,7 @@
  * DESIGN.md §3.16): a payload source, a binary symmetric channel on LNSFAID_LINE_HARD words and the error counters on payload
  * streams.  The host forms in lnsfaid_tables.c are the definition; these kernels return the same bytes.
  *
- * Generator (counter-based, stateless):  cwkey(key, C, d) = mix64(mix64(key + d) + (C + 1) * 0xD1B54A32D192ED03),
- * draw(q) = mix64(cwkey + (q + 1) * 0x9E3779B97F4A7C15), C the global codeword number, d = 1 payload, d = 2 channel.
+ * Generator: the link's (lnsfaid_link.h), domain d = 1 for the payload and d = 2 for the channel.
  *
  * Payload and channel kernels: a workgroup owns LK_CW consecutive codewords.  Their LK_CW keys are computed once, by the first
  * LK_CW threads, and kept in LDS; after that a thread takes units of V output words (V = 4, 2 or 1: the widest the base addresses
@@ -22,39 +21,17 @@
 
 #include "lnsfaid.h"
 #include "lnsfaid_launch.h"
+#include "lnsfaid_link.h"
 
 #define LK_T 256       /* threads per workgroup of the payload and channel kernels */
 #define LK_CW 32u      /* codewords per workgroup */
 #define LC_WAVES 4     /* codewords in flight per workgroup of the counter kernel */
 #define LC_MAX_WG 2048u
 
-__device__ __forceinline__ uint64_t lk_mix64(uint64_t x)
-{
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27; x *= 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-__device__ __forceinline__ uint64_t lk_cwkey(uint64_t key, uint64_t C, uint64_t d) { return lk_mix64(lk_mix64(key + d) + (C + 1u) * 0xD1B54A32D192ED03ull); }
-__device__ __forceinline__ uint64_t lk_draw(uint64_t cwkey, uint64_t q) { return lk_mix64(cwkey + (q + 1u) * 0x9E3779B97F4A7C15ull); }
-
 template <int V> struct LkVec;
 template <> struct LkVec<1> { typedef uint32_t type; };
 template <> struct LkVec<2> { typedef uint2 type; };
 template <> struct LkVec<4> { typedef uint4 type; };
-
-/* the inversion mask of line word w of a codeword: bit 2 j from the low half of draw 16 w + j, bit 2 j + 1 from the high half */
-__device__ __forceinline__ uint32_t lk_flip_mask(uint64_t cwkey, uint32_t w, uint32_t threshold)
-{
-    uint32_t mask = 0u;
-    const uint64_t base = cwkey + ((uint64_t)(16u * w) + 1u) * 0x9E3779B97F4A7C15ull;
-#pragma unroll
-    for (uint32_t j = 0; j < 16u; ++j) {
-        const uint64_t h = lk_mix64(base + (uint64_t)j * 0x9E3779B97F4A7C15ull);
-        mask |= ((uint32_t)h < threshold ? 1u : 0u) << (2u * j);
-        mask |= ((uint32_t)(h >> 32) < threshold ? 2u : 0u) << (2u * j);
-    }
-    return mask;
-}
 
 /* lw: words per codeword (a multiple of V); line_in == line_out is allowed: a thread reads a unit before it writes that unit */
 template <int V>
@@ -68,7 +45,7 @@ __global__ __launch_bounds__(LK_T) void lnsfaid_line_bsc_kernel(const uint32_t* 
     const uint32_t tid = threadIdx.x;
     const uint32_t cw0 = blockIdx.x * LK_CW, cws = n_cw - cw0 < LK_CW ? n_cw - cw0 : LK_CW; /* the grid covers n_cw: cw0 < n_cw */
     if (tid < LK_CW) {
-        sKey[tid] = lk_cwkey(key, first + (uint64_t)cw0 + tid, 2u);
+        sKey[tid] = lnk_cwkey(key, first + (uint64_t)cw0 + tid, 2u);
         sFlips[tid] = 0u;
     }
     __syncthreads();
@@ -83,7 +60,7 @@ __global__ __launch_bounds__(LK_T) void lnsfaid_line_bsc_kernel(const uint32_t* 
         const uint64_t ck = sKey[c];
 #pragma unroll
         for (int i = 0; i < V; ++i) {
-            const uint32_t m = lk_flip_mask(ck, w + (uint32_t)i, threshold);
+            const uint32_t m = lnk_flip_mask(ck, w + (uint32_t)i, threshold);
             x[i] ^= m;
             n += (uint32_t)__popc(m);
         }
@@ -93,12 +70,7 @@ __global__ __launch_bounds__(LK_T) void lnsfaid_line_bsc_kernel(const uint32_t* 
         if (n) atomicAdd(&sFlips[c], n);
     }
     __syncthreads();
-    if (tid < 64u) { /* wave 0: the codewords' sums out, their sum to the call's total */
-        uint32_t n = tid < cws ? sFlips[tid] : 0u;
-        if (flips && tid < cws) flips[cw0 + tid] = n;
-        for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o);
-        if (tid == 0u && n) atomicAdd(total, (unsigned long long)n);
-    }
+    lnk_flips_out(sFlips, cw0, cws, flips, total);
 }
 
 /* kw: words per codeword.  V = 4: kw % 4 == 0, V = 2: kw % 2 == 0 - a unit is one or two whole draws; V = 1: a word is half a draw */
@@ -110,7 +82,7 @@ __global__ __launch_bounds__(LK_T) void lnsfaid_line_payload_kernel(uint32_t* __
     __shared__ uint64_t sKey[LK_CW];
     const uint32_t tid = threadIdx.x;
     const uint32_t cw0 = blockIdx.x * LK_CW, cws = n_cw - cw0 < LK_CW ? n_cw - cw0 : LK_CW;
-    if (tid < LK_CW) sKey[tid] = lk_cwkey(key, first + (uint64_t)cw0 + tid, 1u);
+    if (tid < LK_CW) sKey[tid] = lnk_cwkey(key, first + (uint64_t)cw0 + tid, 1u);
     __syncthreads();
     const uint32_t upc = kw / (uint32_t)V, units = cws * upc;
     const size_t base = (size_t)cw0 * kw;
@@ -119,12 +91,12 @@ __global__ __launch_bounds__(LK_T) void lnsfaid_line_payload_kernel(uint32_t* __
         const uint64_t ck = sKey[c];
         uint32_t x[V];
         if (V == 1) {
-            const uint64_t h = lk_draw(ck, w >> 1);
+            const uint64_t h = lnk_draw(ck, w >> 1);
             x[0] = (w & 1u) ? (uint32_t)(h >> 32) : (uint32_t)h;
         } else {
 #pragma unroll
             for (int i = 0; i < V; i += 2) {
-                const uint64_t h = lk_draw(ck, (w + (uint32_t)i) >> 1);
+                const uint64_t h = lnk_draw(ck, (w + (uint32_t)i) >> 1);
                 x[i] = (uint32_t)h;
                 x[(i + 1) % V] = (uint32_t)(h >> 32);
             }
@@ -142,14 +114,9 @@ __global__ __launch_bounds__(64 * LC_WAVES) void lnsfaid_line_count_kernel(const
                                                                            unsigned long long* __restrict__ acc)
 {
     typedef typename LkVec<V>::type vec_t;
-    __shared__ unsigned int sAcc[9];
     const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-    if (tid < 9u) sAcc[tid] = 0u;
-    __syncthreads();
-    const uint32_t upc = kw / (uint32_t)V;
-    /* lane 0's tallies: error frames, error bits, frames with 1 or 2; uncorrectable, corrected codewords, corrected bits;
-     * undetected, false alarms */
-    uint32_t n_err = 0, n_bits = 0, n_lt3 = 0, n_unc = 0, n_cor = 0, n_cbits = 0, n_und = 0, n_fa = 0;
+    const uint32_t upc = kw / (uint32_t)V; /* in front of the tallies: behind them the instances compile to another instruction order */
+    LNK_COUNT_LOCALS()
     for (uint32_t cw = blockIdx.x * LC_WAVES + wave; cw < n_cw; cw += gridDim.x * LC_WAVES) {
         const uint32_t* p = payload + (size_t)cw * kw;
         const uint32_t* s = sent ? sent + (size_t)cw * kw : nullptr;
@@ -169,43 +136,9 @@ __global__ __launch_bounds__(64 * LC_WAVES) void lnsfaid_line_count_kernel(const
             for (int i = 0; i < V; ++i) wrong += (uint32_t)__popc(x[i]);
         }
         for (int o = 32; o > 0; o >>= 1) wrong += __shfl_down(wrong, o);
-        if (lane == 0u) {
-            if (wrong > 0u) { n_err += 1u; n_bits += wrong; n_lt3 += wrong < 3u ? 1u : 0u; }
-            if (stats) {
-                const int32_t unsat = stats[cw].unsatisfied, corr = stats[cw].corrected;
-                if (unsat > 0) n_unc += 1u;
-                else if (unsat == 0 && corr > 0) { n_cor += 1u; n_cbits += (uint32_t)corr; }
-                if (wrong > 0u) n_und += unsat == 0 ? 1u : 0u;
-                else n_fa += unsat > 0 ? 1u : 0u;
-            }
-        }
+        LNK_COUNT_TALLY(cw, wrong, /* no local */, unsat > 0, unsat == 0)
     }
-    if (lane == 0u) {
-        if (n_err) { atomicAdd(&sAcc[0], n_err); atomicAdd(&sAcc[1], n_bits); atomicAdd(&sAcc[2], n_lt3); }
-        if (n_unc) atomicAdd(&sAcc[3], n_unc);
-        if (n_cor) { atomicAdd(&sAcc[4], n_cor); atomicAdd(&sAcc[5], n_cbits); }
-        if (n_und) atomicAdd(&sAcc[6], n_und);
-        if (n_fa) atomicAdd(&sAcc[7], n_fa);
-    }
-    __syncthreads();
-    if (tid == 0u) {
-        uint32_t walked = 0; /* the codewords this workgroup walked */
-        for (uint32_t cw = blockIdx.x * LC_WAVES; cw < n_cw; cw += gridDim.x * LC_WAVES) walked += n_cw - cw < LC_WAVES ? n_cw - cw : LC_WAVES;
-        atomicAdd(&acc[0], (unsigned long long)walked);
-        if (sAcc[0]) atomicAdd(&acc[1], (unsigned long long)sAcc[0]);
-        if (sAcc[1]) atomicAdd(&acc[2], (unsigned long long)sAcc[1]);
-        if (sAcc[2]) atomicAdd(&acc[3], (unsigned long long)sAcc[2]);
-        if (stats) {
-            atomicAdd(&acc[4], (unsigned long long)walked);
-            if (sAcc[3]) atomicAdd(&acc[5], (unsigned long long)sAcc[3]);
-            if (sAcc[4]) atomicAdd(&acc[6], (unsigned long long)sAcc[4]);
-            if (sAcc[5]) atomicAdd(&acc[7], (unsigned long long)sAcc[5]);
-            atomicAdd(&acc[8], (unsigned long long)walked);
-            if (sAcc[0]) atomicAdd(&acc[9], (unsigned long long)sAcc[0]);
-            if (sAcc[6]) atomicAdd(&acc[10], (unsigned long long)sAcc[6]);
-            if (sAcc[7]) atomicAdd(&acc[11], (unsigned long long)sAcc[7]);
-        }
-    }
+    LNK_COUNT_TAIL(LC_WAVES)
 }
 
 /* words per access: 4 when every pointer given starts on 16 bytes and a codeword is a multiple of four words long (its codewords

@@ -3,9 +3,7 @@
  * DESIGN.md §3.20): a hard channel with memory on LNSFAID_LINE_HARD words.  The host form in lnsfaid_tables.c is the definition; this
  * kernel returns the same bytes.
  *
- * Generator: the link's (lnsfaid_line_link.hip), the BSC's domain d = 2.  The three functions are repeated here, eight lines, on
- * purpose, as in lnsfaid_line_soft.hip: that file is the BSC's and stays as it is.
- *   cwkey(key, C, d) = mix64(mix64(key + d) + (C + 1) * 0xD1B54A32D192ED03),  draw(q) = mix64(cwkey + (q + 1) * 0x9E3779B97F4A7C15)
+ * Generator: the link's (lnsfaid_link.h), the BSC's domain d = 2.
  *
  * The chain e[k] = g[k] | (p[k] & e[k - 1]), g[k] = (u[k] < t_idle), p[k] = (u[k] < t_after), g implies p, is the carry chain of the
  * sum A + B with A the p bits and B the g bits: where both are set the adder generates, where only p is set it propagates, where
@@ -31,20 +29,12 @@
 
 #include "lnsfaid.h"
 #include "lnsfaid_launch.h"
+#include "lnsfaid_link.h"
 
 #define LM_WAVES 4        /* codewords in flight per workgroup */
 #define LM_MAX_WG 2048u   /* 8 192 waves: every SIMD of the device full once, then the waves stride */
 
 struct LmThresholds { uint32_t idle, after, start; };
-
-__device__ __forceinline__ uint64_t lm_mix64(uint64_t x)
-{
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27; x *= 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-__device__ __forceinline__ uint64_t lm_cwkey(uint64_t key, uint64_t C, uint64_t d) { return lm_mix64(lm_mix64(key + d) + (C + 1u) * 0xD1B54A32D192ED03ull); }
-__device__ __forceinline__ uint64_t lm_draw(uint64_t cwkey, uint64_t q) { return lm_mix64(cwkey + (q + 1u) * 0x9E3779B97F4A7C15ull); }
 
 /* m = 2 m + (u < t): the compare's lane mask is the carry-in of m + m.  Two instructions per bit; written out because the compiler
  * turns the C form, m + m + (u < t), into compare, select, shift and or (three per bit and an s_nop in front of every select).  t is
@@ -63,7 +53,7 @@ __device__ __forceinline__ void lm_masks(uint64_t cwkey, uint32_t w, uint32_t t_
     const uint64_t base = cwkey + ((uint64_t)(16u * w) + 1u) * 0x9E3779B97F4A7C15ull;
 #pragma unroll
     for (int j = 15; j >= 0; --j) {
-        const uint64_t h = lm_mix64(base + (uint64_t)j * 0x9E3779B97F4A7C15ull);
+        const uint64_t h = lnk_mix64(base + (uint64_t)j * 0x9E3779B97F4A7C15ull);
         const uint32_t hi = (uint32_t)(h >> 32), lo = (uint32_t)h;
         lm_shift_in(a, hi, t_after);
         lm_shift_in(b, hi, t_idle);
@@ -88,8 +78,8 @@ __global__ __launch_bounds__(64 * LM_WAVES) void lnsfaid_line_markov_kernel(cons
     const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
     unsigned long long sum_flips = 0ull, sum_runs = 0ull; /* lane 0's */
     for (uint32_t cw = blockIdx.x * LM_WAVES + wave; cw < n_cw; cw += gridDim.x * LM_WAVES) {
-        const uint64_t ck = lm_cwkey(key, first + (uint64_t)cw, 2u);
-        uint32_t carry = (uint32_t)lm_draw(ck, (uint64_t)lw * 16u) < t.start ? 1u : 0u; /* e of position -1; uniform, as all of its kind below */
+        const uint64_t ck = lnk_cwkey(key, first + (uint64_t)cw, 2u);
+        uint32_t carry = (uint32_t)lnk_draw(ck, (uint64_t)lw * 16u) < t.start ? 1u : 0u; /* e of position -1; uniform, as all of its kind below */
         const size_t base = (size_t)cw * lw;
         uint32_t n = 0u, r = 0u;
         for (uint32_t w0 = 0u; w0 < lw; w0 += 64u) {

@@ -3,9 +3,8 @@
  * 15-level, symmetric memoryless channel from LNSFAID_LINE_HARD words to LNSFAID_LINE_LLR4 nibbles.  The host form in
  * lnsfaid_tables.c is the definition; this kernel returns the same bytes.
  *
- * Generator: the link's (lnsfaid_line_link.hip), domain d = 3.  The three functions are repeated here, eight lines, on purpose: that
- * file is the BSC's and stays as it is, and a shared header for eight lines would tie the two objects together.
- *   cwkey(key, C, d) = mix64(mix64(key + d) + (C + 1) * 0xD1B54A32D192ED03),  draw(q) = mix64(cwkey + (q + 1) * 0x9E3779B97F4A7C15)
+ * Generator: the link's (lnsfaid_link.h), domain d = 3.  The table struct, the tree's nodes, the walk of one position, the unit loop
+ * and the flip sums are there as well: the burst soft kernel (lnsfaid_burst_link.hip) runs the same text.
  *
  * Shape (the BSC kernel's): a workgroup owns LS_CW consecutive codewords; the first LS_CW threads compute their keys into LDS.  A unit
  * is one input word: 16 draws, 32 levels, 16 output bytes.  Units are taken with the workgroup's stride, consecutive lanes on
@@ -36,45 +35,15 @@
 
 #include "lnsfaid.h"
 #include "lnsfaid_launch.h"
+#include "lnsfaid_link.h"
 
 #define LS_T 256   /* threads per workgroup */
 #define LS_CW 32u  /* codewords per workgroup */
 
-struct LsTable { uint32_t t[14]; };
-
-__device__ __forceinline__ uint64_t ls_mix64(uint64_t x)
-{
-    x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-    x ^= x >> 27; x *= 0x94D049BB133111EBull;
-    return x ^ (x >> 31);
-}
-__device__ __forceinline__ uint64_t ls_cwkey(uint64_t key, uint64_t C, uint64_t d) { return ls_mix64(ls_mix64(key + d) + (C + 1u) * 0xD1B54A32D192ED03ull); }
-__device__ __forceinline__ uint64_t ls_draw(uint64_t cwkey, uint64_t q) { return ls_mix64(cwkey + (q + 1u) * 0x9E3779B97F4A7C15ull); }
-
-/* the threshold at tree node k (1 .. 15): entry (2 p + 1) * 2^(3 - d) - 1 of [0, table[0 .. 13]], d the depth of k and p its place in it */
-__device__ __forceinline__ uint32_t ls_node(const LsTable& tab, int k)
-{
-    const int d = k < 2 ? 0 : k < 4 ? 1 : k < 8 ? 2 : 3, p = k - (1 << d);
-    const int s = (2 * p + 1) * (8 >> d) - 1;
-    return s == 0 ? 0u : tab.t[s - 1];
-}
-
-/* one position: u against the tree, the line bit as sb = -b.  Shifts r = m - b into rw and the level into lv, top nibble first. */
-__device__ __forceinline__ void ls_position(uint32_t u, uint32_t root, const uint32_t* tree, int32_t sb, uint32_t& rw, uint32_t& lv)
-{
-    uint32_t a = u >= root ? 12u : 8u; /* the node's byte address, 4 * node */
-#pragma unroll
-    for (int s = 0; s < 2; ++s) a = 2u * a + (u >= *(const uint32_t*)((const char*)tree + a) ? 4u : 0u);
-    const uint32_t node = (a >> 1) + (u >= *(const uint32_t*)((const char*)tree + a) ? 1u : 0u);
-    const int32_t r = (int32_t)node - 24 + sb;
-    rw = __builtin_amdgcn_alignbit((uint32_t)r, rw, 4);
-    lv = __builtin_amdgcn_alignbit((uint32_t)-(r ^ sb), lv, 4);
-}
-
 /* lw: words per codeword.  A16: llr4_out starts on 16 bytes (every unit's 16 bytes then do), else on 4. */
 template <bool A16>
 __global__ __launch_bounds__(LS_T) void lnsfaid_line_soft_kernel(const uint32_t* __restrict__ line_in, uint32_t* __restrict__ llr4_out, uint32_t n_cw,
-                                                                 uint32_t lw, unsigned long long key, unsigned long long first, LsTable tab,
+                                                                 uint32_t lw, unsigned long long key, unsigned long long first, LnkTable tab,
                                                                  uint32_t* __restrict__ flips, unsigned long long* __restrict__ total)
 {
     __shared__ uint64_t sKey[LS_CW];
@@ -83,12 +52,12 @@ __global__ __launch_bounds__(LS_T) void lnsfaid_line_soft_kernel(const uint32_t*
     const uint32_t tid = threadIdx.x;
     const uint32_t cw0 = blockIdx.x * LS_CW, cws = n_cw - cw0 < LS_CW ? n_cw - cw0 : LS_CW; /* the grid covers n_cw: cw0 < n_cw */
     if (tid < LS_CW) {
-        sKey[tid] = ls_cwkey(key, first + (uint64_t)cw0 + tid, 3u);
+        sKey[tid] = lnk_cwkey(key, first + (uint64_t)cw0 + tid, 3u);
         sFlips[tid] = 0u;
     }
     if (tid == 64u) { /* a lane of the second wave, beside the keys of the first */
 #pragma unroll
-        for (int k = 1; k < 16; ++k) sTree[k] = ls_node(tab, k);
+        for (int k = 1; k < 16; ++k) sTree[k] = lnk_node(tab, k);
     }
     __syncthreads();
     const uint32_t root = tab.t[6];
@@ -100,19 +69,7 @@ __global__ __launch_bounds__(LS_T) void lnsfaid_line_soft_kernel(const uint32_t*
         const uint64_t ck = sKey[c];
         const uint64_t q0 = ck + ((uint64_t)(16u * w) + 1u) * 0x9E3779B97F4A7C15ull;
         uint32_t out[4], n = 0u;
-#pragma unroll
-        for (int i = 0; i < 4; ++i) { /* eight positions, four draws, one output word */
-            uint32_t rw = 0u, lv = 0u;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const uint64_t h = ls_mix64(q0 + (uint64_t)(4 * i + j) * 0x9E3779B97F4A7C15ull);
-                const int b = 8 * i + 2 * j;
-                ls_position((uint32_t)h, root, sTree, (int32_t)(x << (31 - b)) >> 31, rw, lv);
-                ls_position((uint32_t)(h >> 32), root, sTree, (int32_t)(x << (30 - b)) >> 31, rw, lv);
-            }
-            out[i] = lv;
-            n += (uint32_t)__popc(rw & 0x88888888u);
-        }
+        LNK_SOFT_UNIT(x, q0, root, sTree, out, n)
         uint32_t* o = llr4_out + 4u * (base + u);
         if (A16) {
             *(uint4*)o = make_uint4(out[0], out[1], out[2], out[3]);
@@ -122,12 +79,7 @@ __global__ __launch_bounds__(LS_T) void lnsfaid_line_soft_kernel(const uint32_t*
         if (n) atomicAdd(&sFlips[c], n);
     }
     __syncthreads();
-    if (tid < 64u) { /* wave 0: the codewords' sums out, their sum to the call's total */
-        uint32_t n = tid < cws ? sFlips[tid] : 0u;
-        if (flips && tid < cws) flips[cw0 + tid] = n;
-        for (int o = 32; o > 0; o >>= 1) n += __shfl_down(n, o);
-        if (tid == 0u && n) atomicAdd(total, (unsigned long long)n);
-    }
+    lnk_flips_out(sFlips, cw0, cws, flips, total);
 }
 
 /* The caller (lnsfaid_capi.hip) has checked the rules of include/lnsfaid.h: n_cw > 0, the pointers on 4 bytes, the table non-decreasing,
@@ -136,7 +88,7 @@ extern "C" hipError_t lf_launch_line_soft(const uint32_t* d_in, uint8_t* d_out, 
                                           const uint32_t table[14], uint32_t* d_flips, unsigned long long* d_total, hipStream_t stream)
 {
     const dim3 grid((unsigned)((n_cw + LS_CW - 1u) / LS_CW)), block(LS_T);
-    LsTable tab;
+    LnkTable tab;
     for (int i = 0; i < 14; ++i) tab.t[i] = table[i];
     if (((uintptr_t)d_out & 15u) == 0u)
         hipLaunchKernelGGL(lnsfaid_line_soft_kernel<true>, grid, block, 0, stream, d_in, (uint32_t*)d_out, (uint32_t)n_cw, lw, key, first, tab, d_flips, d_total);

@@ -1,10 +1,11 @@
 """Line-format link without a GPU (include/lnsfaid.h "line-format link"): the host forms - the definition of what the
 device calls return - byte for byte against the independent numpy restatement (tests/line_link_ref.py), paging, in-place use,
 domain separation, the channel's rate at a fixed key, the counters on planted batches, the error rules, the stand-alone sanitizer
-program and the driver's argument handling."""
+program, the driver's argument handling and the build-time properties of lnsfaid_line_link.hip from a cross-compile for gfx950."""
 import ctypes as C
 import math
 import os
+import shutil
 import subprocess
 
 import numpy as np
@@ -12,9 +13,12 @@ import pytest
 
 import line_link_ref as ll
 from test_line_cpu import _header_prototype
+from test_packed_io_isa import kernel_meta
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HOST = os.path.join(ROOT, "mod-interleaveavx_multithreads-faid_amd", "host")
+CSRC = os.path.join(ROOT, "mod-interleaveavx_multithreads-faid_amd", "csrc")
+HIPCC = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
 E_INVAL = -1
 KEY = 0x5EED0F50C0DE2025
 FIRSTS = [0, 7, 2 ** 32 + 5]
@@ -285,3 +289,25 @@ def test_line_sim_bad_arguments(tmp_path, args):
     assert r.returncode == 2, (r.returncode, r.stderr[-500:])
     assert r.stderr.startswith("usage: ") and "--ber" in r.stderr and r.stderr.count("\n") == 1
     assert not os.listdir(str(tmp_path))
+
+
+# ---- build-time properties of the kernel file ----
+@pytest.fixture(scope="module")
+def isa(tmp_path_factory):
+    if not os.path.exists(HIPCC):
+        pytest.skip("no hipcc")
+    out = tmp_path_factory.mktemp("isa_line_link") / "lnsfaid_line_link.s"
+    subprocess.run([HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I" + os.path.join(ROOT, "include"), "-I" + CSRC, "-S",
+                    "--cuda-device-only", "-o", str(out), os.path.join(CSRC, "lnsfaid_line_link.hip")], check=True, capture_output=True)
+    return out.read_text()
+
+
+def test_kernels_build_for_gfx950_without_scratch_or_spills(isa):
+    """the nine instances (channel, payload source and counters, each at 1, 2 and 4 words per access), each without scratch and
+    without spills, and few enough vector registers for eight waves per SIMD (at most 64)"""
+    meta = {n: m for n, m in kernel_meta(isa).items() if "lnsfaid_line_" in n}
+    kinds = {k: [n for n in meta if "lnsfaid_line_%s_kernel" % k in n] for k in ("bsc", "payload", "count")}
+    assert {k: len(v) for k, v in kinds.items()} == {"bsc": 3, "payload": 3, "count": 3} and len(meta) == 9, sorted(meta)
+    for name, (vgpr, spill, scratch) in meta.items():
+        print(name, vgpr, spill, scratch)
+        assert spill == 0 and scratch == 0 and vgpr <= 64, (name, vgpr, spill, scratch)

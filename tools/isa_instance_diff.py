@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """Compare the instruction text of every kernel instance of one source file between two source trees.
 
-    python tools/isa_instance_diff.py OLD_CSRC NEW_CSRC lnsfaid_kernel4.hip [lnsfaid_kernel4cw.hip ...]
+    python tools/isa_instance_diff.py [--rename OLD=NEW ...] OLD_CSRC NEW_CSRC lnsfaid_kernel4.hip [lnsfaid_kernel4cw.hip ...]
 
 Each file is compiled for gfx950 with the Makefile's flags (-O3 -std=c++17, device code only) in both trees.  Labels,
 comments, directives and blank lines are dropped; what is left of every kernel body is counted and hashed.  Prints one line per
 instance (old count / hash, new count / hash, same or DIFFERENT) and exits 1 when an instance differs or exists in one tree only.
+
+Instances are paired by mangled name.  --rename OLD=NEW (repeatable) replaces OLD by NEW in the old tree's names first, for a type in
+a kernel's signature that was renamed: --rename 7LsTable=8LnkTable.
 """
 import hashlib
 import os
@@ -38,13 +41,19 @@ def instances(csrc, name, tmp):
 
 
 def main():
-    old_dir, new_dir, files = sys.argv[1], sys.argv[2], sys.argv[3:]
+    args, renames = sys.argv[1:], []
+    while args and args[0] == "--rename":
+        renames.append(args[1].split("=", 1))
+        args = args[2:]
+    old_dir, new_dir, files = args[0], args[1], args[2:]
     bad = 0
     with tempfile.TemporaryDirectory() as tmp:
         for f in files:
             os.makedirs(os.path.join(tmp, "old"), exist_ok=True)
             os.makedirs(os.path.join(tmp, "new"), exist_ok=True)
             a = instances(old_dir, f, os.path.join(tmp, "old"))
+            for old, new in renames:
+                a = {name.replace(old, new): ins for name, ins in a.items()}
             b = instances(new_dir, f, os.path.join(tmp, "new"))
             print("# %s" % f)
             for name in sorted(set(a) | set(b)):
