@@ -1059,6 +1059,15 @@ int lnsfaid_zero_shift_groups(const lnsfaid_ctx* ctx, int32_t* groups, int32_t n
 int lnsfaid_window_free(const lnsfaid_ctx* ctx);
 int lnsfaid_code_zero_shift_order(const lnsfaid_code* code, int32_t* groups, int32_t* order);
 
+/* Edge words.  Where the window-free form applies (lnsfaid_window_free), its kernel has a twin that reads every
+ * rotating edge's LDS address and byte rotations from a compiled-in table instead of computing them in every layer
+ * (lnsfaid_kernel4e.hip).  On by default; lnsfaid_select_edge_words(ctx, 0) keeps lnsfaid_kernel4w.hip there, (ctx, 1) goes back.
+ * Identical results either way; the switch exists for tests and A/B timing.  Environment: LNSFAID_EDGE_WORDS=off.
+ * lnsfaid_edge_words returns 1 if the next decode launches the twin, 0 if not: never 1 where lnsfaid_window_free returns 0.
+ * lnsfaid_window_free and lnsfaid_zero_shift_groups answer the same with the twin as without. */
+int lnsfaid_select_edge_words(lnsfaid_ctx* ctx, int32_t on);
+int lnsfaid_edge_words(const lnsfaid_ctx* ctx);
+
 /* The syndrome walk tables of the bit-flipping stage, without a GPU (for tests).  The stage flips block columns of weight
  * col_weight (REGULAR_COL_WEIGHT) only, so the library walks their circulants in every iteration (`flipped`) and all others once
  * when a codeword enters the stage (`fixed`); `full` is the walk of the layered stage's syndrome.  Per layer, slot and 32-row word

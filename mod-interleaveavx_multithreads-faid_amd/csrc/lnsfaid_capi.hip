@@ -110,6 +110,7 @@ struct lnsfaid_ctx {
                             * (lnsfaid_kernel4z.hip) also where the layer-static kernel applies; 4: the layer-static kernel, asked
                             * for; 5: the same, and lnsfaid_kernel4s.hip also where its window-free twin applies
                             * (lnsfaid_select_zero_shift) */
+    int edge_words = 1;    /* lnsfaid_kernel4e.hip where the window-free kernel applies; 0: lnsfaid_kernel4w.hip there (lnsfaid_select_edge_words) */
     mutable int static_code = -1; /* the code's zero-first edge tables equal the layer-static kernel's constants: -1 not compared yet */
     struct LfCombiner* comb = nullptr; /* call combiner this one-group context is a member of (see below) */
     int comb_slot = -1;
@@ -503,6 +504,8 @@ extern "C" int lnsfaid_create(lnsfaid_ctx** out, const lnsfaid_code* code, const
     if (const char* e = getenv("LNSFAID_ZERO_SHIFT")) /* test / A-B switch, see lnsfaid_select_zero_shift: "off" / "on" */
         ctx->zero_shift = (e[0] == 'o' && e[1] == 'f') ? LNSFAID_ZERO_SHIFT_OFF /* "off" / "loop" / "windowed" */
                           : (e[0] == 'l' ? LNSFAID_ZERO_SHIFT_LOOP : (e[0] == 'w' ? LNSFAID_ZERO_SHIFT_WINDOWED : 0));
+    if (const char* e = getenv("LNSFAID_EDGE_WORDS")) /* test / A-B switch, see lnsfaid_select_edge_words: "off" */
+        ctx->edge_words = (e[0] == 'o' && e[1] == 'f') ? 0 : 1;
     g_live_contexts.fetch_add(1, std::memory_order_relaxed); /* (lnsfaid_destroy takes it back) */
     const int rc = create_impl(ctx, code, cfg);
     if (rc) { lnsfaid_destroy(ctx); return rc; }
@@ -635,6 +638,22 @@ static bool use_window_free(const lnsfaid_ctx* ctx)
     return use_static_layers(ctx) && ctx->zero_shift != LNSFAID_ZERO_SHIFT_WINDOWED && ctx->hcfg.floor_iter_thresh < 0;
 }
 
+/* The edge-word kernel (lnsfaid_kernel4e.hip) takes the window-free kernel's place unless it is switched off. */
+static bool use_edge_words(const lnsfaid_ctx* ctx) { return ctx->edge_words != 0 && use_window_free(ctx); }
+
+extern "C" int lnsfaid_select_edge_words(lnsfaid_ctx* ctx, int32_t on)
+{
+    if (!ctx || on < 0 || on > 1) return LNSFAID_E_INVAL;
+    ctx->edge_words = on;
+    return LNSFAID_OK;
+}
+
+extern "C" int lnsfaid_edge_words(const lnsfaid_ctx* ctx)
+{
+    if (!ctx) return LNSFAID_E_INVAL;
+    return use_edge_words(ctx) ? 1 : 0;
+}
+
 extern "C" int lnsfaid_select_zero_shift(lnsfaid_ctx* ctx, int32_t mode)
 {
     if (!ctx || mode < 0 || mode > LNSFAID_ZERO_SHIFT_WINDOWED) return LNSFAID_E_INVAL;
@@ -740,6 +759,7 @@ static LfInst select_kernel(const lnsfaid_ctx* ctx, int entry)
     case LF_ENTRY_BURST: k.fn = lf_decode4b_func(m, ef, rm); break;
     default: /* the group rule on int8 I/O: every kernel has it */
         if (use_kernel5(ctx)) { k.fn = lf_decode5_func(m); k.threads = lf_decode5_threads(); }
+        else if (use_edge_words(ctx)) k.fn = lf_decode4e_func(m);
         else if (use_window_free(ctx)) k.fn = lf_decode4w_func(m);
         else if (use_static_layers(ctx)) k.fn = lf_decode4s_func(m);
         else if (use_zero_shift(ctx)) k.fn = lf_decode4z_func(m);
@@ -1269,7 +1289,7 @@ static void comb_leave(lnsfaid_ctx* ctx, int slot)
 /* 1: decoded through the combiner (*rc_out = result); 0: not applicable now, take the direct path */
 static int comb_decode(lnsfaid_ctx* ctx, const int8_t* fixInput, int8_t* decodedBits, lnsfaid_group_stats* stats, int rule, int* rc_out)
 {
-    if (ctx->comb_slot < 0 || ctx->rows_per_lane != 0 || ctx->msg_store != 0 || ctx->waves_per_cw != 0 || ctx->zero_shift != 0) return 0;
+    if (ctx->comb_slot < 0 || ctx->rows_per_lane != 0 || ctx->msg_store != 0 || ctx->waves_per_cw != 0 || ctx->zero_shift != 0 || ctx->edge_words != 1) return 0;
     LfCombiner* cb = ctx->comb;
     const int slot = ctx->comb_slot;
     {

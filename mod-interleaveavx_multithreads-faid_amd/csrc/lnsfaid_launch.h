@@ -41,12 +41,13 @@ hipError_t lf_launch_count_errors_packed(const uint32_t* d_bits, const uint32_t*
 /* lnsfaid_kernel4l.hip, lnsfaid_kernel4b.hip */
 const void* lf_decode4l_func(int method, int ef, int rm);
 const void* lf_decode4b_func(int method, int ef, int rm);
-/* lnsfaid_kernel4z.hip, lnsfaid_kernel4s.hip, lnsfaid_kernel4w.hip */
+/* lnsfaid_kernel4z.hip, lnsfaid_kernel4s.hip, lnsfaid_kernel4w.hip, lnsfaid_kernel4e.hip */
 int lf_decode4z_inst(int deg, int zg);
 const void* lf_decode4z_func(int method);
 int lf_decode4s_matches(const LfDevCode* code);
 const void* lf_decode4s_func(int method);
 const void* lf_decode4w_func(int method);
+const void* lf_decode4e_func(int method);
 /* lnsfaid_kernel5.hip */
 const void* lf_decode5_func(int method);
 int lf_decode5_threads(void);

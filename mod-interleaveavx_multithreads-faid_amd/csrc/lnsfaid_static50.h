@@ -68,6 +68,46 @@ struct SwTabStatic<Sw50Tab<BR>> {
     static constexpr int nz = Sw50Tab<BR>::NZ;
 };
 
+/* ---- the edge words of SW_FORM_EDGEW: what a lane needs of a rotating edge besides its block column, in one
+ * word.  With x = lane + shift: bits 7:2 the dword x mod 64 of the column (the word under 0xfc is the LDS address inside the column),
+ * bits 1:0 the read's byte rotation (x div 64) mod 4, bits 9:8 the write-back's, 4 minus that mod 4.  `edge` counts in Sw50Tab's
+ * order, so only edges nz <= edge < deg have words. */
+constexpr uint32_t sw50_edge_word_of(uint32_t s4, int lane) /* (constexpr: host and device) */
+{
+    const uint32_t x = (uint32_t)lane + (s4 >> 2), rq = (x >> 6) & 3u;
+    return ((x & 63u) << 2) | rq | (((4u - rq) & 3u) << 8);
+}
+constexpr uint32_t sw50_edge_word(int layer, int edge, int lane) { return sw50_edge_word_of(sw50_build().layer[layer].s4[edge], lane); }
+/* The table a kernel loads them from: [layer][group of four rotating edges][lane][4], so that the 64 lanes' 16-byte loads of a group
+ * read 1 KB contiguous; a layer's last group is padded with zero words. */
+constexpr int sw50_edge_groups(int layer) { return (sw50_build().layer[layer].deg - sw50_build().layer[layer].nz + 3) / 4; }
+constexpr int sw50_edge_group_base(int layer) /* groups in front of the layer's first */
+{
+    int n = 0;
+    for (int br = 0; br < layer; ++br) n += sw50_edge_groups(br);
+    return n;
+}
+#define SW50_EDGE_GROUPS sw50_edge_group_base(SW50_LAYERS)
+#define SW50_EDGE_GROUP_WORDS 256
+struct Sw50EdgeImage {
+    uint32_t w[SW50_EDGE_GROUPS * SW50_EDGE_GROUP_WORDS];
+};
+constexpr Sw50EdgeImage sw50_edge_image()
+{
+    constexpr Sw50Code c = sw50_build();
+    Sw50EdgeImage im = {};
+    int g0 = 0;
+    for (int br = 0; br < SW50_LAYERS; ++br) {
+        const int rot = c.layer[br].deg - c.layer[br].nz;
+        for (int e = 0; e < rot; ++e)
+            for (int lane = 0; lane < 64; ++lane)
+                im.w[((g0 + e / 4) * 64 + lane) * 4 + e % 4] = sw50_edge_word_of(c.layer[br].s4[c.layer[br].nz + e], lane);
+        g0 += (rot + 3) / 4;
+    }
+    return im;
+}
+static_assert(SW50_EDGE_GROUPS == 56, "206 rotating edges in groups of four, layer by layer");
+
 /* ---- the decision points' cheap "certainly dirty" test on the compile-time tables.  Any unsatisfied row proves
  * the codeword dirty, so the parity of ONE layer's rows is a sufficient condition that spares the plane build and the full
  * syndrome.  The cheapest layer to ask is the one with the most identity circulants: an identity edge is one read from the

@@ -666,6 +666,18 @@ struct SwNoXch {
     SW_MFN uint32_t get(int) const { return 0u; }
     SW_MFN void barrier() const {}
 };
+/* SW_FORM_EDGEW: where the step takes its edge words from.  w(j): the packed word of rotating edge j (j >= NZ) for this lane,
+ * 4 * dword | rotate amount | negated rotate amount << 8 (sw50_edge_word, lnsfaid_static50.h); the step takes the read rotate from it.
+ * wa(j): a word of the same value, from which the step makes the address and the write-back rotate: a caller may hand in ONE
+ * register for all edges of equal shift, whose address and shifted word are then made once.  at(point): called at fixed points of
+ * the step, so that a caller can issue the NEXT layer's loads where registers come free (between scheduling fences of its own, where
+ * it does): j0 behind the write-back of pass 2's group of edges j0 .. j0 + SW_ILP - 1, where that group's registers have come free.
+ * SwNoEw: every other form (both calls compile away). */
+struct SwNoEw {
+    SW_MFN uint32_t w(int) const { return 0u; }
+    SW_MFN uint32_t wa(int) const { return 0u; }
+    SW_MFN void at(int) const {}
+};
 #define SW_OWN(j) (WAVES == 1 || (((j) & 1) == WAVE))
 
 /* A table view whose s4(j) / cb256(j) are compile-time constants of (layer, j) specialises this (lnsfaid_static50.h): `value` and the
@@ -710,14 +722,20 @@ struct SwTabStatic {
  *                  their registers up.  Per-degree FAID / min-sum instances of degree > 16.
  *   SW_FORM_MUL    the single left shifts by 8 of the mask expander go through sw_shl8_mul (K.c100 must be a register), the shift by one
  *                  in front of the old patch's mask becomes an addition (sw_mask6_mul), the byte gathers pack with v_perm_b32
- *                  (sw_gather4_perm), and `lane` is passed as 4 * lane: the caller shifts once per iteration, not the step per layer. */
+ *                  (sw_gather4_perm), and `lane` is passed as 4 * lane: the caller shifts once per iteration, not the step per layer.
+ * And one says where values come from that depend on the lane and the code alone:
+ *   SW_FORM_EDGEW  a rotating edge's dword address and its two rotate amounts are fields of ONE word per edge and lane that the caller
+ *                  hands in (`ew`: a table it loads, the same for every codeword and iteration) instead of four instructions on
+ *                  lane + shift: the address is the word under 0xfc, the read rotate takes the word itself and the write-back rotate
+ *                  the word >> 8 (v_alignbyte_b32 reads two bits of its amount).  Static table views only. */
 #define SW_FORM_NOWIN 1
 #define SW_FORM_FRESH 2
 #define SW_FORM_VK 4
 #define SW_FORM_MUL 8
-template <int METHOD, int DEG, bool ERA = false, int WAVES = 1, int WAVE = 0, int ZG = 0, int PAIRS = 0, int FORM = 0, class Tab, class Xch = SwNoXch>
+#define SW_FORM_EDGEW 16
+template <int METHOD, int DEG, bool ERA = false, int WAVES = 1, int WAVE = 0, int ZG = 0, int PAIRS = 0, int FORM = 0, class Tab, class Xch = SwNoXch, class Ew = SwNoEw>
 SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, const SwK& K, uint32_t lane, int deg, SwRow cur, bool fresh,
-                          uint32_t rowpar, bool lme, uint32_t era_edges = 0u, uint32_t era_plane = 0u, const Xch& xch = Xch())
+                          uint32_t rowpar, bool lme, uint32_t era_edges = 0u, uint32_t era_plane = 0u, const Xch& xch = Xch(), const Ew& ew = Ew())
 {
     constexpr bool NOWIN = (FORM & SW_FORM_NOWIN) != 0, FRESH = (FORM & SW_FORM_FRESH) != 0;
     constexpr bool VK = (FORM & SW_FORM_VK) != 0, MULF = (FORM & SW_FORM_MUL) != 0;
@@ -734,6 +752,8 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
     constexpr bool STATIC = SwTabStatic<Tab>::value;
     static_assert(!STATIC || (ZG == 0 && DEG > 0 && WAVES == 1 && !ERA && SwTabStatic<Tab>::nz <= DEG), "static table view: per-degree, one-wave, non-erasing instances");
     constexpr int NZ = STATIC ? SwTabStatic<Tab>::nz : SW_ILP * ZG; /* edges 0 .. NZ - 1 need no rotation */
+    constexpr bool EDGEW = (FORM & SW_FORM_EDGEW) != 0;
+    static_assert(!EDGEW || (STATIC && WAVES == 1 && !ERA), "edge words: static table views, one-wave, non-erasing instances");
     constexpr int NJ = DEG > 0 ? DEG : SW_MAX_DEG;
     constexpr bool MINSUM = SW_MINSUM(METHOD);
     /* the minimum search merges aligned groups of four edges (pass 1); the per-degree instances only: in the generic one every
@@ -795,6 +815,9 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
     for (int j = 0; j < NJ; ++j) {
         if (j < NZ) {
             ad[j] = STATIC ? tid4 : tid4 | cbj[j]; /* shift 0: dword `lane` of the column, rows in byte order */
+        } else if (EDGEW) {
+            rq[j] = ew.wa(j); /* (bits 1:0: the read rotate; bits 9:8: the write-back rotate) */
+            ad[j] = rq[j] & cfc;
         } else if ((DEG > 0 || j < deg) && SW_OWN(j)) {
             const uint32_t x4 = tid4 + s4j[j];
 #if SW_DEV
@@ -851,7 +874,7 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
 #define SW_P2_MO(g, j) mo[g]
         /* byte k = En + 120 of row k.  The group's LAST read is consumed first: LDS reads return in order, so the one s_waitcnt in
          * front of it covers the group (in ascending order every edge gets a wait of its own) */
-        _Pragma("unroll") for (int g = SW_ILP - 1; g >= 0; --g) { const int j = j0 + g; if (j < NJ && (DEG > 0 || j < deg) && SW_OWN(j)) r_[g] = j < NZ ? ld[j] : sw_alignbyte(ld[j], ld[j], rq[j]); }
+        _Pragma("unroll") for (int g = SW_ILP - 1; g >= 0; --g) { const int j = j0 + g; if (j < NJ && (DEG > 0 || j < deg) && SW_OWN(j)) r_[g] = j < NZ ? ld[j] : sw_alignbyte(ld[j], ld[j], EDGEW ? ew.w(j) : rq[j]); }
         if (FRESH) { /* no shift, no selector build, no look-up: constants */
             SW_EDGES(x_[g] = 0u; s_[g] = c0642; k_[g] = k_fresh;)
         } else {
@@ -1061,7 +1084,7 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
         }                                                                                                            \
         SW_EDGES(lm[g] = sw_upd2_limit<MINSUM>(ms[j], d_[g], u2, c80);)                                              \
         SW_EDGES(EN[g] = sw_upd2_en(mo[g], lm[g], zb[g], d_[g], cm27);)                                              \
-        SW_EDGES(if (j >= NZ) EN[g] = sw_alignbyte(EN[g], EN[g], 4u - rq[j]);)                                       \
+        SW_EDGES(if (j >= NZ) EN[g] = sw_alignbyte(EN[g], EN[g], EDGEW ? rq[j] >> 8 : 4u - rq[j]);)                  \
         if (NSTREE) sw_sign_quad<NJ>(ns, ms, j0, deg, DEG > 0, K.c55, K.c33, K.c0f);                                 \
         else SW_EDGES(sw_sign_edge(ns, ms[j], j, cbit[j & 7]);)                                                      \
     }
@@ -1069,6 +1092,7 @@ SW_FN SwRow sw_layer_step(const SwLds& lds, const Tab& tab, const SwParams& p, c
     {                                                                                                                \
         const int j0 = (J0);                                                                                         \
         SW_EDGES(lds.wr32(ad[j], EN[g], SW_COL(j));)                                                                 \
+        if (EDGEW) ew.at(j0);                                                                                        \
     }
     uint32_t en0[SW_ILP], en1[SW_ILP];
     SW_PASS2_ARITH(0, en0)

@@ -205,6 +205,8 @@ SYMBOLS = {
     "lnsfaid_select_zero_shift": (C.c_int, [C.c_void_p, C.c_int32]),
     "lnsfaid_zero_shift_groups": (C.c_int, [C.c_void_p, C.POINTER(C.c_int32), C.c_int32]),
     "lnsfaid_window_free": (C.c_int, [C.c_void_p]),
+    "lnsfaid_select_edge_words": (C.c_int, [C.c_void_p, C.c_int32]),
+    "lnsfaid_edge_words": (C.c_int, [C.c_void_p]),
     "lnsfaid_code_zero_shift_order": (C.c_int, [C.POINTER(Code), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "lnsfaid_code_bf_walk": (C.c_int, [C.POINTER(Code), C.c_int32, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                       C.POINTER(C.c_int32)]),
@@ -1349,6 +1351,16 @@ class Decoder:
         """the next decode launches the layer-static kernel's window-free form (lnsfaid_kernel4w.hip)"""
         on = self.lib.lnsfaid_window_free(self.ctx)
         self._check(min(on, 0), "lnsfaid_window_free")
+        return on == 1
+
+    def select_edge_words(self, on):
+        """True (default): the edge-word twin where the window-free form applies; False: lnsfaid_kernel4w.hip (lnsfaid_select_edge_words)"""
+        self._check(self.lib.lnsfaid_select_edge_words(self.ctx, 1 if on else 0), "lnsfaid_select_edge_words")
+
+    def edge_words(self):
+        """the next decode launches the window-free form's edge-word twin (lnsfaid_kernel4e.hip)"""
+        on = self.lib.lnsfaid_edge_words(self.ctx)
+        self._check(min(on, 0), "lnsfaid_edge_words")
         return on == 1
 
     def kernel_residency(self):
