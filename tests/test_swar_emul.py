@@ -7,6 +7,7 @@ import os
 import numpy as np
 import pytest
 
+import codeword_cases as cc
 import oracle_abi as oa
 
 EMU = os.path.join(oa.ORACLE_DIR, "libswar_emul.so")
@@ -20,7 +21,10 @@ def _both(abi, code50, method, eb_n0, n_iter, spec, seed=101, max_iter=10):
     em.swar_emul_layered.restype = C.c_int
     em.swar_emul_layered.argtypes = [C.POINTER(abi.Code), C.POINTER(abi.Cfg), C.c_void_p, C.c_int, C.c_int, C.c_void_p]
     cfg = abi.default_cfg(method, max_iter)
-    fix = oa.ReferenceChannel(code50, seed, 13.0).groups(eb_n0, 1)
+    if isinstance(eb_n0, str):  # a batch of tests/codeword_cases.py: its first group stands in place of the all-zero channel draw
+        fix = np.ascontiguousarray(cc.batch(code50, method, eb_n0)[:32 * code50.N])
+    else:
+        fix = oa.ReferenceChannel(code50, seed, 13.0).groups(eb_n0, 1)
     o = oa.Oracle(code50, cfg)
     ref = np.empty(32 * code50.N, dtype=np.int8)
     assert lib.lnsfaid_oracle_layered_en(o.h, fix.ctypes.data, n_iter, ref.ctypes.data) == 0
@@ -30,14 +34,21 @@ def _both(abi, code50, method, eb_n0, n_iter, spec, seed=101, max_iter=10):
 
 
 @pytest.mark.parametrize("method,eb_n0,n_iter,spec", [(2, 3.4, 1, 1), (2, 3.4, 3, 1), (2, 3.0, 10, 0), (2, 4.2, 10, 1),
-                                                       (1, 3.4, 10, 1), (4, 3.6, 7, 0), (5, 3.4, 10, 1), (5, 3.6, 10, 0)])
+                                                       (1, 3.4, 10, 1), (4, 3.6, 7, 0), (5, 3.4, 10, 1), (5, 3.6, 10, 0),
+                                                       (2, "mixed", 1, 1), (2, "mixed", 10, 0), (4, "mixed", 10, 1), (5, "mixed", 10, 1),
+                                                       (2, "minus8", 10, 1), (5, "minus8", 10, 0), (2, "hard4", 10, 1), (1, "hard4", 10, 0)])
 def test_swar_layer_step_equals_the_oracle(abi, code50, method, eb_n0, n_iter, spec):
     """En of all 32 lanes after n_iter iterations (no early stop): saturations at +-31, zero messages, ties between the minima,
-    the back-tracked sign and the error-floor tables (DecodeMethod 5) / selective offsets (OMS loop) all pass through here."""
+    the back-tracked sign and the error-floor tables (DecodeMethod 5) / selective offsets (OMS loop) all pass through here.
+    eb_n0: the Eb/N0 of an all-zero channel draw, or the name of a random-codeword batch of tests/codeword_cases.py (hard4: every
+    |LLR| equal, so every comparison of the minima is a tie), where En must reach the positive limit as well as the negative one."""
     ref, got = _both(abi, code50, method, eb_n0, n_iter, spec)
     bad = np.nonzero(ref != got)[0]
     assert bad.size == 0, "En differs at %s: oracle %s, layer step %s" % (bad[:8].tolist(), ref[bad[:8]].tolist(), got[bad[:8]].tolist())
-    if n_iter == 10 and eb_n0 >= 3.4:
+    if isinstance(eb_n0, str):
+        if n_iter == 10:
+            assert ref.max() == 31 and ref.min() == -31, (ref.min(), ref.max())
+    elif n_iter == 10 and eb_n0 >= 3.4:
         assert np.abs(ref).max() == 31  # these batches reach the saturation limit: the merged clamp is exercised
 
 
@@ -57,7 +68,8 @@ def test_swar_layer_step_runs_normalised_min_sum_with_one_factor(abi, code50, fa
     fix = oa.ReferenceChannel(code50, 163, 13.0).groups(eb_n0, 1)
     ref = np.empty(32 * code50.N, dtype=np.int8)
     got = np.empty(32 * code50.N, dtype=np.int8)
-    assert lib.lnsfaid_oracle_layered_en(oa.Oracle(code50, cfg).h, fix.ctypes.data, n_iter, ref.ctypes.data) == 0
+    o = oa.Oracle(code50, cfg)  # (kept in a name: a temporary would be destroyed before the call that uses its handle)
+    assert lib.lnsfaid_oracle_layered_en(o.h, fix.ctypes.data, n_iter, ref.ctypes.data) == 0
     assert em.swar_emul_layered(C.byref(code50.code), C.byref(cfg), fix.ctypes.data, n_iter, spec, got.ctypes.data) == 0
     bad = np.nonzero(ref != got)[0]
     assert bad.size == 0, "En differs at %s: oracle %s, layer step %s" % (bad[:8].tolist(), ref[bad[:8]].tolist(), got[bad[:8]].tolist())
